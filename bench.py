@@ -2,8 +2,16 @@
 """Headline benchmark (BASELINE.json): queries/sec + index-build GB/s on TPC-H SF100-shaped data,
 filter (FilterIndexRule, TPC-H Q6) + join (JoinIndexRule, TPC-H Q3-style) on 1/2/4/8 MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--sf 100]
+    python bench.py --gpus N --steps K --warmup W [--sf 100] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: data (generated once per data dir), the
+three index builds, W warm-up steps, K timed steps of the headline placement, and the JSON line
+(``value``, ``ms_per_step`` = milliseconds per timed step, the build figures).  ``--full`` adds
+every side measurement and check described below (cold first queries, the join-index run, the
+replicated placement, per-query latencies, ``q3_full``, the N = 1 side configs and the
+cross-check against the un-indexed plan).  ``--dump-outputs DIR`` writes the rows the last timed
+step's two queries returned as ``DIR/<name>.npy`` (float64, one array per result column).
 
 One step = one Q6 filter query + one Q3-style join query, each with fresh literals, through
 the full engine path (analysis, then a plan-cache lookup: a hit re-binds the new literals into
@@ -151,7 +159,17 @@ def main():
     ap.add_argument("--host-breakdown", type=int, default=0, metavar="N",
                     help="after the timed steps, time N queries phase by phase on the host "
                          "(DataFrame build / plan / submit / result), reported as host_breakdown")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: cold first "
+                         "queries, the join-index run, the replicated placement (N > 1), "
+                         "per-query latencies, q3_full, the N = 1 side configs (q3_3way, hybrid) "
+                         "and the cross-check against the un-indexed plan")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last timed step "
+                         "(what collect() returned) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -377,39 +395,42 @@ def main():
     # cold: the first query of each kind after createIndex (index HBM load, kernel compile when
     # the on-disk code-object cache is empty, join-index build) — not part of the timed steps
     s.conf.set("spark.hyperspace.mi.index.placement", "sharded")
-    jit0 = dict(jit_mod.JIT_STATS) if jit_mod is not None else {}
-    from hyperspace_amd.utils.tracing import TRACER as _TR, format_report as _fmt
-    _TR.reset()
-    cprof = None
-    if os.environ.get("HS_BENCH_COLD_PROFILE") and rank == 0:
-        import cProfile
-        cprof = cProfile.Profile()
-        cprof.enable()
-    cold = {"q6_cold_ms": one_query_ms(q6, 999), "q3_cold_ms": one_query_ms(q3, 999)}
-    if cprof is not None:
-        import io
-        import pstats
-        cprof.disable()
-        buf = io.StringIO()
-        pstats.Stats(cprof, stream=buf).sort_stats("tottime").print_stats(25)
-        log(rank, "[bench] cold queries host profile\n" + buf.getvalue())
-    if _TR.profile:
-        log(rank, "[bench] cold queries stage profile\n" + _fmt(_TR.report()))
-    if jit_mod is not None:
-        # kernels the cold queries compiled with hipRTC vs loaded from the code-object cache
-        # (the AOT set of __graft_entry__.build covers the bench's shapes)
-        cold["cold_kernels_compiled"] = jit_mod.JIT_STATS["compiled"] - jit0.get("compiled", 0)
-        cold["cold_kernels_loaded"] = jit_mod.JIT_STATS["loaded"] - jit0.get("loaded", 0)
-    log(rank, f"[bench] cold first queries {cold}")
-
     from hyperspace_amd.utils.tracing import TRACER, format_report
-    # the headline (last) placement is sharded (one query stream over the N GPUs); replicated
-    # runs first as a side key
-    modes = ["replicated", "sharded"] if world > 1 and args.placement == "both" else \
-        [args.placement if world > 1 else "sharded"]
+    cold = {}
+    if args.full:
+        jit0 = dict(jit_mod.JIT_STATS) if jit_mod is not None else {}
+        TRACER.reset()
+        cprof = None
+        if os.environ.get("HS_BENCH_COLD_PROFILE") and rank == 0:
+            import cProfile
+            cprof = cProfile.Profile()
+            cprof.enable()
+        cold = {"q6_cold_ms": one_query_ms(q6, 999), "q3_cold_ms": one_query_ms(q3, 999)}
+        if cprof is not None:
+            import io
+            import pstats
+            cprof.disable()
+            buf = io.StringIO()
+            pstats.Stats(cprof, stream=buf).sort_stats("tottime").print_stats(25)
+            log(rank, "[bench] cold queries host profile\n" + buf.getvalue())
+        if TRACER.profile:
+            log(rank, "[bench] cold queries stage profile\n" + format_report(TRACER.report()))
+        if jit_mod is not None:
+            # kernels the cold queries compiled with hipRTC vs loaded from the code-object cache
+            # (the AOT set of __graft_entry__.build covers the bench's shapes)
+            cold["cold_kernels_compiled"] = jit_mod.JIT_STATS["compiled"] - jit0.get("compiled", 0)
+            cold["cold_kernels_loaded"] = jit_mod.JIT_STATS["loaded"] - jit0.get("loaded", 0)
+        log(rank, f"[bench] cold first queries {cold}")
+
+    # the headline (last) placement is sharded (one query stream over the N GPUs); with --full
+    # replicated runs first as a side key
+    if world > 1 and args.placement == "both":
+        modes = ["replicated", "sharded"] if args.full else ["sharded"]
+    else:
+        modes = [args.placement if world > 1 else "sharded"]
     ji_key = "spark.hyperspace.mi.joinIndex.enabled"
     ji_run = None
-    if on_gpu:
+    if on_gpu and args.full:
         # side key: the same steps through the cached join index (headline placement)
         s.conf.set(ji_key, "true")
         ji_run = timed(modes[-1])
@@ -434,10 +455,11 @@ def main():
         dtq = (time.perf_counter() - tq) / reps
         lat[name] = round((dist.all_reduce_max_float(dtq) if dist else dtq) * 1000, 3)
 
-    latency("q6_filter_ms", q6)
-    latency("q3_join_ms", q3)
+    if args.full:
+        latency("q6_filter_ms", q6)
+        latency("q3_join_ms", q3)
     q3f = None
-    if on_gpu:
+    if on_gpu and args.full:
         # side key: TPC-H Q3's full shape (3-column group, top 10), fresh literals per query,
         # every query through the full engine path; warm-up first (kernel compile + table size)
         for i in range(2):
@@ -458,20 +480,23 @@ def main():
                        "o_orderdate LIMIT 10 (device hash aggregate + top-k)"}
         if backend.last_path != "native":
             raise RuntimeError(f"q3_full fell back: {backend.fallback_reason}")
-    if on_gpu:
+    if on_gpu and args.full:
         s.conf.set(ji_key, "true")
         latency("q3_join_index_ms", q3)
         s.conf.set(ji_key, "false")
     lat.update(cold)
     hb = _host_breakdown(args.host_breakdown, (q6, q3), backend, sync, barrier) \
         if args.host_breakdown and on_gpu else None
-    side = _side_configs(args, sf) if on_gpu and world == 1 and not args.no_side else {}
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, results[-1])
+    side = _side_configs(args, sf) \
+        if args.full and on_gpu and world == 1 and not args.no_side else {}
 
     # ---------------------------------------------------------------- cross-check
     check = None
     # multi-rank: the un-indexed plan runs on the host oracle over all files (slow), so only
     # cross-check small scale factors there
-    if not args.no_crosscheck and (world == 1 or sf <= 10):
+    if args.full and not args.no_crosscheck and (world == 1 or sf <= 10):
         s.disableHyperspace()
         tc = time.perf_counter()
         first = runs[final]["first"]   # the literals of this rank's first timed step
@@ -518,8 +543,11 @@ def main():
                "index_build_s": round(build_s, 3), "index_codec": args.codec,
                "bytes_over_xgmi": int(xgmi_bytes),
                "index_bytes_on_disk": _dir_bytes(idx_root),
-               "index_build": per_index, "latency": lat, "warmup_s": round(warm_s, 3),
-               "datagen_s": round(gen_s, 2), "crosscheck": check, "inflight": args.inflight}
+               "index_build": per_index, "warmup_s": round(warm_s, 3),
+               "datagen_s": round(gen_s, 2), "inflight": args.inflight, "full": args.full}
+        if args.full:
+            out["latency"] = lat
+            out["crosscheck"] = check
         if q3f is not None:
             out["q3_full"] = q3f
         if hb is not None:
@@ -550,6 +578,25 @@ def main():
     if dist:
         barrier()
         torch.distributed.destroy_process_group()
+
+
+def _dump_outputs(out_dir, step_result) -> None:
+    """Write what one step's two queries returned to their caller (``collect()``'s rows) as
+    ``<out_dir>/<name>.npy``, float64, one array per result column: ``q6_revenue`` (one row) and
+    ``q3_o_shippriority`` / ``q3_revenue`` / ``q3_lines`` (one row per group, ordered by the group
+    key; a NULL is NaN).  The data and the literals of a step depend only on the arguments, so two
+    runs with the same arguments write comparable files."""
+    import numpy as np
+    q6_rows, q3_rows = step_result
+    q3_rows = sorted(q3_rows, key=lambda r: (r[0] is not None, r[0]))
+    cols = {"q6_revenue": [r[0] for r in q6_rows],
+            "q3_o_shippriority": [r[0] for r in q3_rows],
+            "q3_revenue": [r[1] for r in q3_rows],
+            "q3_lines": [r[2] for r in q3_rows]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, vals in cols.items():
+        arr = np.array([np.nan if v is None else v for v in vals], dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def _side_configs(args, sf) -> dict:

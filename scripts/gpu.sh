@@ -10,7 +10,8 @@
 #   TAG           output prefix (default run)
 #   TESTS         test files / dirs for `tests` (default tests)
 #   PYTEST_ARGS   extra pytest args for `tests` (no spaces inside one argument)
-#   BENCH_ARGS    args for `bench` / `prof` / `hostprof` (default SF100, 100 / 40 steps)
+#   BENCH_ARGS    args for `bench` / `prof` / `hostprof` (default SF100, 100 / 40 steps; `bench`,
+#                 `prof` and `benchtrace` default to --full: side keys, cross-check)
 #   SF            scale factor for `pmc`, `configs`, `q3f`, `dist` (defaults 10 / 100 / 100 / 2)
 #   CONFIGS       benchmarks/configs.py configs for `configs` (default "sf10_filter q3_3way hybrid")
 #   PMC_REGEX     kernel-name regex for `pmc` (default hs_jit_)
@@ -40,7 +41,7 @@ step_smoke() {
 }
 
 step_bench() {
-  timeout -k 10 ${BENCH_TIMEOUT:-700} python bench.py ${BENCH_ARGS:---sf 100 --steps 100 --warmup 5 --host-breakdown 100} \
+  timeout -k 10 ${BENCH_TIMEOUT:-700} python bench.py ${BENCH_ARGS:---sf 100 --steps 100 --warmup 5 --host-breakdown 100 --full} \
     > "${O}_bench.json" 2> "${O}_bench.log"
 }
 
@@ -52,7 +53,7 @@ step_hostprof() {
 step_prof() {
   (cd /tmp && export TMPDIR=/tmp &&
    timeout -k 10 700 rocprofv3 --kernel-trace --stats --output-format csv -d "${O}_prof" -o run \
-     -- python3 "$REPO/bench.py" ${BENCH_ARGS:---sf 100 --steps 40 --warmup 5 --no-crosscheck} \
+     -- python3 "$REPO/bench.py" ${BENCH_ARGS:---sf 100 --steps 40 --warmup 5 --full --no-crosscheck} \
      > "${O}_prof.json" 2> "${O}_prof.log") || return $?
   find "${O}_prof" -name "*kernel_stats.csv" -exec cp {} "${O}_kernel_stats.csv" \;
 }
@@ -62,7 +63,7 @@ step_benchtrace() {
   # steps are the run of tags / bits-scan / scan kernels after the join-index side run
   (cd /tmp && export TMPDIR=/tmp &&
    timeout -k 10 700 rocprofv3 --kernel-trace --output-format csv -d "${O}_btrace" -o run \
-     -- python3 "$REPO/bench.py" ${BENCH_ARGS:---sf 100 --steps 60 --warmup 5 --no-crosscheck} \
+     -- python3 "$REPO/bench.py" ${BENCH_ARGS:---sf 100 --steps 60 --warmup 5 --full --no-crosscheck} \
      > "${O}_benchtrace.json" 2> "${O}_benchtrace.log") || return $?
   local f
   f=$(find "${O}_btrace" -name "*kernel_trace.csv" | head -n 1)
@@ -209,7 +210,7 @@ step_dist() {
   HS_BENCH_DIR=/tmp/hs_bench_dist HS_DIST_BACKEND=gloo timeout -k 10 700 \
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
     --master-port 29517 bench.py --gpus $n --sf ${SF:-2} --steps ${DIST_STEPS:-100} --warmup 3 \
-    --buckets 16 ${DIST_ARGS} > "${O}_dist$n.json" 2> "${O}_dist$n.log"
+    --buckets 16 --full ${DIST_ARGS} > "${O}_dist$n.json" 2> "${O}_dist$n.log"
 }
 
 step_build() {

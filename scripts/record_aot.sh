@@ -6,4 +6,5 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 mkdir -p gpurun_out/aot
 HS_JIT_RECORD=gpurun_out/aot timeout -k 10 600 python3 -u bench.py --steps 3 \
+  --full \
   > gpurun_out/record_aot.json 2> gpurun_out/record_aot.log

@@ -200,8 +200,8 @@ def test_spmd_device_executor(tmp_path, spmd_data, device):
 
 
 def test_bench_two_ranks_reports_both_placements(tmp_path):
-    """bench.py under torch.distributed (2 gloo ranks, host engine, tiny scale factor): one JSON
-    line from rank 0 with the sharded (strong scaling: one query stream over co-partitioned
+    """bench.py --full under torch.distributed (2 gloo ranks, host engine, tiny scale factor): one
+    JSON line from rank 0 with the sharded (strong scaling: one query stream over co-partitioned
     buckets, the same placement and label as at N = 1) headline value and the replicated numbers
     (weak scaling: one query stream per rank over read replicas) as a side key, and the indexed
     results cross-checked against the un-indexed plan."""
@@ -209,11 +209,13 @@ def test_bench_two_ranks_reports_both_placements(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    # gloo also where a GPU is present: the default there is RCCL, one device per rank
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HS_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(29000 + os.getpid() % 2000),
            os.path.join(root, "bench.py"), "--gpus", "2", "--device", "cpu", "--sf", "0.02",
-           "--steps", "2", "--warmup", "1", "--buckets", "4", "--data-dir", str(tmp_path)]
+           "--steps", "2", "--warmup", "1", "--buckets", "4", "--data-dir", str(tmp_path),
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
