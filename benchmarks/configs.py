@@ -25,6 +25,10 @@ against the same query with Hyperspace disabled (the reference's correctness ora
   covering indexes on all three tables; queries, then +10% appended fact files and an
   incremental ``refreshIndex``, then the same queries on the refreshed index.  Results are
   checked against an independent pyarrow-dataset computation (not this engine's host path).
+* ``like`` — ``p_name LIKE '%green%'``-style filters plus an aggregate over a ``part``-shaped
+  table (200k x SF rows, every name distinct) through an index that includes the
+  dictionary-coded name column; also times the dictionary match kernel against the host route
+  (``match_like`` + pack + upload) at 10^4, 10^6 and all entries.
 """
 import argparse
 import datetime
@@ -538,9 +542,132 @@ def config_tpcds_3way(args):
     return out
 
 
+# -------------------------------------------------------------------------------------- LIKE
+_COLORS = ("almond antique aquamarine azure beige bisque black blanched blue blush brown "
+           "burlywood burnished chartreuse chiffon chocolate coral cornflower cornsilk cream "
+           "cyan dark deep dim dodger drab firebrick floral forest frosted gainsboro ghost "
+           "goldenrod green grey honeydew hot indian ivory khaki lace lavender lawn lemon light "
+           "lime linen magenta maroon medium metallic midnight mint misty moccasin navajo navy "
+           "olive orange orchid pale papaya peach peru pink plum powder puff purple red rose "
+           "rosy royal saddle salmon sandy seashell sienna sky slate smoke snow spring steel "
+           "tan thistle tomato turquoise violet wheat white yellow").split()
+
+
+def _part_table(n, seed=17):
+    """A TPC-H ``part``-shaped table: ``p_name`` is five colour words and the part key, so
+    every name is distinct (the dictionary has ``n`` entries)."""
+    import numpy as np
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    rng = np.random.default_rng(seed)
+    colors = pa.array(_COLORS)
+    words = [colors.take(pa.array(rng.integers(0, len(_COLORS), n).astype(np.int32)))
+             for _ in range(5)]
+    key = np.arange(n, dtype=np.int64)
+    name = pc.binary_join_element_wise(*words, pc.cast(pa.array(key), pa.string()), " ")
+    return pa.table({"p_partkey": key, "p_name": name,
+                     "p_size": rng.integers(1, 51, n).astype(np.int32),
+                     "p_retailprice": np.round(900 + rng.random(n) * 1200, 2)})
+
+
+def _median_ms(fn, runs, device):
+    ts = []
+    for _ in range(runs):
+        _sync(device)
+        t0 = time.perf_counter()
+        fn()
+        _sync(device)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    ts.sort()
+    return round(ts[len(ts) // 2], 4)
+
+
+def config_like(args):
+    """``p_name LIKE '%green%'`` plus an aggregate over a part-shaped table (200k x SF rows)
+    whose name column is dictionary-coded and included in a ``p_size`` index: q/s on the
+    device against the host engine, and the dictionary match itself - the ``hs_dict_like``
+    kernel against the host route (``match_like`` + pack + upload) at 10^4, 10^6 and all
+    entries, medians of ``--like-runs`` alternating runs."""
+    import pyarrow.parquet as pq
+    from hyperspace_amd import Hyperspace, IndexConfig, col, count, sum_
+    n = int(200_000 * args.sf)
+    root = os.path.join(args.data_dir, f"cfg_like_sf{args.sf:g}")
+    shutil.rmtree(root, ignore_errors=True)
+    os.makedirs(os.path.join(root, "part"))
+    t = _part_table(n)
+    nfiles = 8
+    step = (n + nfiles - 1) // nfiles
+    for i in range(nfiles):
+        pq.write_table(t.slice(i * step, step), os.path.join(root, "part", f"part-{i}.parquet"))
+    del t
+    s = _session(root, args.device, args.buckets)
+    hs = Hyperspace(s)
+    part = s.read.parquet(os.path.join(root, "part"))
+    dt, _ = _build(hs, part, IndexConfig("part_size", ["p_size"], ["p_name", "p_retailprice"]),
+                   args.device)
+    Hyperspace.enable(s)
+    pats = ["%green%", "%dark%rose%", "forest%", "%_lmond %", "%99"]
+
+    def q(i):
+        return part.filter((col("p_size") >= 1 + i % 3) & col("p_name").like(pats[i % len(pats)])) \
+            .agg(sum_("p_retailprice").alias("price"), count("*").alias("n"))
+    used = "part_size" in q(0).queryExecution.executed_plan.tree_string()
+    got = [_rows(q(i)) for i in range(len(pats))]
+    path = getattr(s.backend(), "last_path", None)
+    reason = getattr(s.backend(), "fallback_reason", None)
+    k = args.steps * 5
+    el = _timed_loop(lambda i: q(i).collect(), k, args.device)
+    out = {"config": "like", "device": args.device, "sf": args.sf, "rows": n,
+           "index_build_s": round(dt, 3), "index_used": used, "path": path,
+           "fallback_reason": reason, "queries_per_s": round(k / el, 2)}
+    if args.device == "gpu":
+        from hyperspace_amd.exec import like as LK
+        from hyperspace_amd.ops import kernels as K
+        import torch
+        out["like_stats"] = dict(LK.LIKE_STATS)
+        # the dictionary the queries matched: the resident index table's p_name column
+        dicts = [d.dictionary for d in LK._DEV_DICTS.values()]
+        full = max(dicts, key=len)
+        prog = LK.compile_like("%green%")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        sizes = sorted({min(10_000, len(full)), min(1_000_000, len(full)), len(full)})
+        out["dict_match"] = []
+        for m in sizes:
+            d = full.slice(0, m)
+            tu0 = time.perf_counter()
+            dd = LK.device_dictionary(d, dev)
+            _sync("gpu")
+            upload_ms = (time.perf_counter() - tu0) * 1e3
+            kw = K.dict_like(dd, prog)
+            hw = torch.from_numpy(LK.host_bitmap_words(d, prog.pattern)).to(dev)
+            same = bool(torch.equal(kw, hw))
+            kt, ht = [], []
+            for _ in range(args.like_runs):          # alternating, one run each
+                kt.append(_median_ms(lambda: K.dict_like(dd, prog), 1, "gpu"))
+                ht.append(_median_ms(lambda: torch.from_numpy(
+                    LK.host_bitmap_words(d, prog.pattern)).to(dev), 1, "gpu"))
+            kt.sort()
+            ht.sort()
+            out["dict_match"].append({
+                "entries": m, "mean_entry_bytes": round(int(dd.chars.numel()) / max(m, 1), 2),
+                "max_entry_bytes": dd.max_len, "runs": args.like_runs,
+                "hs_dict_like_ms": kt[len(kt) // 2], "host_route_ms": ht[len(ht) // 2],
+                "hs_dict_like_ms_min_max": [kt[0], kt[-1]], "host_route_ms_min_max": [ht[0], ht[-1]],
+                "dictionary_upload_once_ms": round(upload_ms, 3), "bitmaps_equal": same})
+    # the host engine on the same queries (and the cross-check)
+    s.conf.set("spark.hyperspace.mi.execution.device", "cpu")
+    ref = [_rows(q(i)) for i in range(len(pats))]
+    kh = max(3, args.steps)
+    el_h = _timed_loop(lambda i: q(i).collect(), kh, "cpu")
+    out["host_engine_queries_per_s"] = round(kh / el_h, 3)
+    out["match"] = all(_close(a, b) for a, b in zip(got, ref))
+    out["matching_rows"] = [g[0][1] for g in got]
+    return out
+
+
 CONFIGS = {"csv10k": config_csv10k, "sf10_filter": config_sf10_filter, "hybrid": config_hybrid,
            "q3_3way": config_q3_3way, "tpcds_3way": config_tpcds_3way,
-           "streamed": config_streamed}
+           "streamed": config_streamed, "like": config_like}
 
 
 def main():
@@ -554,6 +681,8 @@ def main():
     ap.add_argument("--tpcds-sf", type=float, default=300.0)
     ap.add_argument("--hbm-budget-gb", type=float, default=8.0,
                     help="streamed: the build and resident-table HBM budgets")
+    ap.add_argument("--like-runs", type=int, default=11,
+                    help="like: timed runs per dictionary size and route (medians reported)")
     args = ap.parse_args()
     if args.device == "gpu":
         import torch

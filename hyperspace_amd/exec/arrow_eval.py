@@ -109,6 +109,11 @@ def eval_expr(e: E.Expression, t: pa.Table):
             vtype = pa.float64()
         vs = pa.array(lits, vtype if not pa.types.is_dictionary(vtype) else vtype.value_type)
         return pc.is_in(v, value_set=vs)
+    if isinstance(e, E.Like):
+        v = eval_expr(e.child, t)
+        if pa.types.is_dictionary(v.type):
+            v = pc.cast(v, v.type.value_type)
+        return pc.match_like(v, e.pattern)
     if type(e) in _ARITH:
         a, b = _operands(e, t)
         return _ARITH[type(e)](a, b)

@@ -2,7 +2,8 @@
 
 * Predicates -> CNF of leaf comparisons (``Pred`` structs): NOT is pushed into the leaves
   (De Morgan, operator flip), OR-of-ANDs is distributed, string literals become dictionary-code
-  bounds, dates/timestamps become integers.
+  bounds, dates/timestamps become integers, ``LIKE`` over a dictionary column becomes a code
+  comparison, a code interval or a bitmap over the codes (``exec/like.py``).
 * Aggregate inputs -> products of affine terms ``prod(alpha + beta * col)``.
 Anything outside these shapes raises ``Unsupported`` and the executor falls back.
 """
@@ -17,6 +18,7 @@ import pyarrow as pa
 
 from ..ops import _lib as NL
 from ..plan import expressions as E
+from .like import LIKE_STATS, compile_like, like_bitmap, prefix_code_interval
 
 
 class Unsupported(Exception):
@@ -43,7 +45,7 @@ class Leaf:
         self.lit = lit      # cmp_lit: the Literal node ``value`` came from (``rebind``)
 
     def negate(self) -> "Leaf":
-        if self.kind in ("cmp_lit", "cmp_col", "in", "bitmap"):
+        if self.kind in ("cmp_lit", "cmp_col", "in", "bitmap", "like"):
             return Leaf(self.kind, _NEG[self.op], self.attr, self.attr2, self.value, self.values,
                         self.lit)
         if self.kind == "isnull":
@@ -130,6 +132,10 @@ class KeyBitmap(E.Expression):
 def _leaf(e: E.Expression) -> Leaf:
     if isinstance(e, KeyBitmap):
         return Leaf("bitmap", NL.OP_EQ, e.attr, value=e)
+    if isinstance(e, E.Like):
+        if not isinstance(e.child, E.Attribute):
+            raise Unsupported(f"LIKE over {type(e.child).__name__}")
+        return Leaf("like", NL.OP_EQ, e.child, value=compile_like(e.pattern))
     if isinstance(e, E.Literal) and isinstance(e.value, bool):
         return Leaf("const", 0, None, value=e.value)
     if type(e) in _OPS:
@@ -300,6 +306,38 @@ def bind(clauses: List[List[Leaf]], col_info: Callable[[E.Attribute], ColumnInfo
                 b.buffers.append(kb.words)
                 b.preds.append(NL.Pred(NL.PK_BITMAP, leaf.op, info.slot, 0, group,
                                        kb.words.numel(), kb.base, 0.0, kb.words.data_ptr()))
+            elif leaf.kind == "like":
+                b.rebindable = False
+                if info.dictionary is None:
+                    raise Unsupported("LIKE on a column without a dictionary")
+                prog = leaf.value
+                if prog.cls == "exact":
+                    LIKE_STATS["exact"] += 1
+                    what, op, code = _dict_code_bound(info, leaf.op, prog.literal.decode("utf-8"))
+                    if what == "false":
+                        continue
+                    if what == "notnull":
+                        b.preds.append(NL.Pred(NL.PK_NOT_NULL, 0, info.slot, 0, group, 0, 0, 0.0, None))
+                    else:
+                        b.preds.append(NL.Pred(NL.PK_INT_LIT, op, info.slot, 0, group, 0, int(code),
+                                               0.0, None))
+                elif prog.cls == "prefix" and leaf.op == NL.OP_EQ and len(cl) == 1:
+                    # code interval [lo, hi): two clauses (a clause cannot hold a conjunction)
+                    LIKE_STATS["interval"] += 1
+                    lo, hi = prefix_code_interval(info.dictionary, prog.literal)
+                    if lo >= hi:
+                        continue
+                    b.preds.append(NL.Pred(NL.PK_INT_LIT, NL.OP_GE, info.slot, 0, group, 0, lo, 0.0, None))
+                    group += 1
+                    b.preds.append(NL.Pred(NL.PK_INT_LIT, NL.OP_LT, info.slot, 0, group, 0, hi, 0.0, None))
+                elif len(info.dictionary) == 0:
+                    # an empty dictionary: every row is NULL, nothing matches either way
+                    continue
+                else:
+                    words = like_bitmap(info.dictionary, prog, device)
+                    b.buffers.append(words)
+                    b.preds.append(NL.Pred(NL.PK_BITMAP, leaf.op, info.slot, 0, group,
+                                           words.numel(), 0, 0.0, words.data_ptr()))
             elif leaf.kind == "in":
                 b.rebindable = False
                 vals = [v for v in leaf.values if v is not None]

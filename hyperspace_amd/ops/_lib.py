@@ -210,6 +210,7 @@ def lib():
     _sig(L.hs_run_bitmap_tags, I, P, I64, I64, P, I64, P, P)
     _sig(L.hs_key_bitmap, I, P, I64, I64, I64, P, P, P)
     _sig(L.hs_bitmap_popcount, I, P, I64, P, P)
+    _sig(L.hs_dict_like, I, P, P, I64, P, P, I, P, P)
     _sig(L.hs_str_hash64, I, P, P, I64, P, P)
     _sig(L.hs_str_gather, I, P, P, P, I64, P, P)
     _sig(L.hs_str_differ, I, P, P, P, P, I64, P, P)

@@ -505,6 +505,28 @@ def key_bitmap(col, lo: int, nbits: int, check: bool = True):
     return words, bool(f & 1)
 
 
+def dict_like(dev_dict, program):
+    """int64 words of the bitmap "dictionary entry i matches the LIKE program"
+    (csrc/kernels/dict_like.hip): ``ceil(n / 64)`` words, all written by the kernel, bits past
+    ``n`` zero.  ``dev_dict``: ``exec.like.DeviceDictionary`` (device bytes + int64 offsets);
+    ``program``: ``exec.like.LikeProgram``.  No readback; an empty dictionary launches nothing.
+    The caller checks the kernel's caps (``exec.like.kernel_eligible``)."""
+    torch = _torch()
+    n = int(dev_dict.n)
+    dev = dev_dict.offsets.device
+    words = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev)
+    if n == 0:
+        return words
+    ntok = len(program.kinds)
+    toks = torch.from_numpy(np.frombuffer(bytes(program.kinds) + bytes(program.bytes_) + b"\0",
+                                          dtype=np.uint8).copy()).to(dev)
+    NL.check(NL.lib().hs_dict_like(NL.ptr(dev_dict.chars), NL.ptr(dev_dict.offsets), n,
+                                   C.c_void_p(toks.data_ptr()),
+                                   C.c_void_p(toks.data_ptr() + ntok), ntok, NL.ptr(words),
+                                   NL.stream_ptr()), "hs_dict_like")
+    return words
+
+
 def bitmap_popcount(words) -> int:
     torch = _torch()
     out = torch.zeros(1, dtype=torch.int64, device=words.device)

@@ -89,6 +89,19 @@ class Column:
     def isNotNull(self):
         return Column(E.IsNotNull(self.expr))
 
+    def like(self, pattern: str):
+        """SQL ``LIKE``: ``%`` any run, ``_`` one character, ``\\`` escapes either."""
+        return Column(E.Like(self.expr, pattern))
+
+    def startswith(self, s: str):
+        return Column(E.Like(self.expr, E.escape_like(s) + "%"))
+
+    def endswith(self, s: str):
+        return Column(E.Like(self.expr, "%" + E.escape_like(s)))
+
+    def contains(self, s: str):
+        return Column(E.Like(self.expr, "%" + E.escape_like(s) + "%"))
+
     def between(self, lo, hi):
         return (self >= lo) & (self <= hi)
 

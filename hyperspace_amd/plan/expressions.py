@@ -376,6 +376,92 @@ class InSet(Predicate):
         return f"{self.value.sql()} INSET ({','.join(map(str, sorted(self.hset, key=repr)))})"
 
 
+def check_like_pattern(pattern: str) -> str:
+    """Spark's LIKE escape rule: ``\\`` may only precede ``%``, ``_`` or ``\\``."""
+    if not isinstance(pattern, str):
+        raise TypeError(f"LIKE pattern must be a string literal, got {pattern!r}")
+    i, n = 0, len(pattern)
+    while i < n:
+        if pattern[i] == "\\":
+            if i + 1 >= n:
+                raise ValueError(f"the LIKE pattern {pattern!r} is invalid: "
+                                 "it is not allowed to end with the escape character")
+            if pattern[i + 1] not in "%_\\":
+                raise ValueError(f"the LIKE pattern {pattern!r} is invalid: the escape character "
+                                 f"is not allowed to precede {pattern[i + 1]!r}")
+            i += 2
+        else:
+            i += 1
+    return pattern
+
+
+def escape_like(s: str) -> str:
+    """``s`` with LIKE's special characters escaped: a pattern that matches ``s`` literally."""
+    return s.replace("\\", "\\\\").replace("%", "\\%").replace("_", "\\_")
+
+
+def like_simple_shape(pattern: str):
+    """("prefix" | "suffix" | "contains", literal) when ``pattern`` is ``lit%``, ``%lit`` or
+    ``%lit%`` with a non-empty wildcard-free literal (escapes resolved), else None."""
+    toks, i = [], 0
+    while i < len(pattern):
+        ch = pattern[i]
+        if ch == "\\":
+            toks.append(pattern[i + 1])
+            i += 2
+        else:
+            toks.append(None if ch == "%" else (False if ch == "_" else ch))
+            i += 1
+    if any(t is False for t in toks):
+        return None
+    lead, trail = bool(toks) and toks[0] is None, len(toks) > 1 and toks[-1] is None
+    body = toks[1 if lead else 0:len(toks) - 1 if trail else len(toks)]
+    if not body or any(t is None for t in body) or not (lead or trail):
+        return None
+    lit = "".join(body)
+    return ("contains" if lead and trail else "suffix" if lead else "prefix"), lit
+
+
+def _is_string_type(t: pa.DataType) -> bool:
+    if pa.types.is_dictionary(t):
+        t = t.value_type
+    return pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_null(t)
+
+
+class Like(Predicate):
+    """``child LIKE 'pattern'`` with Spark's semantics: ``%`` any run, ``_`` one character,
+    ``\\`` escapes ``%``, ``_`` and itself; case-sensitive, anchored, NULL in -> NULL out.
+    The pattern is a plain field (not a Literal child), so two patterns are two plan shapes."""
+
+    def __init__(self, child: Expression, pattern: str):
+        self.children = (child,)
+        self.pattern = check_like_pattern(pattern)
+        # resolution rebuilds the node over the resolved child (with_children): a resolved
+        # child that is not a string is an analysis error
+        t = getattr(child, "dtype", None) if isinstance(child, (Attribute, Literal, Cast)) else None
+        if t is not None and not _is_string_type(t):
+            raise TypeError(f"cannot resolve '{self.sql()}' due to data type mismatch: "
+                            f"LIKE requires a string input, not {t}")
+
+    @property
+    def child(self):
+        return self.children[0]
+
+    @property
+    def nullable(self):
+        return self.child.nullable
+
+    def with_children(self, children):
+        return Like(children[0], self.pattern)
+
+    def canonical_key(self):
+        return ("Like", self.child.canonical_key(), self.pattern)
+
+    def sql(self):
+        p = self.pattern.replace("\\", "\\\\").replace("'", "''")
+        return f"{self.child.sql()} LIKE '{p}'"
+
+
 # ---------------------------------------------------------------------------------------------
 # Arithmetic
 # ---------------------------------------------------------------------------------------------

@@ -96,7 +96,7 @@ def push_join_condition(plan):
 def _null_intolerant_attrs(cond: E.Expression) -> List[E.Attribute]:
     out = []
     for c in E.split_conjuncts(cond):
-        if isinstance(c, (E.BinaryComparison, E.In, E.InSet)):
+        if isinstance(c, (E.BinaryComparison, E.In, E.InSet, E.Like)):
             for a in c.references():
                 out.append(a)
         elif isinstance(c, E.IsNotNull) and isinstance(c.child, E.Attribute):

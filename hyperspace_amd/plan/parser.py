@@ -24,6 +24,29 @@ _KEYWORDS = {"AND", "OR", "NOT", "IN", "IS", "NULL", "TRUE", "FALSE", "BETWEEN",
              "TIMESTAMP", "LIKE"}
 
 
+_SIMPLE_ESCAPES = {"n": "\n", "t": "\t", "r": "\r", "0": "\0", "b": "\b", "Z": "\x1a"}
+
+
+def _unquote_pattern(text: str) -> str:
+    """The body of a quoted LIKE pattern, unescaped as Spark's SQL parser does: ``\\\\`` is one
+    backslash, ``\\%`` and ``\\_`` keep their backslash (they are LIKE's own escapes), ``\\n``
+    and friends are control characters, any other escaped character stands for itself."""
+    q, body = text[0], text[1:-1]
+    if q == "'":
+        body = body.replace("''", "'")
+    out, i = [], 0
+    while i < len(body):
+        ch = body[i]
+        if ch == "\\" and i + 1 < len(body):
+            nx = body[i + 1]
+            out.append("\\" + nx if nx in "%_" else _SIMPLE_ESCAPES.get(nx, nx))
+            i += 2
+        else:
+            out.append(ch)
+            i += 1
+    return "".join(out)
+
+
 def tokenize(s: str):
     pos, out = 0, []
     while pos < len(s):
@@ -119,6 +142,12 @@ class _Parser:
             self.expect("kw", "AND")
             hi = self.additive()
             e = E.And(E.GreaterThanOrEqual(left, lo), E.LessThanOrEqual(left, hi))
+            return E.Not(e) if negate else e
+        if self.accept("kw", "LIKE"):
+            kind, text = self.take()
+            if kind != "str":
+                raise SyntaxError(f"the LIKE pattern must be a string literal, got {text!r}")
+            e = E.Like(left, _unquote_pattern(text))
             return E.Not(e) if negate else e
         if self.accept("kw", "IS"):
             neg = self.accept("kw", "NOT")

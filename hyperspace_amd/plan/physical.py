@@ -236,6 +236,12 @@ def _source_filter(e: E.Expression) -> Optional[str]:
             return f"{op}({name(e.left)},{e.right.sql()})"
     if isinstance(e, (E.In, E.InSet)) and name(e.value):
         return f"In({name(e.value)}, [...])"
+    if isinstance(e, E.Like) and name(e.child):
+        shape = E.like_simple_shape(e.pattern)
+        if shape:
+            fn = {"prefix": "StringStartsWith", "suffix": "StringEndsWith",
+                  "contains": "StringContains"}[shape[0]]
+            return f"{fn}({name(e.child)},{shape[1]})"
     return None
 
 
