@@ -193,6 +193,10 @@ __device__ __forceinline__ long long probe_insert(unsigned long long* keys, long
 }
 
 // Insert n dense groups (SoA, row stride in_cap) into a table.
+// Limit: the floating-point atomic min / max compare by value, so when 0.0 and -0.0 both arrive
+// as a group's extremum, which sign the slot keeps depends on the order the atomics land in.
+// The two compare equal everywhere downstream (dimg maps both to one image), so only the sign
+// bit of a zero MIN / MAX is unspecified; tests compare these by value.
 __global__ __launch_bounds__(kBlock) void hagg_merge_kernel(
     const unsigned long long* __restrict__ in_keys, const unsigned char* __restrict__ in_null,
     const double* __restrict__ in_sums, const long long* __restrict__ in_cnts,

@@ -67,6 +67,12 @@ __device__ __forceinline__ unsigned long long uimg(double d) {
 // value is aggregate `agg`'s sum or (src_count) count; table groups read their count at
 // cnt_slot (< 0: none, every group non-empty) and a zero count makes a sum NULL (first when
 // ascending, last when descending, as Spark orders).
+// Limit: `empty` is the slot image of -inf, so a live slot whose larger-is-better value is -inf
+// (a sum of -inf descending, +inf ascending) is indistinguishable from an empty one: it gets
+// image ~0 here and the empty flag in the gather.  Such a slot holds the worst possible value,
+// so it can only be in the top k when the k-th best value is -inf or fewer than k candidates
+// are live; the caller re-runs the exact table path in both cases (exec/gpu_hash.py
+// _topk_fast: empty slots selected with fewer than k live, or bound >= k-th value).
 __global__ __launch_bounds__(kBlock) void topk_runs_images_kernel(
     const long long* __restrict__ vimg, const double* __restrict__ ssum,
     const long long* __restrict__ scnt, long long scap, unsigned long long empty,

@@ -15,8 +15,9 @@ in *hash mode*:
    runs of equal keys first, so sorted inputs cost about one probe per group and batch.
 3. ``hs_hagg_extract`` compacts occupied slots into dense arrays (and resets them, so tables are
    reused without a memset).  With ``ORDER BY <expr> LIMIT k`` the top-k candidates are picked on
-   the device (order-preserving images, LDS bitonic top-k, ties at the k-th value kept) and only
-   those rows cross PCIe; the host finishes the exact multi-key sort over them.
+   the device (order-preserving 64-bit images, a 3-level radix select over their top 36 bits with
+   LDS histograms, ties of the k-th image at that resolution kept) and only those rows cross
+   PCIe; the host finishes the exact multi-key sort over them.
 
 A table that overflows its probe budget (more groups than the size guess) sets a flag, is
 re-sized 4x and the query re-runs; the size that worked is remembered per query shape.
