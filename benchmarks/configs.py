@@ -29,6 +29,10 @@ against the same query with Hyperspace disabled (the reference's correctness ora
   table (200k x SF rows, every name distinct) through an index that includes the
   dictionary-coded name column; also times the dictionary match kernel against the host route
   (``match_like`` + pack + upload) at 10^4, 10^6 and all entries.
+* ``count_distinct`` — ``count(DISTINCT x)`` over a synthetic table (200k x SF rows) under a
+  range filter: ungrouped, grouped by one dictionary column (few groups, the dense level 2) and
+  grouped by an integer column (>= 10^5 groups at SF >= 5, the hash level 2); q/s on the device
+  against the host engine, the level-1 and level-2 kernel times and the level-2 shape that ran.
 """
 import argparse
 import datetime
@@ -665,9 +669,95 @@ def config_like(args):
     return out
 
 
+def config_count_distinct(args):
+    """``count(DISTINCT x)`` under a range filter on the index key, three shapes: ungrouped, one
+    dictionary group column (few groups) and one integer group column (rows / 10 groups).  Each
+    is cross-checked against the host engine; reports q/s on both engines, the device time of
+    level 1 (the hash aggregate on (g, x): its kernels and extract) and of the level-2 kernels
+    per query (stage timers, HIP events), and which level-2 shape ran."""
+    import numpy as np
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+    from hyperspace_amd import Hyperspace, IndexConfig, col, count, countDistinct, sum_
+    from hyperspace_amd.utils.tracing import PROFILE_ENABLED, TRACER
+    n = int(200_000 * args.sf)
+    root = os.path.join(args.data_dir, f"cfg_count_distinct_sf{args.sf:g}")
+    shutil.rmtree(root, ignore_errors=True)
+    os.makedirs(os.path.join(root, "t"))
+    rng = np.random.default_rng(23)
+    nk = max(n // 20, 100)
+    t = pa.table({"k": rng.integers(0, nk, n).astype(np.int64),
+                  "x": pa.array(rng.integers(0, max(n // 4, 10), n).astype(np.int64),
+                                mask=rng.random(n) < 0.05),
+                  "gd": pa.array([f"region-{i:02d}" for i in range(16)]).take(
+                      pa.array(rng.integers(0, 16, n).astype(np.int32))),
+                  "gi": rng.integers(0, max(n // 10, 10), n).astype(np.int64),
+                  "v": np.round(rng.random(n) * 1000, 2)})
+    nfiles = 8
+    step = (n + nfiles - 1) // nfiles
+    for i in range(nfiles):
+        pq.write_table(t.slice(i * step, step), os.path.join(root, "t", f"part-{i}.parquet"))
+    del t
+    s = _session(root, args.device, args.buckets)
+    hs = Hyperspace(s)
+    df = s.read.parquet(os.path.join(root, "t"))
+    dt, _ = _build(hs, df, IndexConfig("cd_k", ["k"], ["x", "gd", "gi", "v"]), args.device)
+    Hyperspace.enable(s)
+
+    def base(i):
+        lo = (i % 5) * (nk // 20)
+        return df.filter((col("k") >= lo) & (col("k") < lo + (nk * 3) // 4))
+    shapes = {
+        "ungrouped": lambda i: base(i).agg(countDistinct("x").alias("c")),
+        "few_groups": lambda i: base(i).groupBy("gd").agg(
+            countDistinct("x").alias("c"), sum_("v").alias("sv"), count("*").alias("n")),
+        "many_groups": lambda i: base(i).groupBy("gi").agg(
+            countDistinct("x").alias("c"), sum_("v").alias("sv")),
+    }
+    out = {"config": "count_distinct", "device": args.device, "sf": args.sf, "rows": n,
+           "index_build_s": round(dt, 3), "shapes": {}}
+    got = {}
+    for name, q in shapes.items():
+        r = {"index_used": "cd_k" in q(0).queryExecution.executed_plan.tree_string()}
+        got[name] = [_rows(q(i)) for i in range(2)]
+        be = s.backend()
+        r["path"] = getattr(be, "last_path", None)
+        r["fallback_reason"] = getattr(be, "fallback_reason", None)
+        r["groups"] = len(got[name][0])
+        k = args.steps
+        el = _timed_loop(lambda i: q(i).collect(), k, args.device)
+        r["queries_per_s"] = round(k / el, 2)
+        if args.device == "gpu" and r["path"] == "native":
+            r["level2_shape"] = be.metrics.get("distinct_level2")
+            s.conf.set(PROFILE_ENABLED, "true")
+            TRACER.reset()
+            for i in range(k):
+                q(i).collect()
+            rep = TRACER.report()
+            s.conf.set(PROFILE_ENABLED, "false")
+            TRACER.configure(s.conf)
+
+            def per_query(*stages):
+                return round(sum(rep.get(x, {}).get("device_ms", 0.0) for x in stages) / k, 4)
+            r["level1_kernels_ms"] = per_query("hagg.kernels", "hagg.extract")
+            r["level2_kernels_ms"] = per_query("hagg.distinct_kernels")
+        out["shapes"][name] = r
+    # the host engine on the same queries (and the cross-check)
+    s.conf.set("spark.hyperspace.mi.execution.device", "cpu")
+    for name, q in shapes.items():
+        ref = [_rows(q(i)) for i in range(2)]
+        kh = max(2, min(3, args.steps))
+        el_h = _timed_loop(lambda i: q(i).collect(), kh, "cpu")
+        out["shapes"][name]["host_engine_queries_per_s"] = round(kh / el_h, 3)
+        out["shapes"][name]["match"] = all(_close(a, b) for a, b in zip(got[name], ref))
+    out["match"] = all(r["match"] for r in out["shapes"].values())
+    return out
+
+
 CONFIGS = {"csv10k": config_csv10k, "sf10_filter": config_sf10_filter, "hybrid": config_hybrid,
            "q3_3way": config_q3_3way, "tpcds_3way": config_tpcds_3way,
-           "streamed": config_streamed, "like": config_like}
+           "streamed": config_streamed, "like": config_like,
+           "count_distinct": config_count_distinct}
 
 
 def main():

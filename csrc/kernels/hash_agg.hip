@@ -27,22 +27,16 @@
 
 #include <cstdint>
 
+#include "hs_hagg_probe.h"
+
 namespace {
 
-constexpr unsigned long long kEmpty = ~0ull;
+using hs_hagg::kEmpty;
+using hs_hagg::probe_insert;   // the probe scheme, shared with distinct_agg.hip
 constexpr int kBlock = 256;
 constexpr int kTopkBits = 12;
 constexpr int kTopkBins = 1 << kTopkBits;
 constexpr int kTopkLevels = 3;
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
 
 __device__ __forceinline__ bool occupied(const unsigned long long* keys, const long long* cnts,
                                          long long M, int star, long long s) {
@@ -174,22 +168,6 @@ __global__ __launch_bounds__(kBlock) void hagg_emit_kernel(
   }
   if (reset && s < M) keys[s] = kEmpty;
   }
-}
-
-// Slot of `key` (null: the NULL slot), inserting it if absent; -1 when the probe sequence
-// exceeds max_probe (the caller flags overflow and re-runs with a larger table).
-__device__ __forceinline__ long long probe_insert(unsigned long long* keys, long long M,
-                                                  unsigned long long key, bool is_null,
-                                                  int max_probe) {
-  if (is_null) return M + 1;
-  if (key == kEmpty) return M;
-  unsigned long long h = mix64(key) & (unsigned long long)(M - 1);
-  for (int p = 0; p < max_probe; ++p) {
-    const unsigned long long prev = atomicCAS(&keys[h], kEmpty, key);
-    if (prev == kEmpty || prev == key) return (long long)h;
-    h = (h + 1) & (unsigned long long)(M - 1);
-  }
-  return -1;
 }
 
 // Insert n dense groups (SoA, row stride in_cap) into a table.

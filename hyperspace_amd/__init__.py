@@ -9,9 +9,11 @@ from .exceptions import HyperspaceException, NoChangesException
 from .hyperspace import Hyperspace, get_context
 from .index.config import IndexConfig
 from .session import Session
-from .plan.column import col, lit, sum_, count, min_, max_, avg
+from .plan.column import (col, lit, sum_, count, countDistinct, count_distinct, min_, max_,
+                          avg)
 
 __all__ = ["Hyperspace", "IndexConfig", "Session", "HyperspaceException", "NoChangesException",
-           "col", "lit", "sum_", "count", "min_", "max_", "avg", "get_context"]
+           "col", "lit", "sum_", "count", "countDistinct", "count_distinct", "min_", "max_",
+           "avg", "get_context"]
 
 __version__ = "0.1.0"

@@ -240,7 +240,63 @@ class CpuBackend:
         if p.mode == "partial":
             return [self._partial_agg(p, t) for t in parts]
         t = _concat(parts, p.child.output) if parts else _empty(p.child.output)
+        if p.mode == "complete":
+            return [self._complete_agg(p, t)]
         return [self._final_agg(p, t)]
+
+    def _complete_agg(self, p, t: pa.Table) -> pa.Table:
+        """An aggregate holding ``count(DISTINCT x)``: every function over all the rows in one
+        pass (a distinct count does not merge from partials).  Float arguments of a distinct
+        count are normalised first, as Spark and the device key images do: -0.0 counts as 0.0
+        and every NaN as one value."""
+        fns = X.agg_functions(p.aggregates)
+        g_names = [f"g{i}" for i in range(len(p.grouping))]
+        cols = {n: eval_expr(g, t) for n, g in zip(g_names, p.grouping)}
+        specs = []      # per function: [(column, pyarrow aggregation)]
+        for i, (_, fn) in enumerate(fns):
+            if fn.child is None:
+                v = pa.array(np.ones(t.num_rows, dtype=np.int64))
+            else:
+                v = eval_expr(fn.child, t)
+                if pa.types.is_decimal(v.type):
+                    v = pc.cast(v, pa.float64())
+            if isinstance(fn, E.CountDistinct) and pa.types.is_floating(v.type):
+                v = pc.if_else(pc.is_nan(v), pa.scalar(float("nan"), v.type),
+                               pc.add(v, pa.scalar(0.0, v.type)))
+            cols[f"a{i}"] = v
+            if isinstance(fn, E.Avg):
+                specs.append([(f"a{i}", "sum"), (f"a{i}", "count")])
+            elif isinstance(fn, E.CountDistinct):
+                specs.append([(f"a{i}", "count_distinct")])
+            elif isinstance(fn, E.Count):
+                specs.append([(f"a{i}", "count")])
+            else:
+                specs.append([(f"a{i}", fn.name)])
+        aggs = [x for sp in specs for x in sp]
+        tt = pa.table(cols) if cols else pa.table({"__x": pa.array(np.zeros(t.num_rows))})
+        if g_names:
+            r = tt.group_by(g_names, use_threads=False).aggregate(aggs)
+            got = {(c, a): r.column(f"{c}_{a}") for c, a in aggs}
+            groups = [r.column(n) for n in g_names]
+            nrows = r.num_rows
+        else:
+            got = {}
+            for c, a in aggs:
+                s = getattr(pc, a)(tt.column(c))
+                got[(c, a)] = pa.array([s.as_py()],
+                                       s.type if s.type != pa.null() else pa.float64())
+            groups = []
+            nrows = 1          # also over an empty input: counts 0, the other functions NULL
+        agg_vals = {}
+        for sp, (_, fn) in zip(specs, fns):
+            if isinstance(fn, E.Avg):
+                v = pc.divide(pc.cast(got[sp[0]], pa.float64()), pc.cast(got[sp[1]], pa.float64()))
+            else:
+                v = got[sp[0]]
+                if isinstance(fn, (E.Count, E.CountDistinct)):
+                    v = pc.fill_null(pc.cast(v, pa.int64()), 0)
+            agg_vals[id(fn)] = v
+        return self._agg_result_table(p, groups, agg_vals, nrows)
 
     def _partial_agg(self, p, t: pa.Table) -> pa.Table:
         fns = X.agg_functions(p.aggregates)
@@ -329,6 +385,10 @@ class CpuBackend:
                 if kind == "count":
                     v = pc.fill_null(pc.cast(v, pa.int64()), 0)
             agg_vals[id(fn)] = v
+        return self._agg_result_table(p, groups, agg_vals, nrows)
+
+    def _agg_result_table(self, p, groups, agg_vals, nrows) -> pa.Table:
+        """The result expressions of an aggregate over its group columns and function values."""
         out_arrays = []
         for e in p.aggregates:
             inner = e.child if isinstance(e, E.Alias) else e

@@ -28,11 +28,14 @@ class AggOps:
     # Aggregation
     # ------------------------------------------------------------------------------------------
     def _match_agg(self, plan):
-        if not (isinstance(plan, X.HashAggregateExec) and plan.mode == "final"):
+        if not (isinstance(plan, X.HashAggregateExec) and plan.mode in ("final", "complete")):
             return None
         ex = plan.child
         if not isinstance(ex, X.ShuffleExchangeExec):
             return None
+        if plan.mode == "complete":
+            # count(DISTINCT x): one aggregate over the exchanged rows (``_distinct_agg``)
+            return plan, ex.child
         partial = ex.child
         if not (isinstance(partial, X.HashAggregateExec) and partial.mode == "partial"):
             return None
@@ -42,9 +45,12 @@ class AggOps:
                   limit=None):
         """Queue a fused aggregate and return ``finish() -> pa.Table``: the dense LDS
         aggregate for one small integer group column, else the hash-mode aggregate
-        (``_hash_agg``)."""
+        (``_hash_agg``); a complete-mode aggregate (``count(DISTINCT x)``) runs as two hash
+        aggregates (``_distinct_agg``)."""
         if any(not isinstance(g, E.Attribute) for g in final.grouping):
             final, child = self._named_groups(final, child)
+        if final.mode == "complete":
+            return self._distinct_agg(final, child)
         try:
             return self._dense_agg(final, child)
         except _NeedHash as e:

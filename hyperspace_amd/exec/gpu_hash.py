@@ -25,12 +25,17 @@ class HashAggOps:
     # ------------------------------------------------------------------------------------------
     # Hash-mode aggregation (multi-column / high-cardinality / float keys; exec/hash_agg.py)
     # ------------------------------------------------------------------------------------------
-    def _hash_agg(self, final: X.HashAggregateExec, child: X.SparkPlan, order, limit):
+    def _hash_agg(self, final: X.HashAggregateExec, child: X.SparkPlan, order, limit,
+                  level1: bool = False):
         """GROUP BY through the device hash table: every (part) launch of the fused scan or
         merge-join kernel inserts into one table, ``hs_hagg_extract`` compacts it, ranks merge
         their groups, and ORDER BY ... LIMIT picks its candidates on the device.  Kernels and the
         extract are queued now; ``finish`` reads the group count (re-running with a 4x table if
-        the size guess overflowed) and copies the result."""
+        the size guess overflowed) and copies the result.
+
+        ``level1`` (``_distinct_agg``): stop once the table held every group and return
+        ``finish() -> (dense Groups, their count, KeyPlan, aggregate slots, min/max)`` with the
+        groups still on the device; functional-dependency grouping and the run top-K are off."""
         from . import hash_agg as H
         if not HyperspaceConf.codegen_enabled(self.session.conf):
             raise Unsupported("hash aggregate needs code generation")
@@ -57,7 +62,8 @@ class HashAggOps:
                 lparts, rparts = left.parts or [left], right.parts or [right]
                 rels = lparts + rparts
                 launches = [("join", lp, rp) for lp in lparts for rp in rparts]
-                fd = self._fd_grouping(final, grouping, left, right, lk, rk, order, limit)
+                fd = None if level1 else \
+                    self._fd_grouping(final, grouping, left, right, lk, rk, order, limit)
                 if fd is not None:
                     grouping = fd[0]
             else:
@@ -102,6 +108,27 @@ class HashAggOps:
         groups = run(M)
         d = self._dist()
 
+        def settle() -> int:
+            """The group count, once a table held every group (4x re-runs while the probe
+            budget overflowed); the size that worked is kept for the query shape."""
+            nonlocal groups, M
+            G, over = groups.count()
+            while over:
+                if M >= H.MAX_SLOTS:
+                    raise Unsupported("hash aggregate table too large")
+                M *= 4
+                groups = run(M, use_tk=False)
+                G, over = groups.count()
+            self.htables.record(shape_key, M, G)
+            return G
+
+        if level1:
+            def dense():
+                with stage("hagg.result"):
+                    G = settle()
+                return groups, G, (hk_box[0] if hk_box else None), A, minmax
+            return dense
+
         def finish() -> pa.Table:
             if fd is not None and d is not None and d.world > 1:
                 # keys partitioned by bucket: this rank's top candidates, then result rows
@@ -141,14 +168,7 @@ class HashAggOps:
                     # a dropped value may tie the k-th one (or ties flood the copy): exact path
                     self.metrics["run_topk"] = 0
                     groups = run(M, use_tk=False)
-                G, over = groups.count()
-                while over:
-                    if M >= H.MAX_SLOTS:
-                        raise Unsupported("hash aggregate table too large")
-                    M *= 4
-                    groups = run(M, use_tk=False)
-                    G, over = groups.count()
-                self.htables.record(shape_key, M, G)
+                G = settle()
                 extra = None
                 if fd is not None:
                     def extra(gmap, host):
@@ -163,6 +183,130 @@ class HashAggOps:
                 return self._hash_table_out(final, fns, grouping, hk, groups.to_host(G), A,
                                             extra)
         return finish
+
+    # ------------------------------------------------------------------------------------------
+    # COUNT(DISTINCT x): two hash aggregates (csrc/kernels/distinct_agg.hip)
+    # ------------------------------------------------------------------------------------------
+    def _distinct_agg(self, final: X.HashAggregateExec, child: X.SparkPlan):
+        """An aggregate holding one ``count(DISTINCT x)``.  Level 1 is the hash-mode aggregate
+        on ``g... + [x]`` (``x`` last: the key's highest bit field) over the query's other
+        functions; level 2 regroups its dense groups by ``g...`` on the device, counting the
+        rows whose ``x`` is not NULL and merging the other functions' partials: in LDS when the
+        outer codes are few (``hs_distinct_regroup_dense``), else through a second hash table
+        (``hs_distinct_regroup``).  Everything that can refuse the plan does so here, before
+        the deferred ``finish``; ``finish`` reads the level-1 group count and the result."""
+        from . import hash_agg as H
+        all_fns = [fn for _, fn in X.agg_functions(final.aggregates)]
+        dfns = [fn for fn in all_fns if isinstance(fn, E.CountDistinct)]
+        xs = []
+        for fn in dfns:
+            if not any(fn.child.semantic_equals(x) for x in xs):
+                xs.append(fn.child)
+        if len(xs) != 1:
+            raise Unsupported("more than one distinct column in an aggregate")
+        d = self._dist()
+        if d is not None and d.world > 1:
+            raise Unsupported("count(DISTINCT) across several ranks")
+        if self._stream_chunks(child) is not None:
+            raise Unsupported("count(DISTINCT) over an index larger than the device budget")
+        self.last_stream_passes = 0
+        x = xs[0]
+        if not isinstance(x, E.Attribute):
+            # a computed column of a projection under the aggregate, like a grouping expression
+            xa = E.Alias(x, "__hs_dx")
+            child = X.ProjectExec(list(child.output) + [xa], child)
+            x = xa.to_attribute()
+        fns = [fn for fn in all_fns if not isinstance(fn, E.CountDistinct)]
+        level1 = X.HashAggregateExec(list(final.grouping) + [x],
+                                     [E.Alias(fn, f"__hs_a{i}") for i, fn in enumerate(fns)],
+                                     "final", final.child)
+        dense1 = self._hash_agg(level1, child, None, None, level1=True)
+        grouping = list(final.grouping)
+        shape2 = ("distinct", tuple(g.name for g in grouping), x.name,
+                  tuple(fn.sql() for fn in fns))
+
+        def finish() -> pa.Table:
+            groups, G, hk, A, minmax = dense1()
+            with stage("hagg.distinct"):
+                if hk is None or G == 0:
+                    host, hk2 = None, None
+                else:
+                    host, hk2 = self._distinct_level2(H, groups, G, hk, A, minmax, shape2)
+                if host is None and not grouping:
+                    # no rows: the one row of an ungrouped aggregate (counts 0, the rest NULL)
+                    host = {"keys": np.zeros(1, np.uint64), "nulls": np.zeros(1, np.uint8),
+                            "sums": np.zeros((1, A + 2)), "cnts": np.zeros((1, A + 2), np.int64),
+                            "mins": np.full((1, A + 2), np.inf),
+                            "maxs": np.full((1, A + 2), -np.inf)}
+                    star = False
+                else:
+                    star = hk is not None and not hk.need_star
+                return self._distinct_table_out(final, all_fns, fns, grouping, hk2, host, A,
+                                                star)
+        return finish
+
+    def _distinct_level2(self, H, groups, G: int, hk, A: int, minmax: bool, shape2):
+        """(host arrays of the outer groups with A + 2 aggregate slots, the outer KeyPlan)."""
+        f = H.DistinctFields.of(hk)
+        hk2 = H.KeyPlan(hk.cols[:-1], "packed", hk.own_counts, hk.need_star)
+        if H.distinct_dense_fits(f, A, minmax):
+            self.metrics["distinct_level2"] = "dense"
+            with stage("hagg.distinct_kernels"):
+                out = H.distinct_regroup_dense(groups, G, f)
+            host = out.to_host(f.slots)
+            live = host["cnts"][:, A + 1] > 0
+            return {k: v[live] for k, v in host.items()}, hk2
+        self.metrics["distinct_level2"] = "hash"
+        M = self.htables.slots_for(shape2, min(G, f.slots))
+        while True:
+            table = self.htables.get(M, A + 2, minmax, self.device)
+            with stage("hagg.distinct_kernels"):
+                out = H.distinct_regroup(groups, G, f, table)
+            G2, over = out.count()
+            if not over:
+                break
+            if M >= H.MAX_SLOTS:
+                raise Unsupported("hash aggregate table too large")
+            M *= 4
+        self.htables.record(shape2, M, G2)
+        return out.to_host(G2), hk2
+
+    def _distinct_table_out(self, final, all_fns, fns, grouping, hk2, host, A: int,
+                            star_is_one: bool) -> pa.Table:
+        """``_hash_table_out`` for the level-2 groups: ``hk2`` packs the outer columns only,
+        function i of ``fns`` reads slot i and ``count(DISTINCT x)`` the count of slot A."""
+        G = 0 if host is None else len(host["keys"])
+        if G and star_is_one:
+            host["cnts"][:, A - 1] = 1     # COUNT(*) not accumulated: every group has rows
+        gmap = {}
+        if hk2 is not None and G and grouping:
+            for g, arr in zip(grouping, hk2.unpack(host["keys"], host["nulls"])):
+                gmap[g.expr_id] = arr
+        else:
+            for g in grouping:
+                gmap[g.expr_id] = pa.array([], type=g.data_type)
+        vals = {}
+        for fn in all_fns:
+            if not G:
+                vals[id(fn)] = pa.array([], type=fn.data_type)
+            elif isinstance(fn, E.CountDistinct):
+                vals[id(fn)] = pa.array(host["cnts"][:, A], type=pa.int64())
+        for i, fn in enumerate(fns):
+            if G:
+                own = hk2.own_counts[i] if hk2 is not None else False
+                cnt = host["cnts"][:, i] if own else host["cnts"][:, A - 1]
+                vals[id(fn)] = _finalize_array(fn, host["sums"][:, i], cnt, host["mins"][:, i],
+                                               host["maxs"][:, i])
+        arrays = []
+        for e, a in zip(final.aggregates, final.output):
+            arr = _eval_vec(e.child if isinstance(e, E.Alias) else e, vals, gmap, G)
+            if not arr.type.equals(a.data_type):
+                try:
+                    arr = arr.cast(a.data_type)
+                except (pa.ArrowInvalid, pa.ArrowNotImplementedError):
+                    pass
+            arrays.append(arr)
+        return arrow_table(arrays, [a.name for a in final.output])
 
     # keys per functional-dependency lookup (one probe per key, in the key's bucket)
     FD_MAX_KEYS = 1 << 22

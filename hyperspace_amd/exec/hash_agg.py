@@ -356,6 +356,77 @@ def next_pow2(n: int) -> int:
 
 
 # ------------------------------------------------------------------------------------------------
+# COUNT(DISTINCT x): level 2 (csrc/kernels/distinct_agg.hip)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class DistinctFields:
+    """Where the level-1 key of a distinct count holds its outer group and ``x``: the outer
+    key is ``key & outer_mask`` and ``x`` is NULL when nullable with a 0 code at ``x_shift``;
+    ``raw``: a single unpacked 64-bit ``x`` (no outer columns, NULL in the nulls byte)."""
+    outer_mask: int = 0
+    x_shift: int = 0
+    x_nullable: bool = False
+    raw: bool = False
+
+    @staticmethod
+    def of(hk: KeyPlan) -> "DistinctFields":
+        x = hk.cols[-1]
+        if hk.mode != "packed":
+            return DistinctFields(raw=True)
+        return DistinctFields((1 << x.shift) - 1, x.shift, x.nullable, False)
+
+    @property
+    def slots(self) -> int:
+        """Outer codes the key can hold (the dense shape's slot count)."""
+        return 1 if self.raw else self.outer_mask + 1
+
+
+def distinct_dense_fits(f: DistinctFields, A: int, minmax: bool) -> bool:
+    """One block's accumulators fit in LDS: slots * (A + 2) * 8 * (2 + 2 * minmax) <= 64 KiB."""
+    return f.slots <= (1 << 20) and \
+        bool(NL.lib().hs_distinct_dense_fits(f.slots, A, int(minmax)))
+
+
+def distinct_regroup_dense(g: Groups, n: int, f: DistinctFields) -> Groups:
+    """Level 2, dense shape: one output row per outer code (``f.slots`` rows, key = code; a
+    code no row fell in has 0 in count slot A + 1).  Stream-ordered, no atomics, bitwise
+    reproducible."""
+    import torch
+    L = NL.lib()
+    A, dev, mm = g.NA, g.device, g.mins is not None
+    S = f.slots
+    cells = int(L.hs_distinct_dense_blocks(n, S, A)) * S * (A + 2)
+    out = Groups.alloc(A + 2, S, mm, dev)
+    slab_s = torch.empty(cells, dtype=torch.float64, device=dev)
+    slab_c = torch.empty(cells, dtype=torch.int64, device=dev)
+    slab_mn = torch.empty(cells, dtype=torch.float64, device=dev) if mm else None
+    slab_mx = torch.empty(cells, dtype=torch.float64, device=dev) if mm else None
+    NL.check(L.hs_distinct_regroup_dense(
+        NL.ptr(g.keys), NL.ptr(g.nulls), NL.ptr(g.sums), NL.ptr(g.cnts), NL.ptr(g.mins),
+        NL.ptr(g.maxs), n, g.cap, A, C.c_uint64(f.outer_mask), f.x_shift, int(f.x_nullable),
+        int(f.raw), S, NL.ptr(slab_s), NL.ptr(slab_c), NL.ptr(slab_mn), NL.ptr(slab_mx), out.cap,
+        NL.ptr(out.keys), NL.ptr(out.nulls), NL.ptr(out.sums), NL.ptr(out.cnts),
+        NL.ptr(out.mins), NL.ptr(out.maxs), NL.stream_ptr()), "hs_distinct_regroup_dense")
+    out.set_count(S)
+    return out
+
+
+def distinct_regroup(g: Groups, n: int, f: DistinctFields, table: HashTable) -> Groups:
+    """Level 2, hash shape: the rows inserted into ``table`` (A + 2 aggregates per group) and
+    the table extracted; ``count()`` of the result gives the outer groups and whether the probe
+    budget overflowed (re-run with a larger table)."""
+    A = g.NA
+    assert table.NA == A + 2 and table.minmax == (g.mins is not None)
+    NL.check(NL.lib().hs_distinct_regroup(
+        NL.ptr(g.keys), NL.ptr(g.nulls), NL.ptr(g.sums), NL.ptr(g.cnts), NL.ptr(g.mins),
+        NL.ptr(g.maxs), n, g.cap, A, C.c_uint64(f.outer_mask), f.x_shift, int(f.x_nullable),
+        int(f.raw), NL.ptr(table.keys), NL.ptr(table.sums), NL.ptr(table.cnts),
+        NL.ptr(table.mins), NL.ptr(table.maxs), table.M, NL.ptr(table.flag), NL.stream_ptr()),
+        "hs_distinct_regroup")
+    return table.extract(A + 1)
+
+
+# ------------------------------------------------------------------------------------------------
 # Top-k
 # ------------------------------------------------------------------------------------------------
 # image sources (csrc/kernels/hash_agg.hip topk_images_kernel)
@@ -577,4 +648,5 @@ def _topk_ws(dev) -> dict:
 
 
 __all__ = ["KeyPlan", "KeyCol", "plan_keys", "HashTable", "Groups", "TablePool",
-           "OrderSource", "topk_candidates", "TopKPlan", "Unsupported"]
+           "OrderSource", "topk_candidates", "TopKPlan", "Unsupported", "DistinctFields",
+           "distinct_dense_fits", "distinct_regroup_dense", "distinct_regroup"]

@@ -236,6 +236,13 @@ def lib():
     _sig(L.hs_topk_runs_gather, I, P, P, I, P, P, P, P, I64, U64, P, P, P, P, I64, P, P, I, P,
          P)
     _sig(L.hs_hagg_take, I, P, I64, P, P, P, P, P, P, I, I64, I64, P, P, P, P, P, P, P)
+    _sig(L.hs_distinct_dense_bytes, I64, I64, I, I)
+    _sig(L.hs_distinct_dense_fits, I, I64, I, I)
+    _sig(L.hs_distinct_dense_blocks, I64, I64, I64, I)
+    _sig(L.hs_distinct_regroup_dense, I, P, P, P, P, P, P, I64, I64, I, U64, I, I, I, I64,
+         P, P, P, P, I64, P, P, P, P, P, P, P)
+    _sig(L.hs_distinct_regroup, I, P, P, P, P, P, P, I64, I64, I, U64, I, I, I,
+         P, P, P, P, P, I64, P, P)
     _lib = L
     return L
 

@@ -156,6 +156,19 @@ def count(c="*") -> Column:
     return Column(E.Count(_expr(col(c) if isinstance(c, str) else c)))
 
 
+def countDistinct(c, *more) -> Column:
+    """``count(DISTINCT c)``: the number of different non-NULL values of one column or
+    expression."""
+    if more:
+        from ..exceptions import HyperspaceException
+        raise HyperspaceException("countDistinct over several columns is not supported: "
+                                  "it takes one argument")
+    return Column(E.CountDistinct(_expr(col(c) if isinstance(c, str) else c)))
+
+
+count_distinct = countDistinct
+
+
 def min_(c) -> Column:
     return Column(E.Min(_expr(col(c) if isinstance(c, str) else c)))
 

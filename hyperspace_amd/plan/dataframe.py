@@ -255,6 +255,11 @@ class DataFrame:
     def agg(self, *aggs) -> "DataFrame":
         return GroupedData(self, []).agg(*aggs)
 
+    def distinct(self) -> "DataFrame":
+        """The different rows of this frame (``SELECT DISTINCT``): an aggregate grouping on
+        every output column, with no functions."""
+        return DataFrame(self.session, L.distinct(self.plan))
+
     def union(self, other: "DataFrame") -> "DataFrame":
         return DataFrame(self.session, L.Union([self.plan, other.plan]))
 
@@ -344,7 +349,8 @@ class GroupedData:
             items = []
             for c, fn in aggs[0].items():
                 f = {"sum": E.Sum, "count": E.Count, "min": E.Min, "max": E.Max,
-                     "avg": E.Avg, "mean": E.Avg}[fn.lower()]
+                     "avg": E.Avg, "mean": E.Avg, "count_distinct": E.CountDistinct,
+                     "countdistinct": E.CountDistinct}[fn.lower()]
                 items.append(_C(E.Alias(f(E.UnresolvedAttribute(c)), f"{fn}({c})")))
             aggs = tuple(items)
         for a in aggs:

@@ -563,6 +563,24 @@ class Count(AggregateFunction):
         return False
 
 
+class CountDistinct(AggregateFunction):
+    """``count(DISTINCT x)``: the number of different non-NULL values of ``x``.  A class of its
+    own (not a flag on ``Count``): it has no partial / final decomposition, so every site that
+    dispatches on the aggregate's type rejects it unless it was written for it."""
+    name = "count"
+
+    @property
+    def data_type(self):
+        return pa.int64()
+
+    @property
+    def nullable(self):
+        return False
+
+    def sql(self):
+        return f"count(DISTINCT {self.child.sql()})"
+
+
 class Min(AggregateFunction):
     name = "min"
 

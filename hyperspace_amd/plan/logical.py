@@ -372,6 +372,12 @@ class Aggregate(UnaryNode):
                 f"[{', '.join(a.sql() for a in self.aggregates)}]")
 
 
+def distinct(p: LogicalPlan) -> LogicalPlan:
+    """``SELECT DISTINCT`` / ``DataFrame.distinct()``: group on every output column."""
+    out = list(p.output)
+    return Aggregate(out, out, p)
+
+
 class Union(LogicalPlan):
     def __init__(self, children: List[LogicalPlan]):
         self.children = tuple(children)

@@ -218,6 +218,18 @@ class _Parser:
             if self.peek() == ("op", "("):
                 self.take()
                 args = []
+                nxt = self.peek()
+                if nxt == ("kw", "DISTINCT") or (
+                        nxt[0] == "id" and nxt[1].upper() == "DISTINCT" and
+                        self.peek(1) not in (("op", ")"), ("op", ","))):
+                    # f(DISTINCT e, ...): outside SQL text DISTINCT is no reserved word, and a
+                    # column may carry the name
+                    self.take()
+                    args.append(self.or_expr())
+                    while self.accept("op", ","):
+                        args.append(self.or_expr())
+                    self.expect("op", ")")
+                    return make_function(text, args, distinct=True)
                 if self.accept("op", "*"):
                     args = []
                 elif not self.accept("op", ")"):
@@ -234,8 +246,15 @@ class _Parser:
         raise SyntaxError(f"unexpected token {text!r}")
 
 
-def make_function(name: str, args):
+def make_function(name: str, args, distinct: bool = False):
     n = name.lower()
+    if distinct:
+        if n != "count":
+            raise SyntaxError(f"{n}(DISTINCT ...) is not supported: only count(DISTINCT x) is")
+        if len(args) != 1:
+            raise SyntaxError("count(DISTINCT ...) over several columns is not supported: "
+                              "it takes one argument")
+        return E.CountDistinct(args[0])
     if n == "isnotnull":
         return E.IsNotNull(args[0])
     if n == "isnull":

@@ -698,6 +698,16 @@ class Planner:
             return self._plan_join(p)
         if isinstance(p, L.Aggregate):
             child = self.plan(p.child)
+            if any(isinstance(fn, E.CountDistinct) for _, fn in agg_functions(p.aggregates)):
+                # a distinct count has no partial / final split: the rows are exchanged on the
+                # grouping and aggregated once
+                if p.grouping:
+                    n = HyperspaceConf.shuffle_partitions(self.session.conf)
+                    keys = [g.child if isinstance(g, E.Alias) else g for g in p.grouping]
+                    exch = ShuffleExchangeExec(HashPartitioning(keys, n), child)
+                else:
+                    exch = ShuffleExchangeExec(SinglePartition(), child)
+                return HashAggregateExec(p.grouping, p.aggregates, "complete", exch)
             partial = HashAggregateExec(p.grouping, p.aggregates, "partial", child)
             if p.grouping:
                 n = HyperspaceConf.shuffle_partitions(self.session.conf)

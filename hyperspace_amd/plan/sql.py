@@ -121,7 +121,7 @@ class SqlPlanner(_Parser):
             all_ = self.accept("kw", "ALL")
             p = L.Union([p, self.select(tail=False)])
             if not all_:
-                p = _distinct(p)
+                p = L.distinct(p)
         orders, limit = self.order_limit()
         if orders:
             # names resolve against the union's output (the first branch's column names)
@@ -412,10 +412,10 @@ class SqlPlanner(_Parser):
             if hidden:
                 plan = L.Project([e.to_attribute() if isinstance(e, E.Alias) else e
                                   for e in out], plan)
-            return _distinct(plan) if distinct else plan
+            return L.distinct(plan) if distinct else plan
         proj = L.Project(exprs, plan)
         if distinct:
-            proj = _distinct(proj)
+            proj = L.distinct(proj)
         if not orders:
             return proj
         out_ids = {(e.to_attribute() if isinstance(e, E.Alias) else e).expr_id for e in exprs}
@@ -445,11 +445,6 @@ def _transform_down(e: E.Expression, fn) -> E.Expression:
     if all(a is b for a, b in zip(new, e.children)):
         return e
     return e.with_children(new)
-
-
-def _distinct(p: L.LogicalPlan) -> L.LogicalPlan:
-    out = list(p.output)
-    return L.Aggregate(out, out, p)
 
 
 def sql(session, text: str):
