@@ -301,6 +301,11 @@ def load_bucketed_index(files, columns: List[str], num_buckets: int, sort_cols: 
         cols = {c: DeviceColumn(torch.empty(0, dtype=torch.int64, device=device), None, pa.int64())
                 for c in columns}
     table = DeviceTable(cols, n, torch.from_numpy(off).to(device), off)
+    if n and not multi and not paged and sort_cols and table.columns[sort_cols[0]].is_float:
+        # another writer's order of a float key is not the kernels' (pyarrow puts NaN next to
+        # the nulls and leaves -0.0 and +0.0 as ties); the range search needs the bit total
+        # order of hs_sortable
+        multi = True
     if multi and n:
         # re-establish (bucket, sort cols) order on the device
         bucket = torch.repeat_interleave(torch.arange(num_buckets, dtype=torch.int32, device=device),

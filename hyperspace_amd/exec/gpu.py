@@ -901,7 +901,17 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps):
             if kc.dictionary is not None or isinstance(v, str):
                 continue
             if kc.is_float:
-                v = float(v)
+                # IEEE comparison on a key sorted in the bit total order (-0.0 < +0.0, NaNs at
+                # both ends): an inclusive image range per comparison, intersected
+                rng = K.float_key_image_range(leaf.op, float(v), kc.hs_type)
+                if rng is None:
+                    continue            # stays a per-row predicate (a NaN literal)
+                used.append(c)
+                if lo is None or rng[0] > lo:
+                    lo = rng[0]
+                if hi is None or rng[1] < hi:
+                    hi = rng[1]
+                continue
             elif isinstance(v, float):
                 if not float(v).is_integer():
                     continue

@@ -660,6 +660,40 @@ def sortable_image(value, hs_type: int) -> int:
     return (int(value) + (1 << (width - 1))) & ((1 << width) - 1)
 
 
+def float_key_image_range(op: int, value: float, hs_type: int):
+    """Inclusive image range ``(lo, hi)`` of the float keys ``k`` with ``k op value`` true under
+    IEEE comparison (``op``: OP_EQ / OP_LT / OP_LE / OP_GT / OP_GE), or None when the comparison
+    is no image interval (a NaN literal; an F32 key against a literal that is no float32).
+
+    The images follow the bit total order, the comparison does not: -0.0 equals +0.0, so a zero
+    literal stands for both zeros, and NaNs of either sign sit outside ``[-inf, +inf]``, so
+    every range is clamped to it.  ``lo > hi`` is an empty range."""
+    import math
+    import struct
+    v = float(value)
+    if math.isnan(v) or op not in (NL.OP_EQ, NL.OP_LT, NL.OP_LE, NL.OP_GT, NL.OP_GE):
+        return None
+    if hs_type == NL.F32 and not math.isinf(v):
+        try:
+            if struct.unpack("<f", struct.pack("<f", v))[0] != v:
+                return None
+        except OverflowError:
+            return None
+    lo, hi = sortable_image(-math.inf, hs_type), sortable_image(math.inf, hs_type)
+    # the smallest / largest image of a key equal to the literal
+    first = sortable_image(-0.0 if v == 0.0 else v, hs_type)
+    last = sortable_image(0.0 if v == 0.0 else v, hs_type)
+    if op in (NL.OP_GE, NL.OP_EQ):
+        lo = first
+    if op in (NL.OP_LE, NL.OP_EQ):
+        hi = last
+    if op == NL.OP_GT:
+        lo = last + 1
+    if op == NL.OP_LT:
+        hi = first - 1
+    return lo, hi
+
+
 def agg_outputs(GA: int, dev):
     """(sum f64, count i64, min f64, max f64) [GA] as views of ONE device buffer, so the host
     reads a query's aggregate result with a single D2H copy (``sum.hs_buf``)."""

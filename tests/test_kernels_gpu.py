@@ -364,6 +364,10 @@ def test_merge_runs_permutation_equals_stable_sort(device, runs_per_bucket):
     assert perm is not None
     ref = K.sort_permutation([ca, cb], extra_leading=(torch.from_numpy(bucket).to(device), 8))
     assert np.array_equal(perm.cpu().numpy(), ref.cpu().numpy()), n
+    # and the independent numpy reference (the device sort and the merge share one key image)
+    from order_ref import ref_sort_perm
+    assert np.array_equal(perm.cpu().numpy(),
+                          ref_sort_perm([(a, mask), (b, None)], leading=bucket))
     # unsorted runs are detected: the caller falls back to the radix sort
     bad = _col(pa.array(rng.integers(0, 100, n).astype(np.int64)), device)
     assert K.merge_runs_permutation([bad], np.asarray(off), np.asarray(grp)) is None
