@@ -12,13 +12,17 @@ streams:
    run into a bitmap: 0 = no (passing) right row, else 1 (ungrouped / left-grouped) or the
    right-side group code + 1.  Tags are assembled in LDS and leave as whole 32-bit words (only
    a tile's two edge words use an atomic OR).  It reads the run keys, the right keys and the
-   right predicate columns once: ~1.5 GB at TPC-H SF100.
+   right predicate columns once: 10 B per run (4 + 4 + 2), 1.5 GB over the 150 M runs of TPC-H
+   SF100 Q3, in ~0.30 ms beside the Q6 scan - 5.0 TB/s one run per lane, 5.2 TB/s four
+   (``profiles/tags2_wide.txt``; a FETCH_SIZE counter pass reads about half of these computed
+   bytes for all three query kernels, ``profiles/pmc_query_kernels_sf100_r6.txt``).
 2. ``hs_jit_run_scan`` - a streaming scan of the left rows (vector loads, no LDS staging, no
    barriers): row -> run index from the group mask by one popcount, tag from the bitmap (the
    NI rows of a thread touch one or a few adjacent words), left predicates, and the compacted
    aggregate tail over the passing rows only.
 
-Both phases are plain streams, so each runs near the HBM roofline; the single-kernel form
+Both phases are plain streams (phase 2 at ~5.8 TB/s of its computed bytes; the three kernels
+of a headline step together move ~4.0 GB in 0.70 ms, 5.7 TB/s); the single-kernel form
 (jit.gen_merge_join_agg) keeps a long chain of dependent round trips per tile.  The two-phase
 form applies when no aggregate input comes from the right side, every right predicate reads
 only right columns, and a right-side group key (if any) has at most 255 groups."""
@@ -37,6 +41,7 @@ _CFG = _KC.active()
 MJ_2P, RS_ITEMS = _CFG.mj_2p, _CFG.rs_items
 RT2_UNROLL, RT2_GRID, RT2_I32 = _CFG.rt2_unroll, _CFG.rt2_grid, _CFG.rt2_i32
 RT2_MATCH, RT2_COPY, RT2_LO16 = _CFG.rt2_match, _CFG.rt2_copy, _CFG.rt2_lo16
+RT2_WIDE, RT2_WIDE_GRID = _CFG.rt2_wide, _CFG.rt2_wide_grid
 RS_BITS, RS_BITS_GRID, RS_PACK = _CFG.rs_bits, _CFG.rs_bits_grid, _CFG.rs_pack
 RS_PIPE, RS_WALK, RS_LDS, RS_LUT = _CFG.rs_pipe, _CFG.rs_walk, _CFG.rs_lds, _CFG.rs_lut
 RS_PK16, RS_WAVES, RS_PACK12 = _CFG.rs_pk16, _CFG.rs_waves, _CFG.rs_pack12
@@ -78,13 +83,29 @@ def _lpreds(p):
 # phase 1: 64-run groups per unrolled iteration of a wavefront (gen_run_tags2)
 
 
+def tags2_wide(p: NL.JoinParams, compacts, ix32: bool, mode: str = "") -> int:
+    """Runs per lane of phase 1 for this join (the lowering's choice): RT2_WIDE's 4-run form
+    only for the verifying kernel (modes "" and "rec") with 32-bit indices, and only when the
+    right key and every staged right column are stored plainly or as a one-array compact code
+    without a validity mask - the grouped 16-bit key encoding and nullable columns keep the
+    one-run form, which reads them element by element."""
+    if RT2_WIDE != 4 or not ix32 or mode not in ("", "rec"):
+        return 1
+    cols = J._col_specs(p, compacts)
+    for sl in dict.fromkeys([p.rkey] + _stage_slots(p)):
+        enc = cols[sl][2]
+        if cols[sl][1] or (enc and len(enc) > 2 and enc[2] == 64):
+            return 1
+    return 4
+
+
 def tags2_shape(p: NL.JoinParams, compacts, W: int, ix32: bool = False, mode: str = "") -> tuple:
     cols = tuple(sorted((s, c) for s, c in J._col_specs(p, compacts).items()
                         if s >= SPLIT or s == p.lkey))
     preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
                    p.preds[k].group) for k in range(p.nlp, p.npreds))
     return ("run_tags2", cols, preds, p.nlp, p.lkey, p.rkey, _tags_grouped(p) and p.group_col,
-            W, RT2_UNROLL, J.BLOCK, ix32, mode)
+            W, RT2_UNROLL, J.BLOCK, ix32, mode, tags2_wide(p, compacts, ix32, mode))
 
 
 def _stage_slots(p: NL.JoinParams) -> list:
@@ -124,8 +145,20 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
     ``mode``: "rec" also stores each run's matched right row (or -1) into ``MOUT``; "match"
     reads that record (``MATCH``, one int32 per run, -1 padded to whole 64-run groups) instead of
     the left run keys, the right key images and the range table - it depends only on the
-    lowering's ranges and the key columns, not on the literals (``record_matches``)."""
+    lowering's ranges and the key columns, not on the literals (``record_matches``).
+
+    Four runs per lane (``tags2_wide``; modes "" and "rec"): the chunk is counted in 256-run
+    blocks, lane l owning runs 256 b + 4 l .. + 3.  A block whose runs all lie in one range and
+    below NRUNS, and whose 256 guessed right rows lie in [s0, s1), is *fast*: one 16-byte load
+    of the lane's 4 left keys, one element-aligned 4-element load of the right key and of each
+    staged right column at the guess, four compares, and a miss gallops per run as above.  The
+    guess of the stage after the current one assumes every run matches (current base + its
+    runs), so its loads are issued before the current stage is resolved - two register sets,
+    the loop unrolled by two so neither is copied; the resolved base (last match + 1) replaces
+    the assumption for the stage after that.  Every other block (a range edge, the table tail,
+    a guess outside the bucket) takes the 64-run code below, one group at a time."""
     IX = "int" if ix32 else "i64"  # noqa: N806 — run / right-row index type
+    wide = tags2_wide(p, compacts, ix32, mode)
     args = J.Args()
     if mode in ("match", "copy"):
         return _gen_tags2_match(p, compacts, W, mode == "copy")
@@ -277,7 +310,7 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
         for sl in stage_slots:
             J._uload(gu, sl, f"g{u}", b, ind)
 
-    def resolve(u: int, ind: str, lo: bool = False) -> None:
+    def resolve(u, ind: str, lo: bool = False, stores: bool = True) -> None:
         gu = J._Gen(args, cols, SPLIT, (f"j{u}", f"j{u}"), frozenset(), True)
         # (a checked group's keys are low halves: a miss gallops with the full left key)
         kfull = f"(unsigned)a.RK{lk}[r{u}] + (unsigned)a.KOF" if lo else f"key{u}"
@@ -322,6 +355,8 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
             J._uload(gm, sl, f"h{u}", b, ind + "  ")
         b.extend([f"{ind}  tg{u} = {tag_expr(gm, f'h{u}', f'hit{u}')};",
                   f"{ind}}}"])
+        if not stores:
+            return
         # the group's 2W tag words: whole words, plain stores
         if W == 1:
             b.extend([f"{ind}{{ const u64 bal_ = __ballot(tg{u} != 0u);",
@@ -348,11 +383,177 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
         b.extend([f"{ind}{{ const {IX} nx_ = __shfl((hit{U - 1} && own{U - 1}) ? m{U - 1} + 1 : "
                   f"({IX})-1, 63, 64);",
                   f"{ind}  gbase = nx_; }}"])
+
+    if wide == 4:
+        del b[:]
+        return _gen_tags2_wide(p, args, cols, b, group, resolve,
+                               image(g.decode(rk, "w_"), False), img, imgf, W, mode)
     iteration(True, ind)
     b.append("    } else {   // a range starts inside this iteration's groups")
     iteration(False, ind)
     b += ["    }", "  }"]
     src = (J._PRELUDE + args.struct_src() +
+           f'extern "C" __global__ __launch_bounds__({J.BLOCK}) void hs_jit_run_tags2(Args a) {{\n' +
+           "\n".join(b) + "\n}\n")
+    return J.Kernel(src, "hs_jit_run_tags2", args)
+
+
+def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, resolve,
+                    imgv: str, img: str, imgf: str, W: int, mode: str) -> J.Kernel:
+    """The four-runs-per-lane body of ``gen_run_tags2`` (its docstring; 32-bit indices).
+    ``group`` / ``resolve`` are that generator's 64-run emitters (appending to ``b``): the slow
+    blocks run them one group at a time, and a fast block's runs resolve through the same miss
+    path, one instance per run."""
+    lk, rk = p.lkey, p.rkey
+    # 256-run blocks per pipeline stage (RT2_UNROLL counts blocks here): at most two - 84 VGPRs
+    # at W = 1, six waves per SIMD; a third block's register sets would spill
+    U = max(1, min(2, RT2_UNROLL))  # noqa: N806
+    WV = J.BLOCK // 64  # noqa: N806
+    MASK = (1 << W) - 1  # noqa: N806
+    L = 8 // W  # noqa: N806 — lanes whose 4 tags share one 32-bit word
+    R = 256 * U  # noqa: N806 — runs per stage
+    stage_slots = _stage_slots(p)
+    g = J._Gen(args, cols, SPLIT, ("row_", "row_"), frozenset(), True)
+    rkt = g.raw_type(rk)
+    # 4 consecutive elements at an element-aligned address (the guess is arbitrary): one load
+    tdefs = ["typedef int hs_i4 __attribute__((ext_vector_type(4)));",
+             f"typedef {rkt} hs_rk4 __attribute__((ext_vector_type(4), "
+             f"aligned({J._SIZEOF[rkt]})));"]
+    for sl in stage_slots:
+        t = g.raw_type(sl)
+        tdefs.append(f"typedef {t} hs_c{sl}x4 __attribute__((ext_vector_type(4), "
+                     f"aligned({J._SIZEOF[t]})));")
+    sets = ("A", "B")
+
+    def adv(ind: str) -> List[str]:
+        return [f"{ind}++rg; lr0 = (int)RG[4 * rg]; lr1 = (int)RG[4 * rg + 1]; "
+                f"s0 = (int)RG[4 * rg + 2];",
+                f"{ind}s1 = (int)RG[4 * rg + 3]; gbase = -1;",
+                f"{ind}nxt0 = rg + 1 < a.NRG ? RG[4 * (rg + 1)] : 0x7fffffffffffffffll;"]
+
+    def fast(blk: str, off: int, ind: str) -> None:
+        """``f_``: the stage of blocks blk .. blk + U - 1 is fast at guess base ``base_`` (the
+        resolved base + ``off``, or range-relative) - all wavefront-uniform, tested before any
+        address is formed."""
+        b.extend([f"{ind}const int rb_ = ({blk}) << 8;",
+                  f"{ind}const int base_ = gbase >= 0 ? gbase + {off} : s0 + (rb_ - lr0);",
+                  f"{ind}const bool f_ = ({blk}) + {U} <= bend && rb_ >= lr0 && "
+                  f"rb_ + {R} <= lr1 && rb_ + {R} <= NR && (i64)rb_ + {R} <= nxt0 && "
+                  f"base_ >= s0 && base_ + {R} <= s1;"])
+
+    def load(s: str, run0: str, base: str, ind: str) -> None:
+        """Set ``s`` <- the stage whose first run is ``run0`` (a multiple of 256), guessed at
+        right row ``base``; the caller has tested both (``fast``)."""
+        b.append(f"{ind}pb{s} = {base};")
+        for u in range(U):
+            b.extend([f"{ind}L{s}{u} = *(const hs_v4u*)(a.RK{lk} + ({run0} + {256 * u} + "
+                      f"4 * lane));",
+                      f"{ind}R{s}{u} = *(const hs_rk4*)({g.ptr(rk)} + ({base} + {256 * u} + "
+                      f"4 * lane));"])
+            for sl in stage_slots:
+                b.append(f"{ind}C{sl}{s}{u} = *(const hs_c{sl}x4*)({g.ptr(sl)} + "
+                         f"({base} + {256 * u} + 4 * lane));")
+
+    def resolve_stage(s: str, ind: str) -> None:
+        """Tags (and matches) of the stage in register set ``s``: blocks nb .. nb + U - 1,
+        loaded at guess base pb<s>; leaves the resolved next base in ``gbase``."""
+        b.append(f"{ind}int nx_ = -1;")
+        for u in range(U):
+            b.append(f"{ind}{{ unsigned pk_ = 0u;" + (" hs_i4 mo_;" if mode == "rec" else ""))
+            i2 = ind + "  "
+            for k in range(4):
+                x = f"{s}{u}_{k}"
+                b.extend([f"{i2}{{ const int j{x} = pb{s} + {256 * u + k} + 4 * lane;",
+                          f"{i2}const int a0_{x} = s0, a1_{x} = s1; const bool act{x} = true;",
+                          f"{i2}const unsigned key{x} = L{s}{u}[{k}] + (unsigned)a.KOF;",
+                          f"{i2}const unsigned k{x} = IMGV(R{s}{u}[{k}]);"])
+                for sl in stage_slots:
+                    J._uload_raw(g, sl, f"g{x}", f"C{sl}{s}{u}[{k}]", "1", b, i2)
+                resolve(x, i2, False, False)
+                b.append(f"{i2}pk_ |= (tg{x} & {MASK}u) << {k * W};")
+                if mode == "rec":
+                    b.append(f"{i2}mo_[{k}] = hit{x} ? m{x} : -1;")
+                if u == U - 1 and k == 3:
+                    b.append(f"{i2}nx_ = hit{x} ? m{x} + 1 : -1;")
+                b.append(f"{i2}}}")
+            # the lanes of one tag word hold disjoint bit fields: OR across them, one stores
+            if L > 1:
+                b.append(f"{i2}pk_ <<= (unsigned)({4 * W} * (lane & {L - 1}));")
+            o = 1
+            while o < L:
+                b.append(f"{i2}pk_ |= (unsigned)__shfl_xor((int)pk_, {o}, 64);")
+                o <<= 1
+            b.append(f"{i2}if ((lane & {L - 1}) == 0) a.tags[(nb + {u}) * {8 * W} + "
+                     f"(lane >> {L.bit_length() - 1})] = pk_;")
+            if mode == "rec":
+                b.append(f"{i2}*(hs_i4*)(a.MOUT + (((nb + {u}) << 8) + 4 * lane)) = mo_;")
+            b.append(f"{ind}}}")
+        b.append(f"{ind}gbase = __builtin_amdgcn_readlane(nx_, 63);")
+
+    b.extend([
+        f"  auto IMG = [&](int row_) -> unsigned {{ return {img}; }};",
+        f"  auto IMGF = [&](int row_) -> unsigned {{ return {imgf}; }};",
+        f"  auto IMGV = [&]({rkt} w_) -> unsigned {{ return {imgv}; }};",
+        "  const int lane = (int)(threadIdx.x & 63);",
+        "  const i64 G = (a.NRUNS + 63) >> 6;",
+        "  const int NR = (int)a.NRUNS, NB = (int)((a.NRUNS + 255) >> 8);",
+        f"  const int nwv = (int)gridDim.x * {WV};",
+        f"  const int wv = (int)blockIdx.x * {WV} + "
+        "__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
+        # whole stages per wavefront, so only a chunk's last stage can be cut by its end
+        f"  const int per = ((NB + nwv - 1) / nwv + {U - 1}) / {U} * {U};",
+        "  const int bbeg = wv * per;",
+        "  const int bend = NB < bbeg + per ? NB : bbeg + per;",
+        "  if (bbeg >= bend || a.NRG <= 0) return;",
+        "  const i64 gend = G < ((i64)bend << 2) ? G : ((i64)bend << 2);",
+        "  const i64* RG = a.RNG;",
+        "  int rg = 0;",
+        "  { int lo = 0, hi = (int)a.NRG; const i64 r0 = (i64)bbeg << 8;",
+        "    while (hi - lo > 1) { const int m = (lo + hi) >> 1; "
+        "if (RG[4 * m] <= r0) lo = m; else hi = m; }",
+        "    rg = lo; }",
+        "  int lr0 = (int)RG[4 * rg], lr1 = (int)RG[4 * rg + 1], s0 = (int)RG[4 * rg + 2], "
+        "s1 = (int)RG[4 * rg + 3];",
+        "  i64 nxt0 = rg + 1 < a.NRG ? RG[4 * (rg + 1)] : 0x7fffffffffffffffll;",
+        "  int gbase = -1;   // right row of the next stage's first run (-1: range-relative)"])
+    for s in sets:
+        b.append(f"  int pb{s} = 0; " + " ".join(
+            f"hs_v4u L{s}{u} = {{}}; hs_rk4 R{s}{u} = {{}};" +
+            "".join(f" hs_c{sl}x4 C{sl}{s}{u} = {{}};" for sl in stage_slots)
+            for u in range(U)))
+    b.extend(["  int nb = bbeg;",
+              "  while (nb < bend) {",
+              "    while (nxt0 <= ((i64)nb << 8)) {"] + adv("      ") + ["    }"])
+    fast("nb", 0, "    ")
+    b.extend(["    if (!f_) {   // slow block: its 64-run groups one at a time",
+              "#pragma unroll 1",
+              "      for (i64 gi = (i64)nb << 2; gi < (((i64)nb + 1) << 2) && gi < gend; ++gi) {",
+              "        while (nxt0 <= (gi << 6)) {"] + adv("          ") + ["        }"])
+    group(0, False, "        ")
+    resolve(0, "        ")
+    b.extend(["        gbase = __builtin_amdgcn_readlane((hit0 && own0) ? m0 + 1 : -1, 63);",
+              "      }",
+              "      ++nb; continue;",
+              "    }"])
+    load("A", "rb_", "base_", "    ")
+    b.append("    for (;;) {")
+    for s, t in (("A", "B"), ("B", "A")):
+        # set s holds the stage at nb: issue the next stage's loads into set t, then resolve s.
+        # The loads are unconditional (under a branch the compiler would wait for them where
+        # the paths merge): when the next stage is not fast they re-read this stage's
+        # addresses, which passed the test, and the loop ends after this stage
+        b.append("      {")
+        fast(f"nb + {U}", R, "        ")
+        b.append(f"        const int nr_ = f_ ? rb_ : (nb << 8), nj_ = f_ ? base_ : pb{s};")
+        load(t, "nr_", "nj_", "        ")
+        resolve_stage(s, "        ")
+        # (leaving the loop: drain the re-read, or the compiler's wait counts, which merge
+        # every path into the loop head, would wait for it in every iteration: vmcnt(0))
+        b.extend([f"        nb += {U};",
+                  "        if (!f_) { __builtin_amdgcn_s_waitcnt(0x0F70); break; }",
+                  "      }"])
+    b.extend(["    }", "  }"])
+    src = (J._PRELUDE + args.struct_src() + "\n".join(tdefs) + "\n" +
            f'extern "C" __global__ __launch_bounds__({J.BLOCK}) void hs_jit_run_tags2(Args a) {{\n' +
            "\n".join(b) + "\n}\n")
     return J.Kernel(src, "hs_jit_run_tags2", args)
@@ -1428,7 +1629,7 @@ def lower(p: NL.JoinParams, rstart, rlen, rbucket, roff, compacts, runs, nrows: 
     vt = {"RNG": rng_d.data_ptr(), "NRG": len(rng), "NRUNS": nruns, "tags": tags.data_ptr(),
           "num_groups": p.num_groups, "group_base": p.group_base}
     tr = rng_d
-    grid_t = max(1, RT2_GRID)
+    grid_t = max(1, RT2_WIDE_GRID if tags2_wide(p, compacts, ix32) == 4 else RT2_GRID)
     vt["KLO"], vt["KSP"], vt["KOF"] = frame
     J._fill_cols(vt, p.cols, compacts)
     lo = lo16_keys(p, compacts, W, vt, nruns, int(roff[-1].item()), grid_t, dev) \

@@ -72,8 +72,15 @@ class KernelConfig:
     # --- two-phase run-keyed join (exec/jit_runs.py) ----------------------------------------
     mj_2p: bool = True           # two phases (tags, then the left rows' scan)
     rs_items: int = 16           # rows per thread of the dense phase-2 scan (W > 1 tags)
-    rt2_unroll: int = 4          # phase-1 64-run groups in flight per wavefront iteration
+    rt2_unroll: int = 4          # phase-1 64-run groups in flight per wavefront iteration; in the
+    #                              four-run form, 256-run blocks per pipeline stage (at most 2)
     rt2_grid: int = 8192
+    rt2_wide: int = 4            # runs per lane of the verifying phase 1: 1 (one dword / short
+    #                              load per run) or 4 (256-run blocks, 16-byte loads, the next
+    #                              stage's loads issued before this one resolves; 32-bit indices,
+    #                              plain right columns: jit_runs.tags2_wide, else the 1 form).
+    #                              SF100 step 0.714 -> 0.705 ms (profiles/bench_tags2_wide.jsonl)
+    rt2_wide_grid: int = 16384   # grid of the four-run form (rt2_grid stays the one-run forms')
     rt2_i32: bool = True         # phase-1 run / right-row index math in 32 bits when tables fit
     rt2_match: bool = True       # phase 1 reads a per-run matched right row recorded at lowering
     #                              (literal-independent) instead of re-verifying the key match
