@@ -33,6 +33,10 @@ against the same query with Hyperspace disabled (the reference's correctness ora
   range filter: ungrouped, grouped by one dictionary column (few groups, the dense level 2) and
   grouped by an integer column (>= 10^5 groups at SF >= 5, the hash level 2); q/s on the device
   against the host engine, the level-1 and level-2 kernel times and the level-2 shape that ran.
+* ``window`` — window functions over TPC-H SF-N ``lineitem`` through an index on
+  ``l_orderkey``: top-3 lines per order by price (``row_number``, filtered and aggregated), a
+  running ``sum(l_quantity)`` per supplier by ship date, and a per-order total that needs no
+  sort; q/s on the device against the host engine and whether the device sort was skipped.
 """
 import argparse
 import datetime
@@ -754,10 +758,78 @@ def config_count_distinct(args):
     return out
 
 
+def config_window(args):
+    """Window functions over ``lineitem`` (index on ``l_orderkey``), each shape aggregated to one
+    row so the result copy does not dominate: ``top3`` ranks every order's lines by price
+    (partitioned on the index key, ordered by another column: one device sort), ``running``
+    sums quantities per supplier by ship date (partitioned on a non-key column: one device
+    sort), ``per_order`` takes each order's total (the index order is the window's: no sort).
+    Each is cross-checked against the host engine (``HS_CFG_SKIP_HOST=1`` skips that, for a
+    kernel-trace run)."""
+    from hyperspace_amd import (Hyperspace, IndexConfig, Window, col, count, max_, row_number,
+                                sum_)
+    sf = args.sf
+    data, _ = _tpch(args, sf)
+    root = os.path.join(args.data_dir, f"cfg_window_sf{sf:g}")
+    shutil.rmtree(root, ignore_errors=True)
+    s = _session(root, args.device, args.buckets)
+    hs = Hyperspace(s)
+    li = s.read.parquet(os.path.join(data, "lineitem"))
+    dt, _ = _build(hs, li, IndexConfig("li_win", ["l_orderkey"], [
+        "l_suppkey", "l_shipdate", "l_quantity", "l_extendedprice"]), args.device)
+    Hyperspace.enable(s)
+
+    def base(i):
+        return li.filter(col("l_orderkey") >= i % 4)
+
+    def top3(i):
+        w = Window.partitionBy("l_orderkey").orderBy(col("l_extendedprice").desc())
+        return base(i).select("l_extendedprice", row_number().over(w).alias("rn")) \
+            .filter(col("rn") <= 3).agg(sum_("l_extendedprice").alias("top3_price"),
+                                        count("*").alias("n"))
+
+    def running(i):
+        w = Window.partitionBy("l_suppkey").orderBy("l_shipdate")
+        return base(i).select(sum_("l_quantity").over(w).alias("run")) \
+            .agg(max_("run").alias("max_run"), sum_("run").alias("sum_run"), count("*").alias("n"))
+
+    def per_order(i):
+        w = Window.partitionBy("l_orderkey")
+        return base(i).select("l_quantity", sum_("l_quantity").over(w).alias("tot")) \
+            .filter(col("tot") > 150.0).agg(sum_("l_quantity").alias("q"), count("*").alias("n"))
+    shapes = {"top3": top3, "running": running, "per_order": per_order}
+    out = {"config": "window", "device": args.device, "sf": sf, "index_build_s": round(dt, 3),
+           "shapes": {}}
+    got = {}
+    for name, q in shapes.items():
+        r = {"index_used": "li_win" in q(0).queryExecution.executed_plan.tree_string()}
+        got[name] = [_rows(q(i)) for i in range(2)]
+        be = s.backend()
+        r["path"] = getattr(be, "last_path", None)
+        r["fallback_reason"] = getattr(be, "fallback_reason", None)
+        r["sort_skipped"] = be.metrics.get("window_sort_skipped")
+        r["rows"] = got[name][0][0][-1]
+        k = args.steps
+        el = _timed_loop(lambda i: q(i).collect(), k, args.device)
+        r["queries_per_s"] = round(k / el, 3)
+        r["ms_per_query"] = round(el / k * 1e3, 2)
+        out["shapes"][name] = r
+    if os.environ.get("HS_CFG_SKIP_HOST"):
+        return out
+    s.conf.set("spark.hyperspace.mi.execution.device", "cpu")
+    for name, q in shapes.items():
+        t0 = time.perf_counter()
+        ref = [_rows(q(i)) for i in range(2)]
+        out["shapes"][name]["host_engine_queries_per_s"] = round(2 / (time.perf_counter() - t0), 4)
+        out["shapes"][name]["match"] = all(_close(a, b) for a, b in zip(got[name], ref))
+    out["match"] = all(r["match"] for r in out["shapes"].values())
+    return out
+
+
 CONFIGS = {"csv10k": config_csv10k, "sf10_filter": config_sf10_filter, "hybrid": config_hybrid,
            "q3_3way": config_q3_3way, "tpcds_3way": config_tpcds_3way,
            "streamed": config_streamed, "like": config_like,
-           "count_distinct": config_count_distinct}
+           "count_distinct": config_count_distinct, "window": config_window}
 
 
 def main():

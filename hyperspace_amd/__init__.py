@@ -10,10 +10,10 @@ from .hyperspace import Hyperspace, get_context
 from .index.config import IndexConfig
 from .session import Session
 from .plan.column import (col, lit, sum_, count, countDistinct, count_distinct, min_, max_,
-                          avg)
+                          avg, row_number, rank, dense_rank, Window, WindowSpec)
 
 __all__ = ["Hyperspace", "IndexConfig", "Session", "HyperspaceException", "NoChangesException",
            "col", "lit", "sum_", "count", "countDistinct", "count_distinct", "min_", "max_",
-           "avg", "get_context"]
+           "avg", "row_number", "rank", "dense_rank", "Window", "WindowSpec", "get_context"]
 
 __version__ = "0.1.0"

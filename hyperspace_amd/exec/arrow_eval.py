@@ -125,6 +125,12 @@ def eval_expr(e: E.Expression, t: pa.Table):
         b = pc.cast(b, pa.float64())
         q = pc.divide(pc.cast(a, pa.float64()), b)
         return pc.if_else(pc.equal(b, 0.0), pa.scalar(None, pa.float64()), q)
+    if isinstance(e, E.NormalizeNaNAndZero):
+        v = eval_expr(e.child, t)
+        if not pa.types.is_floating(v.type):
+            return v
+        return pc.if_else(pc.is_nan(v), pa.scalar(float("nan"), v.type),
+                          pc.add(v, pa.scalar(0.0, v.type)))
     if isinstance(e, E.Cast):
         v = eval_expr(e.child, t)
         if _is_num(v.type) and _is_num(e.dtype):

@@ -159,21 +159,30 @@ class CpuBackend:
     def _exec_BroadcastExchangeExec(self, p):
         return [_concat(self.execute(p.child), p.child.output)]
 
-    def _sort_table(self, t: pa.Table, order) -> pa.Table:
-        if t.num_rows <= 1:
+    def _sort_table(self, t: pa.Table, order, nan_largest: bool = False) -> pa.Table:
+        """``nan_largest``: NaN sorts as the greatest float value (after every number ascending,
+        before them descending) instead of where pyarrow puts it, beside the NULLs."""
+        if t.num_rows <= 1 or not order:
             return t
         tmp = t
         keys = []
         for i, o in enumerate(order):
             name = f"__sort{i}"
-            tmp = tmp.append_column(name, eval_expr(o.child, t))
+            v = eval_expr(o.child, t)
+            if nan_largest and pa.types.is_floating(v.type):
+                # a leading 0 / 1 "is NaN" key (NULL where the value is): same direction and
+                # null placement as the value
+                tmp = tmp.append_column(name + "n", pc.cast(pc.is_nan(v), pa.int8()))
+                keys.append((name + "n", "ascending" if o.ascending else "descending",
+                             "at_start" if o.ascending else "at_end"))
+            tmp = tmp.append_column(name, v)
             keys.append((name, "ascending" if o.ascending else "descending",
                          "at_start" if o.ascending else "at_end"))
         idx = pc.sort_indices(tmp, sort_keys=keys)
         return t.take(idx)
 
     def _exec_SortExec(self, p):
-        return [self._sort_table(t, p.order) for t in self.execute(p.child)]
+        return [self._sort_table(t, p.order, p.nan_largest) for t in self.execute(p.child)]
 
     # -- joins ----------------------------------------------------------------------------------
     def _join_tables(self, lt, rt, lkeys, rkeys, join_type, condition, out_attrs, lattrs, rattrs):
@@ -434,6 +443,113 @@ class CpuBackend:
             pa.table({"__x": pa.array(np.zeros(nrows))})
         return eval_expr(rewritten, t)
 
+    # -- window functions -----------------------------------------------------------------------
+    def _exec_WindowExec(self, p):
+        return [self._window_table(p, t) for t in self.execute(p.child)]
+
+    def _window_table(self, p, t: pa.Table) -> pa.Table:
+        """The window columns of one partition of the plan, whose rows arrive sorted by
+        (partition keys ascending, order keys) - by the Sort below, or by the index.  Row i
+        starts a partition when a partition key differs from row i - 1 (NULL equals NULL, every
+        NaN equals every NaN, 0.0 equals -0.0) and a peer group when an order key does too;
+        every function is a scan over those flags, read at the last row of the row's frame."""
+        n = t.num_rows
+        phead = np.zeros(n, dtype=bool)
+        if n:
+            phead[0] = True
+        for e in p.partition_by:
+            phead |= _changes(eval_expr(e, t), n)
+        qhead = phead.copy()
+        for o in p.order_by:
+            qhead |= _changes(eval_expr(o.child, t), n)
+        idx = np.arange(n, dtype=np.int64)
+        pstart = np.maximum.accumulate(np.where(phead, idx, 0)) if n else idx
+        qstart = np.maximum.accumulate(np.where(qhead, idx, 0)) if n else idx
+        # the frame's last row: the row before the next peer head (running frame), or before
+        # the next partition head (whole-partition frame)
+        heads = qhead if p.order_by else phead
+        nxt = np.where(heads, idx, n)
+        end = (np.minimum.accumulate(np.append(nxt[1:], n)[::-1])[::-1] - 1) if n else idx
+        cols = []
+        for a in p.window_exprs:
+            fn = a.child.function
+            if isinstance(fn, E.RowNumber):
+                v = pa.array((idx - pstart + 1).astype(np.int32))
+            elif isinstance(fn, E.Rank):
+                v = pa.array((qstart - pstart + 1).astype(np.int32))
+            elif isinstance(fn, E.DenseRank):
+                c = np.cumsum(qhead)
+                v = pa.array((c - c[pstart] + 1).astype(np.int32) if n else
+                             np.zeros(0, np.int32))
+            else:
+                v = self._window_agg(fn, t, n, phead, pstart, end)
+            if not v.type.equals(a.data_type):
+                v = v.cast(a.data_type)
+            cols.append(v)
+        for a, v in zip(p.window_exprs, cols):
+            t = t.append_column(pa.field(key(a.to_attribute()), v.type, True), v)
+        return t
+
+    @staticmethod
+    def _window_agg(fn, t: pa.Table, n: int, phead, pstart, end) -> pa.Array:
+        """sum / count / min / max / avg of ``fn``'s argument over each row's frame
+        [partition start, ``end``]: a segmented inclusive scan restarting at ``phead``, read at
+        ``end``; NULL inputs contribute nothing, a frame without a non-NULL input is NULL (0
+        for count)."""
+        if fn.child is None:
+            arg = pa.array(np.ones(n, dtype=np.int64))
+        else:
+            arg = eval_expr(fn.child, t)
+            if isinstance(arg, pa.ChunkedArray):
+                arg = arg.combine_chunks() if arg.num_chunks != 1 else arg.chunk(0)
+            if pa.types.is_decimal(arg.type):
+                arg = pc.cast(arg, pa.float64())
+        valid = np.asarray(arg.is_valid().to_numpy(zero_copy_only=False), dtype=bool) \
+            if n else np.zeros(0, bool)
+        cnt = _seg_cumsum(valid.astype(np.int64), pstart)[end] if n else np.zeros(0, np.int64)
+        if isinstance(fn, E.Count):
+            return pa.array(cnt, pa.int64())
+        null = cnt == 0
+        if isinstance(fn, (E.Min, E.Max)):
+            dictionary = None
+            if not (pa.types.is_integer(arg.type) or pa.types.is_floating(arg.type)):
+                # any ordered type through the ranks of its sorted distinct values
+                dictionary = pc.unique(arg.drop_null()).sort()
+                arg = pc.index_in(arg, value_set=dictionary).cast(pa.int64())
+            x = np.asarray(arg.fill_null(0).to_numpy(zero_copy_only=False)) if n else \
+                np.zeros(0, np.int64)
+            if x.dtype.kind == "f":
+                ident = np.inf if isinstance(fn, E.Min) else -np.inf
+                op = np.fmin if isinstance(fn, E.Min) else np.fmax     # NaN: skipped, as by
+            else:                                                      # the aggregates
+                info = np.iinfo(x.dtype)
+                ident = info.max if isinstance(fn, E.Min) else info.min
+                op = np.minimum if isinstance(fn, E.Min) else np.maximum
+            x = np.where(valid, x, np.array(ident, dtype=x.dtype))
+            got = _seg_scan(x, phead, op)[end] if n else x
+            if x.dtype.kind == "f" and n:
+                # a frame whose inputs are all NaN: the identity is no input value
+                nan = np.isnan(np.where(valid, np.asarray(
+                    arg.fill_null(0).to_numpy(zero_copy_only=False)), 0.0))
+                nn = _seg_cumsum((valid & ~nan).astype(np.int64), pstart)[end]
+                got = np.where((nn == 0) & ~null, np.nan, got)
+            if dictionary is not None:
+                return dictionary.take(pa.array(got, pa.int64(), mask=null)) if len(dictionary) \
+                    else pa.nulls(n, dictionary.type)
+            return pa.array(got, mask=null).cast(arg.type)
+        x = np.asarray(arg.fill_null(0).to_numpy(zero_copy_only=False)) if n else \
+            np.zeros(0, np.float64)
+        if isinstance(fn, E.Sum) and x.dtype.kind in "iub":
+            s = _seg_cumsum(np.where(valid, x, 0).astype(np.int64), pstart)[end] if n else \
+                np.zeros(0, np.int64)
+            return pa.array(s, pa.int64(), mask=null)
+        x = np.where(valid, x, 0).astype(np.float64)
+        s = _seg_scan(x, phead, np.add)[end] if n else x
+        if isinstance(fn, E.Avg):
+            with np.errstate(divide="ignore", invalid="ignore"):
+                s = s / cnt
+        return pa.array(s, pa.float64(), mask=null)
+
     # -- unions ---------------------------------------------------------------------------------
     def _rename_like(self, t: pa.Table, src_attrs, dst_attrs) -> pa.Table:
         return pa.Table.from_arrays(t.columns, names=[key(a) for a in dst_attrs])
@@ -450,6 +566,54 @@ class CpuBackend:
         n = p.bucket_spec.num_buckets
         assert all(len(cp) == n for cp in child_parts)
         return [_concat([cp[i] for cp in child_parts], p.output) for i in range(n)]
+
+
+def _changes(col, n: int) -> np.ndarray:
+    """flags[i]: row i's value differs from row i - 1's (flags[0] is False).  NULL equals NULL;
+    for floats every NaN equals every NaN and 0.0 equals -0.0."""
+    out = np.zeros(n, dtype=bool)
+    if n < 2:
+        return out
+    if isinstance(col, pa.ChunkedArray):
+        col = col.combine_chunks() if col.num_chunks != 1 else col.chunk(0)
+    valid = np.asarray(col.is_valid().to_numpy(zero_copy_only=False), dtype=bool)
+    t = col.type
+    if pa.types.is_floating(t):
+        v = np.asarray(col.fill_null(0).to_numpy(zero_copy_only=False))
+        nan = np.isnan(v)
+        same = (v[1:] == v[:-1]) | (nan[1:] & nan[:-1])
+    else:
+        if not pa.types.is_integer(t):
+            # any other type by the codes of its distinct values
+            col = pc.index_in(col, value_set=pc.unique(col.drop_null()))
+        v = np.asarray(col.fill_null(0).to_numpy(zero_copy_only=False))
+        same = v[1:] == v[:-1]
+    both = valid[1:] & valid[:-1]
+    out[1:] = ~((both & same) | (~valid[1:] & ~valid[:-1]))
+    return out
+
+
+def _seg_cumsum(x: np.ndarray, pstart: np.ndarray) -> np.ndarray:
+    """Inclusive int64 running sums restarting at each partition start (exact: the difference
+    of two prefix sums in wrapping integer arithmetic)."""
+    c = np.cumsum(x)
+    return c - (c[pstart] - x[pstart])
+
+
+def _seg_scan(x: np.ndarray, heads: np.ndarray, op) -> np.ndarray:
+    """Inclusive segmented scan of ``x`` with ``op`` (add, minimum, fmin, ...), restarting at
+    the rows flagged in ``heads``: log2(n) doubling passes (Hillis-Steele with a carried
+    'a head lies in my window' flag), no subtraction - so an infinity or NaN in one partition
+    never leaks into the next, and float sums lose nothing to cancellation."""
+    val = x.copy()
+    flag = heads.copy()
+    d, n = 1, len(x)
+    while d < n:
+        take = ~flag[d:]
+        val[d:] = np.where(take, op(val[d:], val[:-d]), val[d:])
+        flag[d:] = flag[d:] | flag[:-d]
+        d *= 2
+    return val
 
 
 def _align_keys(a, b):

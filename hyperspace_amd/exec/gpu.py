@@ -9,6 +9,8 @@ needs rows, so the hot shapes compile into single fused launches:
 * ``Filter/Project <- Scan``                       -> ``hs_scan_select`` + ``hs_gather``
 * ``SortMergeJoin``                                 -> ``hs_join_count/emit`` + gathers
 * ``Exchange(hashpartitioning) <- Scan``           -> Murmur3 + radix sort on the device
+* ``Window <- [Sort <- Exchange] <- rows``          -> one device sort (none over a matching index)
+                                                      + segmented scans (exec/window.py)
 
 Under ``torch.distributed`` each rank owns the buckets the session's owner map gives it
 (``parallel/placement.py``: size-balanced, ``b % world`` for equal sizes; co-partitioned, so a
@@ -351,6 +353,9 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps):
                         len({x[ai].data.dtype for x in pieces}) > 1:
                     raise Unsupported("union of differently typed columns")
             return self._concat_rels(pieces, out_attrs)
+        if isinstance(p, X.WindowExec):
+            from .window import window_rel
+            return window_rel(self, p)
         if isinstance(p, X.ReusedExchangeExec):
             # the device repartition of a resident table is cached, so the original subtree
             # replays the first exchange's result

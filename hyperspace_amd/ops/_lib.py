@@ -115,6 +115,16 @@ class XchCopy(C.Structure):
                 ("elem_bytes", C.c_int32), ("pad", C.c_int32)]
 
 
+WIN_MAX_KEYS = 8
+# WinAgg (csrc/kernels/window.hip)
+WA_SUM_I64, WA_SUM_F64, WA_COUNT, WA_MIN_I64, WA_MAX_I64, WA_MIN_F64, WA_MAX_F64 = range(7)
+
+
+class WinKeys(C.Structure):
+    _fields_ = [("part", ColDesc * WIN_MAX_KEYS), ("order", ColDesc * WIN_MAX_KEYS),
+                ("npart", C.c_int32), ("norder", C.c_int32)]
+
+
 _lib = None
 
 
@@ -149,7 +159,8 @@ def lib():
     for name, st in (("hs_hash_params_size", HashParams), ("hs_scan_params_size", ScanParams),
                      ("hs_join_params_size", JoinParams), ("hs_sort_key_spec_size", SortKeySpec),
                      ("hs_gather_params_size", GatherParams), ("hs_xch_params_size", XchParams),
-                     ("hs_xch_copy_size", XchCopy), ("hs_merge_keys_size", MergeKeys)):
+                     ("hs_xch_copy_size", XchCopy), ("hs_merge_keys_size", MergeKeys),
+                     ("hs_win_keys_size", WinKeys)):
         f = getattr(L, name)
         f.restype = C.c_int
         if f() != C.sizeof(st):
@@ -243,6 +254,12 @@ def lib():
          P, P, P, P, I64, P, P, P, P, P, P, P)
     _sig(L.hs_distinct_regroup, I, P, P, P, P, P, P, I64, I64, I, U64, I, I, I,
          P, P, P, P, P, I64, P, P)
+    _sig(L.hs_win_tile_rows, I)
+    _sig(L.hs_win_workspace_bytes, I64, I64)
+    _sig(L.hs_win_heads, I, P, I64, P, P)
+    _sig(L.hs_win_rank, I, P, I64, P, P, P, P, P)
+    _sig(L.hs_win_frame_ends, I, P, I64, I, P, P, P)
+    _sig(L.hs_win_agg, I, P, P, P, I64, I, P, P, P, P, P)
     _lib = L
     return L
 

@@ -302,6 +302,99 @@ def exclusive_scan_i64(x):
 
 
 # ------------------------------------------------------------------------------------------------
+# Window functions (csrc/kernels/window.hip): rows already in (partition, order) order
+# ------------------------------------------------------------------------------------------------
+def win_tile_rows() -> int:
+    return int(NL.lib().hs_win_tile_rows())
+
+
+def win_workspace(n: int, device):
+    """Scratch of one ``win_rank`` / ``win_frame_ends`` / ``win_agg`` call over ``n`` rows; calls
+    on one stream may share it."""
+    torch = _torch()
+    nbytes = int(NL.lib().hs_win_workspace_bytes(n))
+    return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+
+
+def win_heads(part_cols: Sequence, order_cols: Sequence, n: int, device):
+    """uint8[n]: bit 0 = the row starts a partition, bit 1 = it starts a peer group (row i
+    against row i - 1 on the key columns; NULL equals NULL, NaN equals NaN, 0.0 equals -0.0)."""
+    torch = _torch()
+    if len(part_cols) > NL.WIN_MAX_KEYS or len(order_cols) > NL.WIN_MAX_KEYS:
+        raise ValueError(f"at most {NL.WIN_MAX_KEYS} partition and {NL.WIN_MAX_KEYS} order keys")
+    for c in list(part_cols) + list(order_cols):
+        if len(c) != n:
+            raise ValueError("key column length differs from the row count")
+    keys = NL.WinKeys()
+    for i, c in enumerate(part_cols):
+        keys.part[i] = c.desc()
+    for i, c in enumerate(order_cols):
+        keys.order[i] = c.desc()
+    keys.npart, keys.norder = len(part_cols), len(order_cols)
+    flags = torch.empty(n, dtype=torch.uint8, device=device)
+    NL.check(NL.lib().hs_win_heads(C.byref(keys), n, NL.ptr(flags), NL.stream_ptr()),
+             "hs_win_heads")
+    return flags
+
+
+def win_rank(flags, row_number: bool = True, rank: bool = True, dense_rank: bool = True,
+             ws=None):
+    """(row_number, rank, dense_rank) int32 tensors (None where not asked for) from the head
+    flags of ``win_heads``."""
+    torch = _torch()
+    n = int(flags.numel())
+    ws = ws if ws is not None else win_workspace(n, flags.device)
+    if ws.numel() < int(NL.lib().hs_win_workspace_bytes(n)):
+        raise ValueError("window workspace too small")
+    outs = [torch.empty(n, dtype=torch.int32, device=flags.device) if want else None
+            for want in (row_number, rank, dense_rank)]
+    NL.check(NL.lib().hs_win_rank(NL.ptr(flags), n, NL.ptr(outs[0]), NL.ptr(outs[1]),
+                                  NL.ptr(outs[2]), NL.ptr(ws), NL.stream_ptr()), "hs_win_rank")
+    return tuple(outs)
+
+
+def win_frame_ends(flags, whole: bool, ws=None):
+    """int64[n]: the last row of every row's frame - of its partition (``whole``) or of its peer
+    group (the running frame of a window with an ORDER BY)."""
+    torch = _torch()
+    n = int(flags.numel())
+    ws = ws if ws is not None else win_workspace(n, flags.device)
+    if ws.numel() < int(NL.lib().hs_win_workspace_bytes(n)):
+        raise ValueError("window workspace too small")
+    ends = torch.empty(n, dtype=torch.int64, device=flags.device)
+    NL.check(NL.lib().hs_win_frame_ends(NL.ptr(flags), n, 1 if whole else 0, NL.ptr(ends),
+                                        NL.ptr(ws), NL.stream_ptr()), "hs_win_frame_ends")
+    return ends
+
+
+def win_agg(col, flags, ends, kind: int, ws=None, with_count: bool = False):
+    """(values, valid) of one windowed aggregate - (values, valid, counts) when ``with_count``,
+    counts being the non-NULL inputs of each row's frame (int64): the segmented inclusive scan of ``col``
+    (restarting at flag bit 0) read at ``ends``.  ``kind``: ``NL.WA_*``; values are int64 for
+    the integer kinds and the count, float64 otherwise; valid is uint8 (1 = the frame holds a
+    non-NULL input).  ``col`` None counts every row (``count(*)``).  Float min / max skip NaN
+    like a NULL; a frame whose non-NULL inputs are all NaN gives NaN."""
+    torch = _torch()
+    n = int(flags.numel())
+    if ends.numel() != n or (col is not None and len(col) != n):
+        raise ValueError("window aggregate inputs differ in length")
+    if ends.dtype != torch.int64 or flags.dtype != torch.uint8:
+        raise ValueError("window flags must be uint8 and frame ends int64")
+    ws = ws if ws is not None else win_workspace(n, flags.device)
+    if ws.numel() < int(NL.lib().hs_win_workspace_bytes(n)):
+        raise ValueError("window workspace too small")
+    floating = kind in (NL.WA_SUM_F64, NL.WA_MIN_F64, NL.WA_MAX_F64)
+    out = torch.empty(n, dtype=torch.float64 if floating else torch.int64, device=flags.device)
+    valid = torch.empty(n, dtype=torch.uint8, device=flags.device)
+    counts = torch.empty(n, dtype=torch.int64, device=flags.device) if with_count else None
+    desc = col.desc() if col is not None else NL.ColDesc(0, 0, NL.I64, 0)
+    NL.check(NL.lib().hs_win_agg(C.byref(desc), NL.ptr(flags), NL.ptr(ends), n, int(kind),
+                                 NL.ptr(out), NL.ptr(valid), NL.ptr(counts), NL.ptr(ws),
+                                 NL.stream_ptr()), "hs_win_agg")
+    return (out, valid, counts) if with_count else (out, valid)
+
+
+# ------------------------------------------------------------------------------------------------
 # Gather
 # ------------------------------------------------------------------------------------------------
 # packed-row gather (hs_gather_packed, opt-in: HS_GATHER_PACKED=1): tables of at least this many

@@ -117,6 +117,14 @@ class Column:
         c.sort_ascending = False
         return c
 
+    def over(self, window: "WindowSpec"):
+        """This function over a window: ``sum_("x").over(Window.partitionBy("k"))``."""
+        if isinstance(window, type) and issubclass(window, Window):
+            window = WindowSpec()
+        if not isinstance(window, WindowSpec):
+            raise TypeError(f"over() takes a Window specification, got {window!r}")
+        return Column(E.WindowExpression(self.expr, window.definition()))
+
     def alias(self, name: str):
         return Column(E.Alias(self.expr, name))
 
@@ -179,6 +187,84 @@ def max_(c) -> Column:
 
 def avg(c) -> Column:
     return Column(E.Avg(_expr(col(c) if isinstance(c, str) else c)))
+
+
+def row_number() -> Column:
+    """1, 2, 3, ... within the partition, in the window's order (ties in an unspecified
+    order)."""
+    return Column(E.RowNumber())
+
+
+def rank() -> Column:
+    """The row's rank in the window's order: peers share a rank, the next one skips."""
+    return Column(E.Rank())
+
+
+def dense_rank() -> Column:
+    """Like ``rank`` without gaps."""
+    return Column(E.DenseRank())
+
+
+def _key_expr(c) -> E.Expression:
+    if isinstance(c, str):
+        from .parser import parse_expression
+        return E.UnresolvedAttribute(c) if c.isidentifier() else parse_expression(c)
+    return _expr(c)
+
+
+class WindowSpec:
+    """An immutable ``PARTITION BY ... ORDER BY ...`` (``Window.partitionBy("k").orderBy("d")``).
+    Frames are Spark's defaults; ``rowsBetween`` / ``rangeBetween`` raise."""
+
+    def __init__(self, partition_by=(), order_by=()):
+        self._partition = tuple(partition_by)
+        self._order = tuple(order_by)      # (expression, ascending)
+
+    @staticmethod
+    def _flat(cols):
+        if len(cols) == 1 and isinstance(cols[0], (list, tuple)):
+            return tuple(cols[0])
+        return cols
+
+    def partitionBy(self, *cols) -> "WindowSpec":
+        return WindowSpec([_key_expr(c) for c in self._flat(cols)], self._order)
+
+    def orderBy(self, *cols) -> "WindowSpec":
+        orders = [(_key_expr(c), bool(getattr(c, "sort_ascending", True)))
+                  for c in self._flat(cols)]
+        return WindowSpec(self._partition, orders)
+
+    def rowsBetween(self, start, end):
+        raise E._frame_error(f"ROWS BETWEEN {start} AND {end}")
+
+    def rangeBetween(self, start, end):
+        raise E._frame_error(f"RANGE BETWEEN {start} AND {end}")
+
+    def definition(self) -> E.WindowSpecDefinition:
+        return E.WindowSpecDefinition(self._partition, self._order)
+
+
+class Window:
+    """Entry points of a window specification, as in PySpark."""
+    unboundedPreceding = -(1 << 63)
+    unboundedFollowing = (1 << 63) - 1
+    currentRow = 0
+
+    @staticmethod
+    def partitionBy(*cols) -> WindowSpec:
+        return WindowSpec().partitionBy(*cols)
+
+    @staticmethod
+    def orderBy(*cols) -> WindowSpec:
+        return WindowSpec().orderBy(*cols)
+
+    @staticmethod
+    def rowsBetween(start, end):
+        return WindowSpec().rowsBetween(start, end)
+
+    @staticmethod
+    def rangeBetween(start, end):
+        return WindowSpec().rangeBetween(start, end)
 
 
 def input_file_name() -> Column:  # documented for API parity; lineage is attached natively.

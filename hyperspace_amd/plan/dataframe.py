@@ -172,6 +172,10 @@ class DataFrame:
     # -- transformations ---------------------------------------------------------------------
     def filter(self, condition) -> "DataFrame":
         e = parse_expression(condition) if isinstance(condition, str) else self._to_expr(condition)
+        if E.contains_window(e):
+            raise HyperspaceException(
+                "window functions are not allowed in a filter: compute the column first "
+                "(select / withColumn) and filter the result")
         return DataFrame(self.session, L.Filter(self._resolve(e), self.plan))
 
     where = filter
@@ -189,8 +193,12 @@ class DataFrame:
                 e = E.Alias(e, e.sql())
             exprs.append(e)
         if any(E.contains_aggregate(e) for e in exprs):
+            if any(E.contains_window(e) for e in exprs):
+                raise HyperspaceException(
+                    "window functions beside aggregates in one select are not supported: "
+                    "aggregate first, then select the window functions over the result")
             return DataFrame(self.session, L.Aggregate([], exprs, self.plan))
-        return DataFrame(self.session, L.Project(exprs, self.plan))
+        return DataFrame(self.session, L.project_with_windows(exprs, self.plan))
 
     def toDF(self, *names) -> "DataFrame":
         if len(names) != len(self.plan.output):
@@ -207,7 +215,7 @@ class DataFrame:
     def withColumn(self, name: str, c) -> "DataFrame":
         e = self._resolve(self._to_expr(c))
         exprs = [a for a in self.plan.output if a.name != name] + [E.Alias(e, name)]
-        return DataFrame(self.session, L.Project(exprs, self.plan))
+        return DataFrame(self.session, L.project_with_windows(exprs, self.plan))
 
     def drop(self, *names) -> "DataFrame":
         keep = [a for a in self.plan.output if a.name not in names]
@@ -409,6 +417,11 @@ def _dedup(plan: L.LogicalPlan, conflicting: set):
         if isinstance(p, L.RepartitionByExpression):
             return L.RepartitionByExpression([rewrite_expr(e) for e in p.partition_expressions],
                                              p.child, p.num_partitions)
+        if isinstance(p, L.Window):
+            return L.Window([rewrite_expr(e) for e in p.window_exprs],
+                            [rewrite_expr(e) for e in p.partition_by],
+                            [L.SortOrder(rewrite_expr(o.child), o.ascending) for o in p.order_by],
+                            p.child)
         return None
 
     new_plan = plan.transform_up(fn)

@@ -605,6 +605,171 @@ class Avg(AggregateFunction):
         return pa.float64()
 
 
+class NormalizeNaNAndZero(Expression):
+    """A float with ``-0.0`` as ``0.0`` and every NaN as the one canonical NaN: values that are
+    equal as keys then have equal bits (what a hash of the bits needs)."""
+
+    def __init__(self, child: Expression):
+        self.children = (child,)
+
+    @property
+    def child(self):
+        return self.children[0]
+
+    def with_children(self, children):
+        return NormalizeNaNAndZero(children[0])
+
+    @property
+    def data_type(self):
+        return self.child.data_type
+
+    def sql(self):
+        return f"knownfloatingpointnormalized(normalizenanandzero({self.child.sql()}))"
+
+
+# ---------------------------------------------------------------------------------------------
+# Window functions
+# ---------------------------------------------------------------------------------------------
+class RankingFunction(LeafExpression):
+    """``row_number()`` / ``rank()`` / ``dense_rank()``: only meaningful inside a
+    ``WindowExpression`` whose specification has an ORDER BY."""
+    name = "rank"
+
+    @property
+    def data_type(self):
+        return pa.int32()
+
+    @property
+    def nullable(self):
+        return False
+
+    def sql(self):
+        return f"{self.name}()"
+
+
+class RowNumber(RankingFunction):
+    name = "row_number"
+
+
+class Rank(RankingFunction):
+    name = "rank"
+
+
+class DenseRank(RankingFunction):
+    name = "dense_rank"
+
+
+def _frame_error(what: str):
+    from ..exceptions import HyperspaceException
+    return HyperspaceException(
+        f"explicit window frames ({what}) are not supported: a window takes Spark's default "
+        "frame - the whole partition without ORDER BY, RANGE BETWEEN UNBOUNDED PRECEDING AND "
+        "CURRENT ROW with it")
+
+
+class WindowSpecDefinition(Expression):
+    """``(PARTITION BY p... ORDER BY o [ASC|DESC]...)``.  ``order_by`` takes sort orders (anything
+    with ``child`` and ``ascending``) or (expression, ascending) pairs.  The keys are the node's
+    children (so they resolve and rewrite like any expression); the split between them and the
+    directions are plain fields, which keeps two specifications apart in every plan key."""
+
+    def __init__(self, partition_by=(), order_by=(), frame=None):
+        if frame is not None:
+            raise _frame_error(str(frame))
+        orders = [(o.child, o.ascending) if hasattr(o, "ascending") else (o[0], o[1])
+                  for o in order_by]
+        self.children = tuple(partition_by) + tuple(e for e, _ in orders)
+        self.n_part = len(tuple(partition_by))
+        self.ascending = tuple(bool(a) for _, a in orders)
+
+    @property
+    def partition_by(self) -> list:
+        return list(self.children[:self.n_part])
+
+    @property
+    def order_by(self) -> list:
+        """[(expression, ascending)]"""
+        return list(zip(self.children[self.n_part:], self.ascending))
+
+    def with_children(self, children):
+        children = tuple(children)
+        return WindowSpecDefinition(children[:self.n_part],
+                                    list(zip(children[self.n_part:], self.ascending)))
+
+    @property
+    def data_type(self):
+        raise ValueError("a window specification has no value")
+
+    @property
+    def nullable(self):
+        return False
+
+    def canonical_key(self):
+        return ("WindowSpecDefinition",
+                tuple(e.canonical_key() for e in self.partition_by),
+                tuple((e.canonical_key(), a) for e, a in self.order_by))
+
+    def sql(self):
+        parts = []
+        if self.n_part:
+            parts.append("PARTITION BY " + ", ".join(e.sql() for e in self.partition_by))
+        if self.ascending:
+            parts.append("ORDER BY " + ", ".join(
+                f"{e.sql()} {'ASC NULLS FIRST' if a else 'DESC NULLS LAST'}"
+                for e, a in self.order_by))
+        return "(" + " ".join(parts) + ")"
+
+
+class WindowExpression(Expression):
+    """``function OVER spec``: a ranking function, or ``sum`` / ``count`` / ``min`` / ``max`` /
+    ``avg`` over Spark's default frame.  With an ORDER BY the frame runs from the partition's
+    first row to the current row's last peer (rows that tie on every order key share one value);
+    without one it is the whole partition."""
+
+    def __init__(self, function: Expression, spec: WindowSpecDefinition):
+        from ..exceptions import HyperspaceException
+        if not isinstance(spec, WindowSpecDefinition):
+            raise TypeError(f"OVER needs a window specification, got {spec!r}")
+        if isinstance(function, RankingFunction):
+            if not spec.ascending:
+                raise HyperspaceException(
+                    f"window function {function.name}() requires the window to be ordered: "
+                    f"add an ORDER BY to {spec.sql()}")
+        elif isinstance(function, CountDistinct) or \
+                not isinstance(function, (Sum, Count, Min, Max, Avg)):
+            raise HyperspaceException(
+                f"{function.sql()} is not a window function: OVER takes row_number, rank, "
+                "dense_rank, sum, count, min, max or avg")
+        elif contains_window(function):
+            raise HyperspaceException("a window function cannot be nested in another one")
+        self.children = (function, spec)
+
+    @property
+    def function(self):
+        return self.children[0]
+
+    @property
+    def spec(self) -> WindowSpecDefinition:
+        return self.children[1]
+
+    def with_children(self, children):
+        return WindowExpression(children[0], children[1])
+
+    @property
+    def data_type(self):
+        return self.function.data_type
+
+    @property
+    def nullable(self):
+        return not isinstance(self.function, (RankingFunction, Count))
+
+    def canonical_key(self):
+        return ("WindowExpression", self.function.canonical_key(), self.spec.canonical_key())
+
+    def sql(self):
+        return f"{self.function.sql()} OVER {self.spec.sql()}"
+
+
 # ---------------------------------------------------------------------------------------------
 # helpers
 # ---------------------------------------------------------------------------------------------
@@ -633,4 +798,14 @@ def attr_set(exprs) -> set:
 
 
 def contains_aggregate(e: Expression) -> bool:
-    return any(isinstance(x, AggregateFunction) for x in e.iter_tree())
+    """Whether ``e`` holds an aggregate function of its own: one wrapped in a
+    ``WindowExpression`` (``sum(x) OVER w``) is a per-row value, not an aggregate."""
+    if isinstance(e, WindowExpression):
+        return False
+    if isinstance(e, AggregateFunction):
+        return True
+    return any(contains_aggregate(c) for c in e.children)
+
+
+def contains_window(e: Expression) -> bool:
+    return any(isinstance(x, WindowExpression) for x in e.iter_tree())

@@ -1,6 +1,6 @@
 """Logical plans of the query front-end (Catalyst's node set, reduced to what the index rules and
 executors need): LogicalRelation over a file-based HadoopFsRelation, Filter, Project, Join,
-Aggregate, Union, BucketUnion, RepartitionByExpression, Sort, Limit.
+Aggregate, Union, BucketUnion, RepartitionByExpression, Sort, Window, Limit.
 
 Reference analogs: Spark's LogicalRelation/HadoopFsRelation, Hyperspace's
 ``IndexHadoopFsRelation`` (``index/plans/logical/IndexHadoopFsRelation.scala:29-50``) and
@@ -470,6 +470,78 @@ class Sort(UnaryNode):
 
     def simple_string(self):
         return f"Sort [{', '.join(o.sql() for o in self.order)}], {str(self.global_sort).lower()}"
+
+
+class Window(UnaryNode):
+    """The window functions of one specification: the child's columns plus one column per
+    ``window_exprs`` entry (``Alias(WindowExpression)``), every one over ``partition_by`` /
+    ``order_by`` (a list of ``SortOrder``)."""
+
+    def __init__(self, window_exprs: List[E.Expression], partition_by: List[E.Expression],
+                 order_by: List[SortOrder], child: LogicalPlan):
+        self.window_exprs = list(window_exprs)
+        self.partition_by = list(partition_by)
+        self.order_by = list(order_by)
+        self.children = (child,)
+
+    @property
+    def output(self):
+        return list(self.child.output) + [e.to_attribute() for e in self.window_exprs]
+
+    def expressions(self):
+        return self.window_exprs + self.partition_by + [o.child for o in self.order_by]
+
+    def with_children(self, children):
+        return Window(self.window_exprs, self.partition_by, self.order_by, children[0])
+
+    def simple_string(self):
+        return (f"Window [{', '.join(e.sql() for e in self.window_exprs)}], "
+                f"[{', '.join(e.sql() for e in self.partition_by)}], "
+                f"[{', '.join(o.sql() for o in self.order_by)}]")
+
+
+def project_with_windows(project_list: List[E.Expression], child: LogicalPlan) -> LogicalPlan:
+    """``Project(project_list, child)`` with the window expressions pulled out (Catalyst's
+    ``ExtractWindowExpressions``): one ``Window`` per distinct specification, chained in order
+    of first appearance, and the projection above reading their columns."""
+    windowed, bare = False, None
+    for e in project_list:
+        if type(e) is E.Attribute:
+            continue
+        for x in e.iter_tree():
+            if isinstance(x, E.WindowExpression):
+                windowed = True
+            elif isinstance(x, E.RankingFunction):
+                bare = x
+    if not windowed:
+        if bare is not None:
+            from ..exceptions import HyperspaceException
+            raise HyperspaceException(f"window function {bare.sql()} requires an OVER clause")
+        return Project(project_list, child)
+    by_spec: dict = {}       # spec key -> (spec, [Alias(WindowExpression)])
+    named: dict = {}         # window expression key -> its attribute
+
+    def pull(w: E.WindowExpression, alias: E.Alias = None) -> E.Attribute:
+        k = w.canonical_key()
+        if k in named and alias is None:
+            return named[k]
+        a = alias if alias is not None else E.Alias(w, f"_we{len(named)}")
+        by_spec.setdefault(w.spec.canonical_key(), (w.spec, []))[1].append(a)
+        named.setdefault(k, a.to_attribute())
+        return a.to_attribute()
+
+    out = []
+    for e in project_list:
+        if isinstance(e, E.Alias) and isinstance(e.child, E.WindowExpression):
+            out.append(pull(e.child, e))
+            continue
+        out.append(e.transform_up(
+            lambda x: pull(x) if isinstance(x, E.WindowExpression) else None))
+    plan = child
+    for spec, aliases in by_spec.values():
+        plan = Window(aliases, spec.partition_by,
+                      [SortOrder(e, a) for e, a in spec.order_by], plan)
+    return Project(out, plan)
 
 
 class Limit(UnaryNode):

@@ -66,6 +66,8 @@ def push_down_predicates(plan):
             return L.Join(left, right, c.join_type, jcond)
         if isinstance(c, L.Union):
             return None
+        # a Filter over a Window stays above it: the filter changes which rows a frame
+        # holds, also when it reads partition keys only
         return None
     return plan.transform_down(fn)
 
@@ -173,6 +175,14 @@ def column_pruning(plan, required=None):
     if isinstance(plan, (L.Sort, L.Limit, L.RepartitionByExpression)):
         need = set(required) | {a.expr_id for e in plan.expressions() for a in e.references()}
         return plan.with_children((column_pruning(plan.child, need),))
+    if isinstance(plan, L.Window):
+        # the window columns are made here; everything else the parent or the window's own
+        # functions and keys read comes from the child, narrowed by a Project (so the scan
+        # below reads those columns only and a covering index over them qualifies)
+        own = {e.expr_id for e in plan.window_exprs}
+        need = (set(required) - own) | {a.expr_id for e in plan.expressions()
+                                        for a in e.references()}
+        return plan.with_children((_prune_child(plan.child, need, wrap=True),))
     if isinstance(plan, (L.Union, L.BucketUnion)):
         return plan.with_children(tuple(column_pruning(c) for c in plan.children))
     return plan

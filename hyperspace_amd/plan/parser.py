@@ -1,7 +1,8 @@
 """Tiny SQL expression parser for ``df.filter("c3 == 'x' AND c1 > 5")`` style strings.
 
 Grammar (precedence low->high): OR, AND, NOT, comparison / IN / BETWEEN / IS [NOT] NULL,
-additive, multiplicative, unary minus, primary (literal, column, function call, parenthesised).
+additive, multiplicative, unary minus, primary (literal, column, function call with an optional
+``OVER ([PARTITION BY e, ...] [ORDER BY e [ASC|DESC], ...])``, parenthesised).
 Produces expressions with ``UnresolvedAttribute`` leaves; the DataFrame resolves them.
 """
 from __future__ import annotations
@@ -216,34 +217,88 @@ class _Parser:
             return e
         if kind == "id":
             if self.peek() == ("op", "("):
-                self.take()
-                args = []
-                nxt = self.peek()
-                if nxt == ("kw", "DISTINCT") or (
-                        nxt[0] == "id" and nxt[1].upper() == "DISTINCT" and
-                        self.peek(1) not in (("op", ")"), ("op", ","))):
-                    # f(DISTINCT e, ...): outside SQL text DISTINCT is no reserved word, and a
-                    # column may carry the name
-                    self.take()
-                    args.append(self.or_expr())
-                    while self.accept("op", ","):
-                        args.append(self.or_expr())
-                    self.expect("op", ")")
-                    return make_function(text, args, distinct=True)
-                if self.accept("op", "*"):
-                    args = []
-                elif not self.accept("op", ")"):
-                    args.append(self.or_expr())
-                    while self.accept("op", ","):
-                        args.append(self.or_expr())
-                    self.expect("op", ")")
-                    return make_function(text, args)
-                else:
-                    return make_function(text, args)
-                self.expect("op", ")")
-                return make_function(text, args)
+                return self.over(self.call(text))
             return E.UnresolvedAttribute(text)
         raise SyntaxError(f"unexpected token {text!r}")
+
+    # -- fn(args) [OVER (...)] ------------------------------------------------------------------
+    def word(self, text: str, k: int = 0) -> bool:
+        """Whether token ``k`` ahead is the word ``text``: a keyword of the SQL front end, a
+        plain identifier in an expression string (where OVER, PARTITION, ... are not reserved)."""
+        t = self.peek(k)
+        return t[0] in ("id", "kw") and t[1] is not None and t[1].upper() == text
+
+    def accept_word(self, text: str) -> bool:
+        if self.word(text):
+            self.i += 1
+            return True
+        return False
+
+    def over(self, fn):
+        """``fn OVER ([PARTITION BY e, ...] [ORDER BY e [ASC|DESC], ...])`` after a call."""
+        if not (self.word("OVER") and self.peek(1) == ("op", "(")):
+            return fn
+        self.take()
+        self.take()
+        parts, orders = [], []
+        if self.accept_word("PARTITION"):
+            if not self.accept_word("BY"):
+                raise SyntaxError(f"expected BY after PARTITION, got {self.peek()[1]!r}")
+            parts.append(self.or_expr())
+            while self.accept("op", ","):
+                parts.append(self.or_expr())
+        if self.accept_word("ORDER"):
+            if not self.accept_word("BY"):
+                raise SyntaxError(f"expected BY after ORDER, got {self.peek()[1]!r}")
+            while True:
+                e = self.or_expr()
+                asc = True
+                if self.accept_word("DESC"):
+                    asc = False
+                else:
+                    self.accept_word("ASC")
+                if self.accept_word("NULLS"):
+                    first = self.accept_word("FIRST")
+                    if not first and not self.accept_word("LAST"):
+                        raise SyntaxError("NULLS FIRST | LAST")
+                    if first != asc:
+                        from ..exceptions import HyperspaceException
+                        raise HyperspaceException(
+                            "a window ORDER BY takes the default null ordering only "
+                            "(ASC NULLS FIRST, DESC NULLS LAST)")
+                orders.append((e, asc))
+                if not self.accept("op", ","):
+                    break
+        if self.word("ROWS") or self.word("RANGE"):
+            raise E._frame_error(f"{self.peek()[1].upper()} BETWEEN ...")
+        self.expect("op", ")")
+        return E.WindowExpression(fn, E.WindowSpecDefinition(parts, orders))
+
+    def call(self, text: str):
+        """The function call ``text(...)``, positioned at its opening parenthesis."""
+        self.take()
+        args = []
+        nxt = self.peek()
+        if nxt == ("kw", "DISTINCT") or (
+                nxt[0] == "id" and nxt[1].upper() == "DISTINCT" and
+                self.peek(1) not in (("op", ")"), ("op", ","))):
+            # f(DISTINCT e, ...): outside SQL text DISTINCT is no reserved word, and a
+            # column may carry the name
+            self.take()
+            args.append(self.or_expr())
+            while self.accept("op", ","):
+                args.append(self.or_expr())
+            self.expect("op", ")")
+            return make_function(text, args, distinct=True)
+        if self.accept("op", "*"):
+            self.expect("op", ")")
+            return make_function(text, [])
+        if not self.accept("op", ")"):
+            args.append(self.or_expr())
+            while self.accept("op", ","):
+                args.append(self.or_expr())
+            self.expect("op", ")")
+        return make_function(text, args)
 
 
 def make_function(name: str, args, distinct: bool = False):
@@ -263,6 +318,11 @@ def make_function(name: str, args, distinct: bool = False):
              "mean": E.Avg}
     if n in table:
         return table[n](args[0] if args else None)
+    ranking = {"row_number": E.RowNumber, "rank": E.Rank, "dense_rank": E.DenseRank}
+    if n in ranking:
+        if args:
+            raise SyntaxError(f"{n}() takes no arguments")
+        return ranking[n]()
     raise SyntaxError(f"unknown function {name}")
 
 

@@ -2,7 +2,8 @@
 
 The operator set mirrors what the reference makes Spark run: file scans (plain or
 bucketed index scans), Filter, Project, ShuffleExchange(hashpartitioning), Sort, SortMergeJoin,
-BroadcastHashJoin, HashAggregate, Union and BucketUnion (``BucketUnionExec.scala:52-121``).
+BroadcastHashJoin, HashAggregate, Window, Union and BucketUnion
+(``BucketUnionExec.scala:52-121``).
 Execution is delegated to a backend (``exec.cpu.CpuBackend`` — pyarrow oracle — or
 ``exec.gpu.GpuBackend`` — HIP kernels on MI355X); both honour the same partitioning semantics so
 plans are interchangeable and results comparable row-for-row.
@@ -400,13 +401,17 @@ class BroadcastExchangeExec(UnaryExec):
 
 
 class SortExec(UnaryExec):
-    def __init__(self, order: List[L.SortOrder], global_sort: bool, child: SparkPlan):
+    def __init__(self, order: List[L.SortOrder], global_sort: bool, child: SparkPlan,
+                 nan_largest: bool = False):
         self.order = list(order)
         self.global_sort = global_sort
         self.children = (child,)
+        # a window's sort: NaN orders as the greatest float value (Spark's order, and the device
+        # sort's), so ranks agree between the engines; other sorts keep the host sort's placement
+        self.nan_largest = nan_largest
 
     def with_children(self, children):
-        return SortExec(self.order, self.global_sort, children[0])
+        return SortExec(self.order, self.global_sort, children[0], self.nan_largest)
 
     @property
     def output_ordering(self):
@@ -577,6 +582,41 @@ def _buffer_fields(fn):
     return [(fn.name, fn.data_type)]
 
 
+class WindowExec(UnaryExec):
+    """Window functions of one specification over a child partitioned by ``partition_by`` and
+    sorted by (``partition_by`` ascending, ``order_by``) within each partition."""
+
+    def __init__(self, window_exprs, partition_by, order_by: List[L.SortOrder],
+                 child: SparkPlan):
+        self.window_exprs = list(window_exprs)     # Alias(WindowExpression)
+        self.partition_by = list(partition_by)
+        self.order_by = list(order_by)
+        self.children = (child,)
+
+    @property
+    def node_name(self):
+        return "Window"
+
+    @property
+    def output(self):
+        return list(self.child.output) + [e.to_attribute() for e in self.window_exprs]
+
+    @property
+    def output_ordering(self):
+        return self.child.output_ordering
+
+    def required_ordering(self) -> List[L.SortOrder]:
+        return [L.SortOrder(k, True) for k in self.partition_by] + list(self.order_by)
+
+    def with_children(self, children):
+        return WindowExec(self.window_exprs, self.partition_by, self.order_by, children[0])
+
+    def simple_string(self):
+        return (f"Window [{', '.join(e.sql() for e in self.window_exprs)}], "
+                f"[{', '.join(e.sql() for e in self.partition_by)}], "
+                f"[{', '.join(o.sql() for o in self.order_by)}]")
+
+
 class UnionExec(SparkPlan):
     def __init__(self, children):
         self.children = tuple(children)
@@ -665,6 +705,14 @@ def extract_equi_join_keys(join: L.Join):
     return lk, rk, E.conjoin(rest)
 
 
+def window_clustering(partition_by) -> List[E.Expression]:
+    """The expressions a window's exchange hashes: its partition keys, float keys normalised
+    (one zero, one NaN) - the hash reads a float's bits, and ``0.0`` / ``-0.0`` or two NaNs must
+    reach the same partition to be one window partition (Spark's NormalizeFloatingNumbers)."""
+    return [E.NormalizeNaNAndZero(e) if pa.types.is_floating(e.data_type) else e
+            for e in partition_by]
+
+
 def estimate_size(plan: L.LogicalPlan) -> int:
     if isinstance(plan, L.LogicalRelation):
         return max(1, plan.relation.location.size_in_bytes())
@@ -726,6 +774,19 @@ class Planner:
             if p.global_sort:
                 child = ShuffleExchangeExec(SinglePartition(), child)
             return SortExec(p.order, p.global_sort, child)
+        if isinstance(p, L.Window):
+            child = self.plan(p.child)
+            if p.partition_by:
+                n = HyperspaceConf.shuffle_partitions(self.session.conf)
+                child = ShuffleExchangeExec(
+                    HashPartitioning(window_clustering(p.partition_by), n), child)
+            else:
+                child = ShuffleExchangeExec(SinglePartition(), child)
+            w = WindowExec(p.window_exprs, p.partition_by, p.order_by, child)
+            order = w.required_ordering()
+            if not order:      # fn(...) OVER (): one partition, nothing to sort by
+                return w
+            return w.with_children((SortExec(order, False, child, nan_largest=True),))
         if isinstance(p, L.Limit):
             return CollectLimitExec(p.n, self.plan(p.child))
         if isinstance(p, L.BucketUnion):
@@ -820,8 +881,32 @@ def ensure_requirements(plan: SparkPlan, session) -> SparkPlan:
             right = _ensure_sorted(right, p.right_keys)
             if left is not p.left or right is not p.right:
                 return p.with_children((left, right))
-        if isinstance(p, BucketUnionExec):
-            return None
+        if isinstance(p, WindowExec):
+            # the planner's Sort over Exchange: both go when the input is already partitioned
+            # on the partition keys and sorted by (partition keys, order keys) - a bucketed
+            # index on them; the sort alone stays when only the partitioning matches
+            sort = p.child if isinstance(p.child, SortExec) and not p.child.global_sort \
+                else None
+            exch = sort.child if sort is not None else p.child
+            if not isinstance(exch, ShuffleExchangeExec):
+                return None
+            base = exch.child
+            bp = base.output_partitioning
+            if p.partition_by:
+                ok = isinstance(bp, HashPartitioning) and \
+                    bp.satisfies_clustering(window_clustering(p.partition_by))
+            else:
+                ok = isinstance(bp, SinglePartition)
+            if not ok:
+                return None
+            if sort is None:
+                return p.with_children((base,))
+            have = base.output_ordering
+            if len(have) >= len(sort.order) and all(
+                    h.child.semantic_equals(o.child) and h.ascending == o.ascending
+                    for h, o in zip(have, sort.order)):
+                return p.with_children((base,))
+            return p.with_children((sort.with_children((base,)),))
         return None
     return plan.transform_up(fn)
 

@@ -10,6 +10,7 @@ Supported (the shapes the reference's tests and notebooks run through ``spark.sq
     select  := SELECT [DISTINCT] item, ... FROM from [WHERE e] [GROUP BY e, ...] [HAVING e]
                [ORDER BY e [ASC|DESC], ...] [LIMIT n]
     item    := * | rel.* | e [[AS] alias]
+               (e may hold fn(args) OVER ([PARTITION BY e, ...] [ORDER BY e [ASC|DESC], ...]))
     from    := ref [, ref | [INNER|CROSS|LEFT [OUTER]|RIGHT [OUTER]|FULL [OUTER]|LEFT SEMI|
                LEFT ANTI] JOIN ref [ON e]]*
     ref     := name [[AS] alias] | ( query ) [AS] alias
@@ -164,7 +165,12 @@ class SqlPlanner(_Parser):
         where_parts: List[E.Expression] = []
         plan = self.from_clause(scope, where_parts)
         if self.accept("kw", "WHERE"):
-            where_parts.extend(E.split_conjuncts(self.resolve(self.or_expr(), scope)))
+            cond = self.or_expr()
+            if E.contains_window(cond):
+                raise HyperspaceException(
+                    "window functions are not allowed in WHERE: compute them in a subquery in "
+                    "FROM and filter its result")
+            where_parts.extend(E.split_conjuncts(self.resolve(cond, scope)))
         plan = self.place_conjuncts(plan, scope, where_parts)
         grouping = []
         if self.accept("kw", "GROUP"):
@@ -374,6 +380,10 @@ class SqlPlanner(_Parser):
         agg = bool(grouping) or any(E.contains_aggregate(e) for e in exprs) or \
             (having is not None)
         if agg:
+            if any(E.contains_window(e) for e in exprs):
+                raise HyperspaceException(
+                    "window functions over a grouped query are not supported: aggregate in a "
+                    "subquery in FROM and select the window functions over its result")
             groups = []
             for g in grouping:
                 g2 = self.resolve(g, scope, lambda n: (aliases[n.lower()].child
@@ -413,7 +423,7 @@ class SqlPlanner(_Parser):
                 plan = L.Project([e.to_attribute() if isinstance(e, E.Alias) else e
                                   for e in out], plan)
             return L.distinct(plan) if distinct else plan
-        proj = L.Project(exprs, plan)
+        proj = L.project_with_windows(exprs, plan)
         if distinct:
             proj = L.distinct(proj)
         if not orders:
@@ -431,6 +441,9 @@ class SqlPlanner(_Parser):
             if isinstance(x, E.Attribute) and x.expr_id in sub:
                 return sub[x.expr_id]
             return None
+        if any(E.contains_window(e) for e in exprs):
+            raise HyperspaceException("ORDER BY of a column that is not in the select list, "
+                                      "beside window functions, is not supported")
         below = L.Sort([L.SortOrder(e.transform_up(unalias), a) for e, a in sort], True, plan)
         return L.Project(exprs, below)
 

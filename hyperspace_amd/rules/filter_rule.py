@@ -10,6 +10,7 @@ from __future__ import annotations
 import logging
 
 from ..actions import states
+from ..plan import expressions as E
 from ..plan import logical as L
 from ..telemetry.events import (AppInfo, HyperspaceIndexUsageEvent, NoOpEventLogger,
                                 get_event_logger)
@@ -53,9 +54,21 @@ def find_covering_indexes(session, filt, out_cols, filt_cols) -> list:
     return RU.get_candidate_indexes(session, cands, rel)
 
 
+def _window_keys(p):
+    """The partition column names of a Window directly over a filter node, else None."""
+    if isinstance(p, L.Window) and p.partition_by and \
+            all(isinstance(e, E.Attribute) for e in p.partition_by):
+        return [e.name for e in p.partition_by]
+    return None
+
+
 def FilterIndexRule(session, plan):
     def fn(p):
-        m = extract_filter_node(p)
+        # a Window partitioned on exactly the index's indexed columns reads the index with its
+        # bucket spec: the buckets are the window's partitioning (and their sort order its
+        # ordering), so it needs no shuffle - worth more than the scan parallelism given up
+        wkeys = _window_keys(p)
+        m = extract_filter_node(p.children[0] if wkeys else p)
         if m is None:
             return None
         original, filt, out_cols, filt_cols, _ = m
@@ -64,12 +77,20 @@ def FilterIndexRule(session, plan):
             index = rank_filter(session, filt, cands)
             if index is None:
                 return None
-            transformed = RU.transform_plan_to_use_index(session, index, original, False)
+            if wkeys is not None:
+                cs = session.case_sensitive
+                fold = (lambda n: n) if cs else str.lower
+                if [fold(n) for n in wkeys] != [fold(n) for n in index.indexed_columns]:
+                    return None      # the child is visited next and rewritten as usual
+            transformed = RU.transform_plan_to_use_index(session, index, original,
+                                                         wkeys is not None)
             logger = get_event_logger(session.conf)
             if not isinstance(logger, NoOpEventLogger):  # plan strings only when someone listens
                 logger.log_event(HyperspaceIndexUsageEvent(
                     AppInfo(session.user, session.app_id, session.app_name), [index],
                     filt.tree_string(), transformed.tree_string(), "Filter index rule applied."))
+            if wkeys is not None:
+                return p.with_children((_Done(transformed),))
             return _Done(transformed)
         except Exception as e:  # noqa: BLE001
             log.warning("Non fatal exception in running filter index rule: %s", e)
