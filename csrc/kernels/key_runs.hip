@@ -133,9 +133,83 @@ __global__ __launch_bounds__(256) void hs_run_bitmap_tags_kernel(const int32_t* 
   if (lane < 2 && (g << 6) < nruns) tags[2 * g + lane] = (uint32_t)(b >> (32 * lane));
 }
 
+// Per-run bounds of a 16-bit compact column over the run form (exec/jit_runs.py run_bounds: the
+// pre-filter of phase 1).  mn[r] / mx[r] = smallest / largest code + 32768 (the order-preserving
+// unsigned image of the signed code) over run r's rows.  A wavefront owns RB_GROUPS consecutive
+// 64-row groups and stores the bounds of the runs that *start* in them: one row per lane, a
+// segmented shuffle scan per group, the group's last (open) run carried into the next group -
+// past the wavefront's own groups until that run ends, so a run of any length has one writer and
+// nothing needs an atomic.  The run continuing into the wavefront's first group belongs to an
+// earlier wavefront (skip).
+constexpr int RB_GROUPS = 16;
+
+__global__ __launch_bounds__(256) void hs_run_minmax16_kernel(const uint64_t* __restrict__ gmask,
+                                                              const int32_t* __restrict__ gruns,
+                                                              const int16_t* __restrict__ codes,
+                                                              int64_t n, uint16_t* __restrict__ mn,
+                                                              uint16_t* __restrict__ mx) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ng = (n + 63) >> 6;
+  const int64_t wv = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t g0 = wv * RB_GROUPS;
+  if (g0 >= ng) return;   // wavefront-uniform
+  const int64_t g1 = g0 + RB_GROUPS < ng ? g0 + RB_GROUPS : ng;
+  int cmn = 0xFFFF, cmx = 0;   // bounds of the open run so far (uniform)
+  bool open = false;           // a run that started in this wavefront's groups is open
+  for (int64_t g = g0; g < ng; ++g) {
+    if (g >= g1 && !open) break;
+    const uint64_t m = gmask[g];
+    const int64_t i = (g << 6) + lane;
+    const bool in = i < n;
+    int a = 0xFFFF, b = 0;
+    if (in) { a = b = (int)codes[i] + 32768; }
+    // segment heads: the run starts, and lane 0 (its segment continues the previous group's run
+    // when bit 0 of m is clear)
+    bool f = lane == 0 || ((m >> lane) & 1ull);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int a2 = __shfl_up(a, o, 64), b2 = __shfl_up(b, o, 64);
+      const int f2 = __shfl_up((int)f, o, 64);
+      if (lane >= o && !f) { a = a2 < a ? a2 : a; b = b2 > b ? b2 : b; f = f2 != 0; }
+    }
+    const bool first = (m & ((2ull << lane) - 1ull)) == 0ull;   // no start at or before this lane
+    if (first) { a = cmn < a ? cmn : a; b = cmx > b ? cmx : b; }
+    // the lane's row ends its run: the next row starts one, or is past the table
+    bool end;
+    if (lane < 63) {
+      end = in && (i + 1 >= n || ((m >> (lane + 1)) & 1ull));
+    } else {
+      end = in && (g + 1 >= ng || (gmask[g + 1] & 1ull));
+    }
+    // which runs this wavefront stores: in its own groups all but a continuing run it does not
+    // own; past them only the run it carried in
+    const bool mine = first ? open : g < g1;
+    if (end && mine) {
+      const int64_t r = (int64_t)gruns[g] + __popcll(m & ((2ull << lane) - 2ull));
+      mn[r] = (uint16_t)a;
+      mx[r] = (uint16_t)b;
+    }
+    // lane 63's run stays open when its row does not end it
+    const bool lopen = __shfl((int)(in && !end && mine), 63, 64) != 0;
+    cmn = __shfl(a, 63, 64);
+    cmx = __shfl(b, 63, 64);
+    open = lopen;
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+// mn / mx: one uint16 per run (the caller pads them); codes: n int16 rows of the run form's table
+int hs_run_minmax16(const uint64_t* gmask, const int32_t* gruns, const int16_t* codes, int64_t n,
+                    uint16_t* mn, uint16_t* mx, void* stream) {
+  const int64_t nw = (((n + 63) >> 6) + RB_GROUPS - 1) / RB_GROUPS;
+  if (nw > 0)
+    hipLaunchKernelGGL(hs_run_minmax16_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, gmask, gruns, codes, n, mn, mx);
+  return (int)hipGetLastError();
+}
 
 // tags: at least 2 * ceil(nruns / 64) words
 int hs_run_bitmap_tags(const int32_t* runkeys, int64_t nruns, int64_t code_off,

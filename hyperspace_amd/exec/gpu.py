@@ -74,6 +74,7 @@ def release_process_device_memory() -> None:
     jit_join._RUNS_HASH_LOWERED.clear()
     jit_runs._PACKS.clear()
     jit_runs._P12.clear()
+    jit_runs._RBOUNDS.clear()
     jit_join.LAST_MJ_LAUNCHER[0] = None
     # a plain gc.collect() skips what utils/hostgc.py froze: the released sessions' cycles
     # (and the device tensors they hold) are only found after an unfreeze

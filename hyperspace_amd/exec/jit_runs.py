@@ -23,7 +23,16 @@ streams:
 
 Both phases are plain streams (phase 2 at ~5.8 TB/s of its computed bytes; the three kernels
 of a headline step together move ~4.0 GB in 0.70 ms, 5.7 TB/s); the single-kernel form
-(jit.gen_merge_join_agg) keeps a long chain of dependent round trips per tile.  The two-phase
+(jit.gen_merge_join_agg) keeps a long chain of dependent round trips per tile.
+
+The pruned pair (``prune_plan``, RS_PRUNE; the headline Q3's form) reads fewer bytes: phase 1
+also loads one per-run bound of the left predicate column (2 B per run: 12 B per run, 1.8 GB)
+and clears the tags of runs no row of which can pass, and phase 2 (``hs_jit_run_bits_cand``)
+drops its row stream - the 0.9 GB 12-bit ``l_shipdate`` copy - and gathers the tail words of the
+tagged runs' rows only (1.35 instead of 1.27 128-byte lines per 100 left rows): ~1.0 GB
+instead of ~1.9.  The step moves ~3.45 GB in 0.68 ms (5.1 TB/s): phase 1 369 us (4.9 TB/s),
+phase 2 256 us - a gather, not a stream, so below the streaming rate
+(``profiles/run_prune.txt``).  The two-phase
 form applies when no aggregate input comes from the right side, every right predicate reads
 only right columns, and a right-side group key (if any) has at most 255 groups."""
 from __future__ import annotations
@@ -45,6 +54,7 @@ RT2_WIDE, RT2_WIDE_GRID = _CFG.rt2_wide, _CFG.rt2_wide_grid
 RS_BITS, RS_BITS_GRID, RS_PACK = _CFG.rs_bits, _CFG.rs_bits_grid, _CFG.rs_pack
 RS_PIPE, RS_WALK, RS_LDS, RS_LUT = _CFG.rs_pipe, _CFG.rs_walk, _CFG.rs_lds, _CFG.rs_lut
 RS_PK16, RS_WAVES, RS_PACK12 = _CFG.rs_pk16, _CFG.rs_waves, _CFG.rs_pack12
+RS_PRUNE = _CFG.rs_prune
 
 
 def tag_width(p: NL.JoinParams) -> int:
@@ -99,13 +109,54 @@ def tags2_wide(p: NL.JoinParams, compacts, ix32: bool, mode: str = "") -> int:
     return 4
 
 
-def tags2_shape(p: NL.JoinParams, compacts, W: int, ix32: bool = False, mode: str = "") -> tuple:
+def tags2_shape(p: NL.JoinParams, compacts, W: int, ix32: bool = False, mode: str = "",
+                prune: tuple = ()) -> tuple:
     cols = tuple(sorted((s, c) for s, c in J._col_specs(p, compacts).items()
                         if s >= SPLIT or s == p.lkey))
     preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
                    p.preds[k].group) for k in range(p.nlp, p.npreds))
     return ("run_tags2", cols, preds, p.nlp, p.lkey, p.rkey, _tags_grouped(p) and p.group_col,
-            W, RT2_UNROLL, J.BLOCK, ix32, mode, tags2_wide(p, compacts, ix32, mode))
+            W, RT2_UNROLL, J.BLOCK, ix32, mode, tuple(prune),
+            tags2_wide(p, compacts, ix32, mode))
+
+
+def prune_plan(p: NL.JoinParams, compacts, W: int, hk=None, record: bool = False) -> tuple:
+    """The left conjuncts phase 1 pre-filters by per-run bounds (RS_PRUNE), as ((predicate
+    index, column slot, uses the run's maximum), ...) - or () when the pruned pair of kernels
+    does not apply and the join keeps the streaming phase 2.
+
+    It applies to the plain-aggregate, 1-bit-tag, verifying form (``hk`` None, no recorded
+    match, no left group key) when every left predicate is a conjunct of its own comparing a
+    non-nullable 16-bit compact column with a literal by <, <=, > or >= in code space (the
+    CL<k> / CH<k> bounds of ``fill_preds_aggs``; an IS NOT NULL conjunct on a non-nullable
+    column holds for every row and is passed over), and those columns' codes fit the row-packed
+    tail word beside the aggregate inputs (``pack_layout`` with ``extra``).  A run can hold a
+    passing row only if its largest code reaches CL (>, >=) or its smallest stays within CH
+    (<, <=): conservative for any literal, and phase 2 still tests every candidate row exactly."""
+    if not (RS_PRUNE and RS_BITS) or W != 1 or hk is not None or record or _scan_grouped(p):
+        return ()
+    out, groups = [], set()
+    for k, pr in _lpreds(p):
+        if pr.kind == NL.PK_TRUE:
+            continue
+        if pr.group in groups or p.cols[pr.col].valid:
+            return ()
+        groups.add(pr.group)
+        if pr.kind == NL.PK_NOT_NULL:       # holds for every row of a non-nullable column
+            continue
+        c = (compacts or {}).get(pr.col)
+        if c is None or \
+                type(c).__name__ != "Compact" or c.width != 2 or getattr(c, "runs", None):
+            return ()
+        if pr.op not in (NL.OP_LT, NL.OP_LE, NL.OP_GT, NL.OP_GE):
+            return ()
+        if not ((pr.kind == NL.PK_INT_LIT and c.scale is None) or
+                (pr.kind == NL.PK_FLT_LIT and c.scale is not None)):
+            return ()
+        out.append((k, pr.col, pr.op in (NL.OP_GT, NL.OP_GE)))
+    if not out or pack_layout(p, compacts, tuple(dict.fromkeys(sl for _, sl, _ in out))) is None:
+        return ()
+    return tuple(out)
 
 
 def _stage_slots(p: NL.JoinParams) -> list:
@@ -122,7 +173,7 @@ def _tags_grouped(p: NL.JoinParams) -> bool:
 
 
 def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
-                  mode: str = "") -> J.Kernel:
+                  mode: str = "", prune: tuple = ()) -> J.Kernel:
     """Phase 1, direct form: no tiles and no LDS.  Each wavefront owns a contiguous chunk of
     64-run groups of the left run list (so it owns whole 2W-word stretches of the tag bitmap
     and stores them without atomics).  Lane l of a group guesses the right row of its run: the
@@ -156,7 +207,13 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
     runs), so its loads are issued before the current stage is resolved - two register sets,
     the loop unrolled by two so neither is copied; the resolved base (last match + 1) replaces
     the assumption for the stage after that.  Every other block (a range edge, the table tail,
-    a guess outside the bucket) takes the 64-run code below, one group at a time."""
+    a guess outside the bucket) takes the 64-run code below, one group at a time.
+
+    ``prune`` (``prune_plan``; mode ""): per listed left conjunct the run's bound - ``RMX<slot>``
+    or ``RMN<slot>``, one uint16 per run (code + 32768, ``run_bounds``) - is loaded with the run
+    key (the four-run form: one 8-byte load per lane) and the tag is cleared when the bound
+    fails the conjunct's code range [CL<k>, CH<k>]."""
+    assert not prune or mode == ""
     IX = "int" if ix32 else "i64"  # noqa: N806 — run / right-row index type
     wide = tags2_wide(p, compacts, ix32, mode)
     args = J.Args()
@@ -178,6 +235,13 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
     if mode == "rec":
         assert ix32
         args.add("p", "MOUT", "int*")
+    # the pre-filter's bound arrays and its tests on the loaded bounds (bm<i>_<u>: conjunct i's
+    # bound of run u; hs_c20 keeps the sum in int32)
+    bounds, btests = [], []
+    for i, (k, sl, mx) in enumerate(prune):
+        bounds.append(args.add("p", f"RMX{sl}" if mx else f"RMN{sl}", "const unsigned short*"))
+        lit = args.add("q", f"CL{k}" if mx else f"CH{k}", "long long")
+        btests.append(f"bm{i}_@U@ {'>=' if mx else '<='} hs_c20({lit}) + 32768")
     lo16 = mode in ("lo16", "lo16prep")
     if lo16:
         assert ix32
@@ -306,6 +370,8 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
             b.extend([f"{ind}const unsigned key{u} = (unsigned)a.RK{lk}[act{u} ? r{u} : 0] + "
                       f"(unsigned)a.KOF;",
                       f"{ind}const unsigned k{u} = IMGF(j{u});"])
+        for i, bp in enumerate(bounds):
+            b.append(f"{ind}const int bm{i}_{u} = (int){bp}[act{u} ? r{u} : 0];")
         gu = J._Gen(args, cols, SPLIT, (f"j{u}", f"j{u}"), frozenset(), True)
         for sl in stage_slots:
             J._uload(gu, sl, f"g{u}", b, ind)
@@ -355,6 +421,10 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
             J._uload(gm, sl, f"h{u}", b, ind + "  ")
         b.extend([f"{ind}  tg{u} = {tag_expr(gm, f'h{u}', f'hit{u}')};",
                   f"{ind}}}"])
+        if btests:
+            # a run whose bound fails a left conjunct holds no passing row
+            ok = " && ".join(f"({t.replace('@U@', str(u))})" for t in btests)
+            b.append(f"{ind}tg{u} = ({ok}) ? tg{u} : 0u;")
         if not stores:
             return
         # the group's 2W tag words: whole words, plain stores
@@ -387,7 +457,7 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
     if wide == 4:
         del b[:]
         return _gen_tags2_wide(p, args, cols, b, group, resolve,
-                               image(g.decode(rk, "w_"), False), img, imgf, W, mode)
+                               image(g.decode(rk, "w_"), False), img, imgf, W, mode, bounds)
     iteration(True, ind)
     b.append("    } else {   // a range starts inside this iteration's groups")
     iteration(False, ind)
@@ -399,11 +469,13 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
 
 
 def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, resolve,
-                    imgv: str, img: str, imgf: str, W: int, mode: str) -> J.Kernel:
+                    imgv: str, img: str, imgf: str, W: int, mode: str,
+                    bounds=()) -> J.Kernel:
     """The four-runs-per-lane body of ``gen_run_tags2`` (its docstring; 32-bit indices).
     ``group`` / ``resolve`` are that generator's 64-run emitters (appending to ``b``): the slow
     blocks run them one group at a time, and a fast block's runs resolve through the same miss
-    path, one instance per run."""
+    path, one instance per run.  ``bounds``: the pre-filter's per-run bound arrays (uint16), a
+    lane's four loaded with one 8-byte load beside its run keys."""
     lk, rk = p.lkey, p.rkey
     # 256-run blocks per pipeline stage (RT2_UNROLL counts blocks here): at most two - 84 VGPRs
     # at W = 1, six waves per SIMD; a third block's register sets would spill
@@ -416,7 +488,9 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
     g = J._Gen(args, cols, SPLIT, ("row_", "row_"), frozenset(), True)
     rkt = g.raw_type(rk)
     # 4 consecutive elements at an element-aligned address (the guess is arbitrary): one load
-    tdefs = ["typedef int hs_i4 __attribute__((ext_vector_type(4)));",
+    tdefs = ["typedef int hs_i4 __attribute__((ext_vector_type(4)));"] + \
+        (["typedef unsigned short hs_us4 __attribute__((ext_vector_type(4)));"] if bounds
+         else []) + [
              f"typedef {rkt} hs_rk4 __attribute__((ext_vector_type(4), "
              f"aligned({J._SIZEOF[rkt]})));"]
     for sl in stage_slots:
@@ -450,6 +524,9 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
                       f"4 * lane));",
                       f"{ind}R{s}{u} = *(const hs_rk4*)({g.ptr(rk)} + ({base} + {256 * u} + "
                       f"4 * lane));"])
+            for i, bp in enumerate(bounds):
+                b.append(f"{ind}M{i}{s}{u} = *(const hs_us4*)({bp} + ({run0} + {256 * u} + "
+                         f"4 * lane));")
             for sl in stage_slots:
                 b.append(f"{ind}C{sl}{s}{u} = *(const hs_c{sl}x4*)({g.ptr(sl)} + "
                          f"({base} + {256 * u} + 4 * lane));")
@@ -467,6 +544,8 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
                           f"{i2}const int a0_{x} = s0, a1_{x} = s1; const bool act{x} = true;",
                           f"{i2}const unsigned key{x} = L{s}{u}[{k}] + (unsigned)a.KOF;",
                           f"{i2}const unsigned k{x} = IMGV(R{s}{u}[{k}]);"])
+                for i in range(len(bounds)):
+                    b.append(f"{i2}const int bm{i}_{x} = (int)M{i}{s}{u}[{k}];")
                 for sl in stage_slots:
                     J._uload_raw(g, sl, f"g{x}", f"C{sl}{s}{u}[{k}]", "1", b, i2)
                 resolve(x, i2, False, False)
@@ -519,6 +598,7 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
     for s in sets:
         b.append(f"  int pb{s} = 0; " + " ".join(
             f"hs_v4u L{s}{u} = {{}}; hs_rk4 R{s}{u} = {{}};" +
+            "".join(f" hs_us4 M{i}{s}{u} = {{}};" for i in range(len(bounds))) +
             "".join(f" hs_c{sl}x4 C{sl}{s}{u} = {{}};" for sl in stage_slots)
             for u in range(U)))
     b.extend(["  int nb = bbeg;",
@@ -889,12 +969,14 @@ def _tail_slots(p: NL.JoinParams) -> list:
     return list(dict.fromkeys(J._agg_slots(aggs) + ([p.group_col] if grouped else [])))
 
 
-def pack_layout(p: NL.JoinParams, compacts) -> Optional[tuple]:
+def pack_layout(p: NL.JoinParams, compacts, extra: tuple = ()) -> Optional[tuple]:
     """((slot, bit offset, code bytes), ...) of the row-packed aggregate inputs of the bits
-    scan: two or more compact-coded tail columns without validity whose codes fit 64 bits."""
+    scan: two or more compact-coded tail columns without validity whose codes fit 64 bits.
+    ``extra``: the predicate columns the candidate form of phase 2 tests on the word
+    (``prune_plan``), as further fields after the aggregate inputs (their full codes)."""
     if not RS_PACK:
         return None
-    slots = _tail_slots(p)
+    slots = list(dict.fromkeys(_tail_slots(p) + list(extra)))
     if len(slots) < 2:
         return None
     out, off = [], 0
@@ -937,6 +1019,31 @@ def packed_tail(layout, compacts):
 # bytes for the one column phase 2 reads for every row.  Derived once per resident table (like
 # the compact codes and the row-packed aggregate inputs), kept while its codes are.
 _P12: dict = {}
+
+
+# per-run bounds of a left predicate column over the join key's run form (``prune_plan``):
+# (id of the codes, id of the run masks) -> (those tensors, min, max).  Derived once per resident
+# table and column, like the packed copies above; they depend on no literal.
+_RBOUNDS: dict = {}
+
+
+def run_bounds(runs, c) -> tuple:
+    """(mn, mx) of 16-bit compact column ``c`` per run of ``runs`` (a RunCompact of the same
+    table): uint16 bits of code + 32768, padded to whole 256-run blocks with the empty interval
+    (``ops.kernels.run_minmax16``)."""
+    from ..ops import kernels as K
+    from .device_cache import track_derived
+    key = (id(c.codes), id(runs.gmask))
+    hit = _RBOUNDS.get(key)
+    if hit is not None and hit[0] is c.codes and hit[1] is runs.gmask:
+        return hit[2], hit[3]
+    mn, mx = K.run_minmax16(runs.gmask, runs.gruns, runs.nruns, c.codes)
+    track_derived(mn)
+    track_derived(mx)
+    if len(_RBOUNDS) >= 8:
+        _RBOUNDS.pop(next(iter(_RBOUNDS)))
+    _RBOUNDS[key] = (c.codes, runs.gmask, mn, mx)
+    return mn, mx
 
 
 def _p12_offset(c) -> int:
@@ -1011,14 +1118,18 @@ def fill_pack12(vs: dict, p: NL.JoinParams, compacts) -> list:
     return keep
 
 
-def sparse_shape(p: NL.JoinParams, compacts, hk=None, tk=None) -> tuple:
+def sparse_shape(p: NL.JoinParams, compacts, hk=None, tk=None, cand: tuple = ()) -> tuple:
+    if cand:
+        return ("run_bits_cand", RS_WALK, RS_LUT, RS_WAVES) + scan_shape(p, compacts, 1, 64)[1:] + \
+            (pack_layout(p, compacts, cand),)
     return ("run_bits_scan", RS_PIPE, RS_WALK, RS_LDS, RS_LUT, RS_PK16, RS_WAVES,
             _p12_slots(p, compacts)) + scan_shape(p, compacts, 1, 64)[1:] + \
         (pack_layout(p, compacts),) + ((hk.shape(),) if hk is not None else ()) + \
         ((tk.shape(),) if tk is not None else ())
 
 
-def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kernel:
+def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
+                        cand: tuple = ()) -> J.Kernel:
     """Phase 2 for 1-bit tags, bit-parallel: the dense per-row scan spends ~20 VALU
     instructions per row (decode, predicate, run index by popcount, tag extract, compaction
     ballot + mbcnt), which bounds it below HBM speed.  Here a wavefront takes 4096-row tiles of
@@ -1046,7 +1157,22 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
     the next (``jit_hash._topk_accumulate``): a key is final when the walk leaves it and competes
     for the wavefront's top-K registers instead of probing the table; only keys that may
     continue into the neighbouring wavefronts' tiles (at most two per wavefront) go to the
-    table (kernel ``hs_jit_run_bits_topk``; every wavefront writes its list at the end)."""
+    table (kernel ``hs_jit_run_bits_topk``; every wavefront writes its list at the end).
+
+    Candidate form (``cand``: the predicate slots of ``prune_plan``; kernel
+    ``hs_jit_run_bits_cand``): phase 1 tagged only runs that may hold a passing row, so step 2's
+    row stream goes.  The rows of (tag mask & range mask) are the tile's *candidates*; they go
+    to a small per-wavefront LDS list ``clst_``, 64 * RS_WALK at a time, the wavefront loads
+    each candidate's row-packed tail word (which holds the predicate columns' codes as extra
+    fields), tests the left predicates on those fields and appends the passing entries stably
+    (ballot + prefix count) to ``lst_``, which the unchanged walk of step 3 consumes.  The walk
+    runs once per tile, after its last candidate (so a tile's passing-row sequence, and with it
+    every lane's sum order, is that of the streaming form while the tile has at most CAP
+    passing rows), or earlier whenever ``lst_`` holds more than CAP entries.  The walk reloads
+    the tail word of a passing row (an L2 hit a few hundred cycles after the filter's load)
+    rather than keeping 8 bytes per entry in LDS: 12.6 KB of LDS per workgroup instead of ~53
+    (68 VGPRs, no scratch, 7 waves per SIMD)."""
+    assert not cand or (hk is None and tk is None)
     args = J.Args()
     for n, ct in (("rstart", "const long long*"), ("rlen", "const long long*"),
                   ("tile_prefix", "const long long*")):
@@ -1104,7 +1230,10 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
               "o_ |= (((unsigned)e_ >> (4u + k_)) & 1u) << j_; }",
               "    dlut_[e_] = (unsigned char)o_; }",
               "  __syncthreads();"]
-    b += [f"  __shared__ unsigned short lst_[{WV}][{CAP}];",
+    CC = 64 * EW  # noqa: N806 — candidate form: candidates per filter pass
+    if cand:
+        b.append(f"  __shared__ unsigned short clst_[{WV}][{CC}];")
+    b += [f"  __shared__ unsigned short lst_[{WV}][{CAP + CC if cand else CAP}];",
           "  const int ln = (int)(threadIdx.x & 63);",
           "  const int wq = (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
           "  const i64 ntiles = a.tile_prefix[a.R];",
@@ -1135,7 +1264,8 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
     slab = 0    # RS_LDS: 16-byte LDS slots per wavefront
     issue.append("    { const i64 w_ = (i64)grC >> 5; tw0@S@_ = a.tags[w_]; "
                  "tw1@S@_ = a.tags[w_ + 1]; tw2@S@_ = a.tags[w_ + 2]; }")
-    p12 = _p12_slots(p, compacts)
+    p12 = () if cand else _p12_slots(p, compacts)
+    pipe = 0 if cand else RS_PIPE
     for sl in p12:
         # 24 dwords (96 bytes) per lane: its 64-row group's 12-bit packed codes
         pp = args.add("p", f"P12_{sl}", "const unsigned*")
@@ -1143,7 +1273,7 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
         b.append(f"  unsigned x{sl}qA[24], x{sl}qB[24];")
         issue.append(f"    bload<24>(hs_rsrc((const char*){pp} + (tbC >> 6) * 96, "
                      f"@LIVE@((a.nrows + 63 - tbC) >> 6) * 96), (unsigned)(ln * 96), x{sl}q@S@);")
-    for name, ct, ptr in ([] if p12 else J._vec_loads(g1, pslots)):
+    for name, ct, ptr in ([] if p12 or cand else J._vec_loads(g1, pslots)):
         es = J._SIZEOF[ct]
         nw = NI * es // 4
         per = 4 // es
@@ -1166,7 +1296,7 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
         return [x.replace("@S@", sfx).replace("@LIVE@", "") for x in lines]
 
     b.append("  if (t0 < t1) {")
-    if RS_PIPE:
+    if pipe:
         b += geom("t0", "C")
         b += buf(issue, "A")
         b += ["    if (t0 + 1 < t1) {"]
@@ -1176,7 +1306,7 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
         b += geom("t0", "N")
     b += ["  }"]
     body: List[str] = []   # one tile (@T@), its buffer @S@, the next tile's buffer @O@
-    if not RS_PIPE:
+    if not pipe:
         # this tile's loads, then the next tile's run-form words: two round trips per tile (the
         # column stream, then the walk's aggregate inputs), fewer registers
         body += ["    rsC = rsN; reC = reN; tbC = tbN; gmC = gmN; grC = grN;"]
@@ -1236,88 +1366,90 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
             f"  __shared__ hs_v4u xt_[{WV}][{nslot}];",
             f"  unsigned short (*lst_)[{nslot * 8}] = (unsigned short (*)[{nslot * 8}])&xt_[0][0];"]
         body += xpose
-    # predicate mask: 64 compares, shift-or into two 32-bit halves (a C loop: each row's
-    # value is decoded where it is compared, not all 64 held decoded at once)
-    body.append("    unsigned plo_ = 0u, phi_ = 0u;")
-    cond = J._rename(g1.cnf(lpreds), pslots, "k")
-    # narrow compact-code ranges: fail bits from a sign word (no compares, no constants held in
-    # registers for the select), else the generic condition's pass bits
-    sign = g1.cnf_sign(lpreds)
-    if sign is not None:
-        sign = J._rename(sign, pslots, "k")
-    # two rows per 32-bit word (16-bit signed codes): packed saturating range tests, fail bits
-    # gathered in even/odd order per 32-row half, then unzipped (2.5 VALU per row instead of 5)
-    sign2 = g1.cnf_sign2(lpreds, "x{}w@S@[w_]") if RS_PK16 and sign is not None and \
-        all(J._SIZEOF.get(g1.raw_type(sl)) == 2 for sl in pslots) else None
-    if p12:
-        # 12-bit chunks: decode 8 rows per 3 dwords, pair them into 16-bit halves, packed tests
-        sign12 = g1.cnf_sign2(lpreds, "pw{}_", offset="a.P12O_{}")
-        assert sign12 is not None
-        for i in range(8):
-            body.append("    {")
-            for sl in p12:
-                body += [f"      const unsigned a{sl}_ = x{sl}q@S@[{3 * i}], "
-                         f"b{sl}_ = x{sl}q@S@[{3 * i + 1}], c{sl}_ = x{sl}q@S@[{3 * i + 2}];",
-                         f"      const unsigned v{sl}_0 = a{sl}_ & 0xFFFu, "
-                         f"v{sl}_1 = (a{sl}_ >> 12) & 0xFFFu, "
-                         f"v{sl}_2 = ((a{sl}_ >> 24) | (b{sl}_ << 8)) & 0xFFFu, "
-                         f"v{sl}_3 = (b{sl}_ >> 4) & 0xFFFu;",
-                         f"      const unsigned v{sl}_4 = (b{sl}_ >> 16) & 0xFFFu, "
-                         f"v{sl}_5 = ((b{sl}_ >> 28) | (c{sl}_ << 4)) & 0xFFFu, "
-                         f"v{sl}_6 = (c{sl}_ >> 8) & 0xFFFu, v{sl}_7 = c{sl}_ >> 20;"]
-            for q in range(4):
-                w = 4 * i + q
-                half, wl = ("plo_", w) if w < 16 else ("phi_", w - 16)
-                body.append("      {")
-                for sl in p12:
-                    body.append(f"        const unsigned pw{sl}_ = v{sl}_{2 * q} | "
-                                f"(v{sl}_{2 * q + 1} << 16);")
-                body += [f"        const unsigned s2_ = {sign12};",
-                         f"        {half} |= (s2_ >> {15 - wl}) & {(1 << wl) | (1 << (wl + 16))}u;",
-                         "      }"]
-            body.append("    }")
-        body += ["    plo_ = hs_unzip16(plo_);", "    phi_ = hs_unzip16(phi_);"]
-    elif sign2 is not None:
-        for half, off in (("plo_", 0), ("phi_", 16)):
-            body += ["    #pragma unroll",
-                     "    for (int w_ = 0; w_ < 16; ++w_) {",
-                     f"      const unsigned s2_ = {sign2.replace('[w_]', f'[w_ + {off}]')};",
-                     f"      {half} |= (s2_ >> (15 - w_)) & ((1u << w_) | (1u << (w_ + 16)));",
-                     "    }",
-                     f"    {half} = hs_unzip16({half});"]
-    for half, off in ((("plo_", 0), ("phi_", 32)) if sign2 is None and not p12 else ()):
-        body.append("    #pragma unroll")
-        body.append("    for (int k_ = 0; k_ < 32; ++k_) {")
-
-        def raw_of(name: str) -> str:
-            et, word, bits, per = elem[name]
-            i = f"{off} + k_"
-            w = word.format(i=i)
-            return f"(({et})({w} >> ({bits} * (({i}) % {per}))))" if per > 1 else f"(({et}){w})"
-        for sl in pslots:
-            ct = J._CTYPE[cols[sl][0]]
-            enc = cols[sl][2]
-            raw = raw_of(f"x{sl}")
-            body.append(f"      const auto xr{sl}_k = {raw};")
-            raw = f"xr{sl}_k"
-            if enc:
-                body.append(f"      const int r{sl}_k = (int){raw};")
-            if enc and enc[1]:
-                bq = args.add("q", f"B{sl}", "long long")
-                body.append(f"      const i64 q{sl}_k = {bq} + (i64){raw};")
-            body.append(f"      const {ct} x{sl}_k = {g1.decode(sl, raw)};")
-            if cols[sl][1]:
-                body.append(f"      const bool n{sl}_k = {raw_of(f'n{sl}')} != 0;")
+    # (the candidate form tests the predicates per candidate row, on its tail word: below)
+    if not cand:
+        # predicate mask: 64 compares, shift-or into two 32-bit halves (a C loop: each row's
+        # value is decoded where it is compared, not all 64 held decoded at once)
+        body.append("    unsigned plo_ = 0u, phi_ = 0u;")
+        cond = J._rename(g1.cnf(lpreds), pslots, "k")
+        # narrow compact-code ranges: fail bits from a sign word (no compares, no constants held in
+        # registers for the select), else the generic condition's pass bits
+        sign = g1.cnf_sign(lpreds)
         if sign is not None:
-            body.append(f"      {half} |= ((unsigned)({sign}) >> 31) << k_;")
+            sign = J._rename(sign, pslots, "k")
+        # two rows per 32-bit word (16-bit signed codes): packed saturating range tests, fail bits
+        # gathered in even/odd order per 32-row half, then unzipped (2.5 VALU per row instead of 5)
+        sign2 = g1.cnf_sign2(lpreds, "x{}w@S@[w_]") if RS_PK16 and sign is not None and \
+            all(J._SIZEOF.get(g1.raw_type(sl)) == 2 for sl in pslots) else None
+        if p12:
+            # 12-bit chunks: decode 8 rows per 3 dwords, pair them into 16-bit halves, packed tests
+            sign12 = g1.cnf_sign2(lpreds, "pw{}_", offset="a.P12O_{}")
+            assert sign12 is not None
+            for i in range(8):
+                body.append("    {")
+                for sl in p12:
+                    body += [f"      const unsigned a{sl}_ = x{sl}q@S@[{3 * i}], "
+                             f"b{sl}_ = x{sl}q@S@[{3 * i + 1}], c{sl}_ = x{sl}q@S@[{3 * i + 2}];",
+                             f"      const unsigned v{sl}_0 = a{sl}_ & 0xFFFu, "
+                             f"v{sl}_1 = (a{sl}_ >> 12) & 0xFFFu, "
+                             f"v{sl}_2 = ((a{sl}_ >> 24) | (b{sl}_ << 8)) & 0xFFFu, "
+                             f"v{sl}_3 = (b{sl}_ >> 4) & 0xFFFu;",
+                             f"      const unsigned v{sl}_4 = (b{sl}_ >> 16) & 0xFFFu, "
+                             f"v{sl}_5 = ((b{sl}_ >> 28) | (c{sl}_ << 4)) & 0xFFFu, "
+                             f"v{sl}_6 = (c{sl}_ >> 8) & 0xFFFu, v{sl}_7 = c{sl}_ >> 20;"]
+                for q in range(4):
+                    w = 4 * i + q
+                    half, wl = ("plo_", w) if w < 16 else ("phi_", w - 16)
+                    body.append("      {")
+                    for sl in p12:
+                        body.append(f"        const unsigned pw{sl}_ = v{sl}_{2 * q} | "
+                                    f"(v{sl}_{2 * q + 1} << 16);")
+                    body += [f"        const unsigned s2_ = {sign12};",
+                             f"        {half} |= (s2_ >> {15 - wl}) & {(1 << wl) | (1 << (wl + 16))}u;",
+                             "      }"]
+                body.append("    }")
+            body += ["    plo_ = hs_unzip16(plo_);", "    phi_ = hs_unzip16(phi_);"]
+        elif sign2 is not None:
+            for half, off in (("plo_", 0), ("phi_", 16)):
+                body += ["    #pragma unroll",
+                         "    for (int w_ = 0; w_ < 16; ++w_) {",
+                         f"      const unsigned s2_ = {sign2.replace('[w_]', f'[w_ + {off}]')};",
+                         f"      {half} |= (s2_ >> (15 - w_)) & ((1u << w_) | (1u << (w_ + 16)));",
+                         "    }",
+                         f"    {half} = hs_unzip16({half});"]
+        for half, off in ((("plo_", 0), ("phi_", 32)) if sign2 is None and not p12 else ()):
+            body.append("    #pragma unroll")
+            body.append("    for (int k_ = 0; k_ < 32; ++k_) {")
+
+            def raw_of(name: str) -> str:
+                et, word, bits, per = elem[name]
+                i = f"{off} + k_"
+                w = word.format(i=i)
+                return f"(({et})({w} >> ({bits} * (({i}) % {per}))))" if per > 1 else f"(({et}){w})"
+            for sl in pslots:
+                ct = J._CTYPE[cols[sl][0]]
+                enc = cols[sl][2]
+                raw = raw_of(f"x{sl}")
+                body.append(f"      const auto xr{sl}_k = {raw};")
+                raw = f"xr{sl}_k"
+                if enc:
+                    body.append(f"      const int r{sl}_k = (int){raw};")
+                if enc and enc[1]:
+                    bq = args.add("q", f"B{sl}", "long long")
+                    body.append(f"      const i64 q{sl}_k = {bq} + (i64){raw};")
+                body.append(f"      const {ct} x{sl}_k = {g1.decode(sl, raw)};")
+                if cols[sl][1]:
+                    body.append(f"      const bool n{sl}_k = {raw_of(f'n{sl}')} != 0;")
+            if sign is not None:
+                body.append(f"      {half} |= ((unsigned)({sign}) >> 31) << k_;")
+            else:
+                body.append(f"      {half} |= ({cond} ? 1u : 0u) << k_;")
+            body.append("    }")
+        if sign is not None:
+            body += ["    d_ &= ~(((u64)phi_ << 32) | (u64)plo_);"]
         else:
-            body.append(f"      {half} |= ({cond} ? 1u : 0u) << k_;")
-        body.append("    }")
-    if sign is not None:
-        body += ["    d_ &= ~(((u64)phi_ << 32) | (u64)plo_);"]
-    else:
-        body += ["    d_ &= ((u64)phi_ << 32) | (u64)plo_;"]
-    if RS_PIPE:
+            body += ["    d_ &= ((u64)phi_ << 32) | (u64)plo_;"]
+    if pipe:
         # this tile's column words are consumed: the next tile's loads go out now
         # (the scheduler must not hoist the next tile's loads above this tile's masks: both
         # buffers would be live at once)
@@ -1338,7 +1470,50 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
           "    int inc_ = cn_;",
           "    for (int o_ = 1; o_ < 64; o_ <<= 1) { const int y_ = __shfl_up(inc_, o_, 64); "
           "if (ln >= o_) inc_ += y_; }",
-          "    const int tot_ = __shfl(inc_, 63, 64);",
+          "    const int tot_ = __shfl(inc_, 63, 64);"]
+    layout = pack_layout(p, compacts, cand)
+    if cand:
+        # candidates -> clst_ (CC per pass) -> tail word -> left predicates on its fields ->
+        # stable append to lst_; the walk below runs after the tile's last pass (or when lst_
+        # holds more than CAP entries: a pass adds at most CC)
+        assert layout is not None
+        sign = g1.cnf_sign(lpreds)
+        assert sign is not None
+        fields = {sl: off for sl, off, nb in layout if sl in cand and nb == 2}
+        assert set(fields) == set(cand)
+        sync = J._wave_sync(True)
+        body += ["    const u64* PKc_ = a.PK + tb0;",
+                 "    int np_ = 0, wb_ = 0;",
+                 "    for (;;) {",
+                 "    if (wb_ < tot_) {",
+                 "      { int pos_ = inc_ - cn_ - wb_; u64 e_ = (pos_ < " + str(CC) +
+                 " && pos_ + cn_ > 0) ? d_ : 0ull;",
+                 "        while (e_) { const int bq_ = __builtin_ctzll(e_); "
+                 f"if (pos_ >= 0 && pos_ < {CC}) clst_[wq][pos_] = (unsigned short)(64 * ln + bq_); "
+                 "++pos_; e_ &= e_ - 1ull; } }",
+                 f"      {sync}",
+                 f"      const int cw_ = tot_ - wb_ < {CC} ? tot_ - wb_ : {CC};"]
+        for k in range(EW):
+            body += [f"      const bool fok{k} = {64 * k} + ln < cw_;",
+                     f"      const int fof{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;"]
+        for k in range(EW):
+            body.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
+        body.append(f"      {sync}")
+        for k in range(EW):
+            for sl, off in fields.items():
+                body.append(f"      const int r{sl}_f{k} = (int)(short)(unsigned short)"
+                            f"(fw{k}_ >> {off});")
+            body += [f"      {{ const bool fp_ = fok{k} && (int)({J._rename(sign, pslots, f'f{k}')}) >= 0;",
+                     "        const u64 bl_ = __ballot(fp_);",
+                     "        if (fp_) lst_[wq][np_ + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bl_ >> 32), "
+                     f"__builtin_amdgcn_mbcnt_lo((unsigned)bl_, 0u))] = (unsigned short)fof{k};",
+                     "        np_ += __popcll(bl_); }"]
+        body += [f"      wb_ += {CC};",
+                 f"      if (wb_ < tot_ && np_ <= {CAP}) continue;",
+                 "    }",
+                 "    const int wn_ = np_;"]
+    else:
+        body += [
           f"    for (int wb_ = 0; wb_ < tot_; wb_ += {CAP}) {{",
           f"    const int wn_ = tot_ - wb_ < {CAP} ? tot_ - wb_ : {CAP};",
           "    { int pos_ = inc_ - cn_ - wb_; u64 e_ = d_;",
@@ -1347,9 +1522,9 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
           + ("lrn_[wq][pos_] = (unsigned short)(qr_ + __popcll(m_ & ((2ull << bq_) - 1ull))); "
              if tk is not None else "") +
           "} ++pos_; e_ &= e_ - 1ull; } }",
-          f"    {J._wave_sync()}",
-          f"    for (int cb = 0; cb < wn_; cb += {64 * EW}) {{"]
-    layout = pack_layout(p, compacts)
+          ]
+    body += [f"    {J._wave_sync(bool(cand))}",
+             f"    for (int cb = 0; cb < wn_; cb += {64 * EW}) {{"]
     if layout:
         body.append("      const u64* PKt_ = a.PK + tb0;")
     ind2 = "      "
@@ -1403,18 +1578,19 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
             body += [J._rename(x, tail, it)
                      for x in J._accumulate(g, aggs, grouped, "cok", gvar, ind2)]
         body.append(f"{ind2}}}")
-    body += ["    }", f"    {J._wave_sync()}", "    }"]
+    body += ["    }", f"    {J._wave_sync(bool(cand))}"]
+    body += ["    np_ = 0;", "    if (wb_ >= tot_) break;", "    }"] if cand else ["    }"]
 
     def tile(tv: str, cur: str, nxt: str) -> List[str]:
         return ["   {"] + [x.replace("@T@", tv).replace("@S@", cur).replace("@O@", nxt)
                           for x in body] + ["   }"]
-    if RS_PIPE == 2:
+    if pipe == 2:
         b += ["  for (i64 t = t0; t < t1; t += 2) {"]
         b += tile("t", "A", "B")
         b += ["    if (t + 1 >= t1) break;"]
         b += tile("(t + 1)", "B", "A")
         b += ["  }"]
-    elif RS_PIPE:
+    elif pipe:
         b += ["  for (i64 t = t0; t < t1; ++t) {"]
         b += tile("t", "A", "A")
         b += ["  }"]
@@ -1436,7 +1612,7 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None) -> J.Kerne
             out.append(f"{ind_}const u64 tkey_ = tkey_l;")
             return out
         b += JH._topk_flush(aggs, tk, args, "wid", key_lines)
-    name = "hs_jit_run_bits_scan" if hk is None else \
+    name = "hs_jit_run_bits_cand" if cand else "hs_jit_run_bits_scan" if hk is None else \
         ("hs_jit_run_bits_hash" if tk is None else "hs_jit_run_bits_topk")
     occ = f" __attribute__((amdgpu_waves_per_eu({RS_WAVES}, {RS_WAVES})))" if RS_WAVES else ""
     src = (J._PRELUDE + args.struct_src() +
@@ -1608,9 +1784,15 @@ def lower(p: NL.JoinParams, rstart, rlen, rbucket, roff, compacts, runs, nrows: 
     sparse = RS_BITS and onebit
     if tk is not None and hk is None:
         tk = None
+    # the pruned pair (``prune_plan``): phase 1 pre-filters by per-run bounds and phase 2 takes
+    # the candidate form - always together (the candidate form over unfiltered tags would
+    # gather half the table's tail words), and never with the 16-bit-half or recorded phase 1
+    prune = prune_plan(p, compacts, W, hk, record) if sparse and not \
+        (RT2_LO16 and cache_spans) else ()
+    cand = tuple(dict.fromkeys(sl for _, sl, _ in prune))
     if sparse:
-        ks = J.kernel_for(sparse_shape(p, compacts, hk, tk),
-                          lambda: gen_run_sparse_scan(p, compacts, hk, tk))
+        ks = J.kernel_for(sparse_shape(p, compacts, hk, tk, cand),
+                          lambda: gen_run_sparse_scan(p, compacts, hk, tk, cand))
     else:
         ks = J.kernel_for(scan_shape(p, compacts, W, NI),
                           lambda: gen_run_scan(p, compacts, W, NI))
@@ -1624,16 +1806,21 @@ def lower(p: NL.JoinParams, rstart, rlen, rbucket, roff, compacts, runs, nrows: 
                              __import__("numpy").zeros(4, "int64")).to(dev)
     # 32-bit run / right-row indices when both fit (with slack for the gallop's overshoot)
     ix32 = RT2_I32 and nruns < (1 << 31) - (1 << 20) and int(roff[-1].item()) < (1 << 31) - (1 << 20)
-    kt = J.kernel_for(tags2_shape(p, compacts, W, ix32),
-                      lambda: gen_run_tags2(p, compacts, W, ix32))
+    kt = J.kernel_for(tags2_shape(p, compacts, W, ix32, "", prune),
+                      lambda: gen_run_tags2(p, compacts, W, ix32, "", prune))
     vt = {"RNG": rng_d.data_ptr(), "NRG": len(rng), "NRUNS": nruns, "tags": tags.data_ptr(),
           "num_groups": p.num_groups, "group_base": p.group_base}
     tr = rng_d
+    bnd = []
+    for _, sl, mx in prune:
+        mn_t, mx_t = run_bounds(runs, compacts[sl])
+        vt[f"RMX{sl}" if mx else f"RMN{sl}"] = (mx_t if mx else mn_t).data_ptr()
+        bnd += [mn_t, mx_t]
     grid_t = max(1, RT2_WIDE_GRID if tags2_wide(p, compacts, ix32) == 4 else RT2_GRID)
     vt["KLO"], vt["KSP"], vt["KOF"] = frame
     J._fill_cols(vt, p.cols, compacts)
     lo = lo16_keys(p, compacts, W, vt, nruns, int(roff[-1].item()), grid_t, dev) \
-        if RT2_LO16 and ix32 and cache_spans else None
+        if RT2_LO16 and ix32 and cache_spans and not prune else None
     if lo is not None:
         kt = J.kernel_for(tags2_shape(p, compacts, W, ix32, "lo16"),
                           lambda: gen_run_tags2(p, compacts, W, ix32, "lo16"))
@@ -1649,11 +1836,12 @@ def lower(p: NL.JoinParams, rstart, rlen, rbucket, roff, compacts, runs, nrows: 
         from ..ops import kernels as K
         tp64 = K.ranges_to_tiles(rlen + (rstart & 63), 4096)   # 64-aligned 4096-row tiles
         vs["tile_prefix"] = tp64.data_ptr()
-        layout = pack_layout(p, compacts)
+        layout = pack_layout(p, compacts, cand)
         pk = packed_tail(layout, compacts) if layout else None
         if pk is not None:
             vs["PK"] = pk.data_ptr()
-        spans = (spans, tp64, pk, fill_pack12(vs, p, compacts))
+        # (the candidate form reads no row stream: no 12-bit copy is built for it)
+        spans = (spans, tp64, pk, bnd if cand else fill_pack12(vs, p, compacts))
         grid_s = max(1, RS_BITS_GRID)
     if tk is not None:
         tk.bind(grid_s * (J.BLOCK // 64), dev)

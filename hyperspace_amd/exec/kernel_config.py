@@ -100,6 +100,11 @@ class KernelConfig:
     rs_waves: int = 0            # bits scan waves per SIMD the compiler must fit (0: its choice)
     rs_pack12: bool = True       # bits scan reads 16-bit predicate codes within [0, 4095] from a
                                  # 12-bit packed copy (25% fewer bytes of its row stream)
+    rs_prune: bool = True        # phase 1 also tests per-run bounds of the left predicate columns
+                                 # (hs_run_minmax16), so only runs that may hold a passing row
+                                 # stay tagged; phase 2 then reads no row stream: it tests the
+                                 # tagged runs' rows on predicate fields of the row-packed tail
+                                 # word (jit_runs.prune_plan; plain aggregates, 1-bit tags)
     rs_lut: bool = True          # bits scan row tags by nibble through an LDS table (else a loop
                                  # over each group's run starts + prefix XOR)
     rs_lds: bool = False         # bits scan predicate columns loaded lane-coalesced, then moved

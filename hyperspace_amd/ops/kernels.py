@@ -738,6 +738,21 @@ def ranges_to_tiles(rlen, tile_rows: int = None):
     return tp
 
 
+def run_minmax16(gmask, gruns, nruns: int, codes):
+    """Per-run bounds of a 16-bit compact column over a key's run form (``hs_run_minmax16``):
+    (mn, mx) int16 tensors holding uint16 bits, code + 32768, padded to a multiple of 256 runs
+    with mn = 0xFFFF and mx = 0 (an empty interval)."""
+    torch = _torch()
+    assert codes.dtype == torch.int16 and (codes.numel() + 63) // 64 == gmask.numel()
+    nrp = max(256, (int(nruns) + 255) // 256 * 256)
+    mn = torch.full((nrp,), -1, dtype=torch.int16, device=codes.device)
+    mx = torch.zeros(nrp, dtype=torch.int16, device=codes.device)
+    NL.check(NL.lib().hs_run_minmax16(NL.ptr(gmask), NL.ptr(gruns), NL.ptr(codes),
+                                      int(codes.numel()), NL.ptr(mn), NL.ptr(mx),
+                                      NL.stream_ptr()), "hs_run_minmax16")
+    return mn, mx
+
+
 def sortable_image(value, hs_type: int) -> int:
     """Host mirror of hs_sortable for a literal."""
     import struct

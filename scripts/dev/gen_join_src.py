@@ -62,6 +62,13 @@ def main(out):
         ks = [jit_runs.gen_run_tags2(p, comp, W, jit_runs.RT2_I32), jit_runs.gen_run_scan(p, comp, W, NI)]
         if W == 1 and not (p.group_col >= 8 and p.num_groups > 1):
             ks.append(jit_runs.gen_run_sparse_scan(p, comp))
+            # the pruned pair (rs_prune): bounds-tested phase 1, candidate form of phase 2
+            pr = jit_runs.prune_plan(p, comp, W)
+            if pr:
+                cand = tuple(dict.fromkeys(sl for _, sl, _ in pr))
+                kp = jit_runs.gen_run_tags2(p, comp, W, jit_runs.RT2_I32, "", pr)
+                kp.name += "_pruned"     # (file name only)
+                ks += [kp, jit_runs.gen_run_sparse_scan(p, comp, None, None, cand)]
             # hash walk grouped by the left key (the functionally reduced Q3 GROUP BY)
             from hyperspace_amd.exec import hash_agg as H
             ph, _, _ = q3_params(ng)
