@@ -37,6 +37,11 @@ against the same query with Hyperspace disabled (the reference's correctness ora
   ``l_orderkey``: top-3 lines per order by price (``row_number``, filtered and aggregated), a
   running ``sum(l_quantity)`` per supplier by ship date, and a per-order total that needs no
   sort; q/s on the device against the host engine and whether the device sort was skipped.
+* ``broadcast_join`` — ``lineitem`` (index on ``l_shipdate``) joined to small tables with the
+  broadcast threshold at its default: ``supplier`` summed, grouped by nation, ``nation`` chained
+  on top, and a left-anti join against a 1000-key local list; ms per query, the executor path
+  and the hash-join metrics of each shape.  ``--probe-sweep`` instead times the probe kernel
+  alone against a 25-key and a 1M-key table for 1 / 2 / 4 / 8 stream rows per lane.
 """
 import argparse
 import datetime
@@ -826,10 +831,171 @@ def config_window(args):
     return out
 
 
+def _write_dimensions(root, sf):
+    """TPC-H-shaped ``supplier`` (10k x SF rows: the domain of ``l_suppkey``; key and nation only,
+    so SF100's 1M rows stay under the 10 MiB broadcast threshold) and ``nation`` (25 rows)."""
+    import numpy as np
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+    n = int(10_000 * sf)
+    rng = np.random.default_rng(31)
+    sup = pa.table({"s_suppkey": rng.permutation(np.arange(1, n + 1, dtype=np.int64)),
+                    "s_nationkey": rng.integers(0, 25, n).astype(np.int32)})
+    nat = pa.table({"n_nationkey": np.arange(25, dtype=np.int32),
+                    "n_name": pa.array([f"NATION-{i:02d}" for i in range(25)]),
+                    "n_regionkey": (np.arange(25) % 5).astype(np.int32)})
+    for name, t in (("supplier", sup), ("nation", nat)):
+        os.makedirs(os.path.join(root, name))
+        pq.write_table(t, os.path.join(root, name, "part-0.parquet"))
+    return n
+
+
+def _probe_sweep(rows, reps=15):
+    """The probe kernel alone (``hs_hj_probe``, csrc/kernels/hash_join.hip): ``rows`` random int64
+    stream keys, ~80 % of them present, against a unique 25-key and a unique 1M-key table, for
+    1 / 2 / 4 / 8 stream rows per lane, writing the mark byte alone and the mark plus the build
+    row id.  Median of ``reps`` launches by device events; bytes are the stream side's (key,
+    mark, row id).  Under ``rocprofv3 --kernel-trace --stats`` use ``HS_CFG_SWEEP_LANES=4
+    HS_CFG_SWEEP_REPS=3`` for a short run of the default."""
+    import ctypes as C
+    import pyarrow as pa
+    import torch
+    from hyperspace_amd.exec.device_table import DeviceColumn
+    from hyperspace_amd.ops import _lib as NL, kernels as K
+    dev = torch.device("cuda", torch.cuda.current_device())
+    lanes = [int(x) for x in os.environ.get("HS_CFG_SWEEP_LANES", "1,2,4,8").split(",")]
+    reps = int(os.environ.get("HS_CFG_SWEEP_REPS", reps))
+    L = NL.lib()
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    out = []
+    for nkeys in (25, 1_000_000):
+        bk = (torch.randperm(nkeys, device=dev, generator=g) + 1).to(torch.int64)
+        table = K.hash_join_table(DeviceColumn(bk, None, pa.int64()))
+        sk = torch.randint(1, nkeys + nkeys // 4 + 2, (rows,), device=dev, generator=g,
+                           dtype=torch.int64)
+        desc = DeviceColumn(sk, None, pa.int64()).desc()
+        mark = torch.empty(rows, dtype=torch.uint8, device=dev)
+        build = torch.empty(rows, dtype=torch.int64, device=dev)
+
+        def probe(rpl, want_build):
+            NL.check(L.hs_hj_probe(
+                C.byref(desc), rows, None, rows, NL.ptr(table.keys), NL.ptr(table.first),
+                NL.ptr(table.last), NL.ptr(table.perm), table.slots, table.nbuild, 0, rpl, None,
+                None, NL.ptr(mark), NL.ptr(build) if want_build else None, NL.stream_ptr()),
+                "hs_hj_probe")
+        for want_build in (False, True):
+            for rpl in lanes:
+                probe(rpl, want_build)
+                torch.cuda.synchronize()
+                ts = []
+                for _ in range(reps):
+                    a = torch.cuda.Event(enable_timing=True)
+                    b = torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    probe(rpl, want_build)
+                    b.record()
+                    b.synchronize()
+                    ts.append(a.elapsed_time(b))
+                ts.sort()
+                nbytes = rows * (8 + 1 + (8 if want_build else 0))
+                med = ts[len(ts) // 2]
+                out.append({"keys": nkeys, "slots": table.slots, "rows": rows,
+                            "rows_per_lane": rpl,
+                            "outputs": "mark+row_id" if want_build else "mark",
+                            "ms_median": round(med, 4), "ms_min": round(ts[0], 4),
+                            "ms_max": round(ts[-1], 4), "stream_bytes": nbytes,
+                            "table_bytes": (table.slots + 2) * 16 + table.nbuild * 4,
+                            "stream_GBps": round(nbytes / med / 1e6, 1),
+                            "hits": int(mark.sum().item())})
+    return out
+
+
+def config_broadcast_join(args):
+    """Joins of ``lineitem`` (index on ``l_shipdate``) with small tables under the DEFAULT
+    broadcast threshold, so they plan as ``BroadcastHashJoin``: a one-year ship-date range joined
+    to ``supplier`` (unique key) and summed; the same grouped by ``s_nationkey``; ``nation``
+    chained on top (a second broadcast join); a left-anti join against a 1000-key
+    ``createDataFrame`` list.  Each shape is reduced to one row or a handful of groups and
+    cross-checked against the host engine (``HS_CFG_SKIP_HOST=1`` skips that).
+    ``HS_CFG_BROADCAST_THRESHOLD=-1`` plans the same queries as shuffled sort-merge joins, for
+    comparison.  ``--probe-sweep`` runs the probe-kernel sweep alone (``_probe_sweep``)."""
+    if getattr(args, "probe_sweep", False):
+        from hyperspace_amd.ops import _lib as NL
+        return {"config": "broadcast_join", "device": args.device,
+                "default_rows_per_lane": int(NL.lib().hs_hj_rows_per_lane()),
+                "probe_sweep": _probe_sweep(args.probe_rows)}
+    import numpy as np
+    from hyperspace_amd import Hyperspace, IndexConfig, col, count, sum_
+    sf = args.sf
+    data, _ = _tpch(args, sf)
+    root = os.path.join(args.data_dir, f"cfg_broadcast_join_sf{sf:g}")
+    shutil.rmtree(root, ignore_errors=True)
+    nsup = _write_dimensions(root, sf)
+    thr = os.environ.get("HS_CFG_BROADCAST_THRESHOLD", "10485760")
+    s = _session(root, args.device, args.buckets,
+                 **{"spark.sql.autoBroadcastJoinThreshold": thr})
+    hs = Hyperspace(s)
+    li = s.read.parquet(os.path.join(data, "lineitem"))
+    dt, _ = _build(hs, li, IndexConfig("li_ship_bj", ["l_shipdate"], [
+        "l_suppkey", "l_extendedprice", "l_discount"]), args.device)
+    Hyperspace.enable(s)
+    sup = s.read.parquet(os.path.join(root, "supplier"))
+    nat = s.read.parquet(os.path.join(root, "nation"))
+    keys = np.random.default_rng(5).choice(np.arange(1, nsup + 1, dtype=np.int64),
+                                           size=min(1000, nsup), replace=False)
+    lst = s.createDataFrame({"k": keys})
+
+    def base(i):
+        year = 1993 + i % 5
+        lo, hi = datetime.date(year, 1, 1), datetime.date(year + 1, 1, 1)
+        return li.filter((col("l_shipdate") >= lo) & (col("l_shipdate") < hi))
+
+    def joined(i):
+        return base(i).join(sup, li["l_suppkey"] == sup["s_suppkey"])
+    aggs = (sum_("l_extendedprice").alias("price"), count("*").alias("n"))
+    shapes = {
+        "supplier_sum": lambda i: joined(i).agg(*aggs),
+        "by_nation": lambda i: joined(i).groupBy("s_nationkey").agg(*aggs),
+        "nation_chain": lambda i: joined(i).join(nat, sup["s_nationkey"] == nat["n_nationkey"])
+        .groupBy("n_regionkey").agg(*aggs),
+        "anti_list": lambda i: base(i).join(lst, li["l_suppkey"] == lst["k"], "leftanti")
+        .agg(*aggs),
+    }
+    out = {"config": "broadcast_join", "device": args.device, "sf": sf, "threshold": thr,
+           "supplier_rows": nsup, "index_build_s": round(dt, 3), "shapes": {}}
+    got = {}
+    for name, q in shapes.items():
+        plan = q(0).queryExecution.executed_plan.tree_string()
+        r = {"index_used": "li_ship_bj" in plan, "broadcast_joins": plan.count("BroadcastHashJoin")}
+        got[name] = [_rows(q(i)) for i in range(2)]
+        be = s.backend()
+        r["path"] = getattr(be, "last_path", None)
+        r["fallback_reason"] = getattr(be, "fallback_reason", None)
+        r["hash_join"] = getattr(be, "metrics", {}).get("hash_join") \
+            if r["path"] == "native" and r["broadcast_joins"] else None
+        k = args.steps if r["path"] == "native" else max(2, min(3, args.steps))
+        el = _timed_loop(lambda i: q(i).collect(), k, args.device)
+        r["ms_per_query"] = round(el / k * 1e3, 2)
+        out["shapes"][name] = r
+    if os.environ.get("HS_CFG_SKIP_HOST"):
+        return out
+    s.conf.set("spark.hyperspace.mi.execution.device", "cpu")
+    for name, q in shapes.items():
+        t0 = time.perf_counter()
+        ref = [_rows(q(i)) for i in range(2)]
+        out["shapes"][name]["host_engine_ms_per_query"] = \
+            round((time.perf_counter() - t0) / 2 * 1e3, 1)
+        out["shapes"][name]["match"] = all(_close(a, b) for a, b in zip(got[name], ref))
+    out["match"] = all(r["match"] for r in out["shapes"].values())
+    return out
+
+
 CONFIGS = {"csv10k": config_csv10k, "sf10_filter": config_sf10_filter, "hybrid": config_hybrid,
            "q3_3way": config_q3_3way, "tpcds_3way": config_tpcds_3way,
            "streamed": config_streamed, "like": config_like,
-           "count_distinct": config_count_distinct, "window": config_window}
+           "count_distinct": config_count_distinct, "window": config_window,
+           "broadcast_join": config_broadcast_join}
 
 
 def main():
@@ -845,6 +1011,10 @@ def main():
                     help="streamed: the build and resident-table HBM budgets")
     ap.add_argument("--like-runs", type=int, default=11,
                     help="like: timed runs per dictionary size and route (medians reported)")
+    ap.add_argument("--probe-sweep", action="store_true",
+                    help="broadcast_join: time the hash-join probe kernel alone, per rows per lane")
+    ap.add_argument("--probe-rows", type=int, default=1 << 26,
+                    help="broadcast_join --probe-sweep: stream rows")
     args = ap.parse_args()
     if args.device == "gpu":
         import torch

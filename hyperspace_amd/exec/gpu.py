@@ -8,6 +8,7 @@ needs rows, so the hot shapes compile into single fused launches:
 * ``Aggregate <- SortMergeJoin(IndexScan, IndexScan)`` -> ``hs_join_agg`` (co-located, no shuffle)
 * ``Filter/Project <- Scan``                       -> ``hs_scan_select`` + ``hs_gather``
 * ``SortMergeJoin``                                 -> ``hs_join_count/emit`` + gathers
+* ``BroadcastHashJoin``                             -> ``hs_hj_build/probe/emit`` + gathers
 * ``Exchange(hashpartitioning) <- Scan``           -> Murmur3 + radix sort on the device
 * ``Window <- [Sort <- Exchange] <- rows``          -> one device sort (none over a matching index)
                                                       + segmented scans (exec/window.py)
@@ -20,8 +21,9 @@ and the whole query runs on the host oracle (recorded in ``last_path``).
 
 ``GpuBackend`` is composed from one module per operator family: ``gpu_agg`` (fused scan
 aggregates, prepared lowerings, streaming, cross-rank combine), ``gpu_join`` (co-partitioned
-joins and the device shuffle), ``gpu_semi`` (bitmap and co-partitioned semi-joins) and
-``gpu_hash`` (hash-mode GROUP BY, run top-K); shared names live in ``gpu_common``.  This module
+joins and the device shuffle), ``gpu_semi`` (bitmap and co-partitioned semi-joins),
+``gpu_hash`` (hash-mode GROUP BY, run top-K) and ``gpu_hash_join`` (broadcast hash joins); shared
+names live in ``gpu_common``.  This module
 keeps the query entry points, relations, scans and row output."""
 from __future__ import annotations
 
@@ -50,6 +52,7 @@ from .gpu_common import (arrow_table, _AggProgram, _needs_eval, _prefix_sorted,
                          _warm_torch_kernels, DRel, log, QueryFuture, Unsupported)
 from .gpu_agg import AggOps
 from .gpu_hash import HashAggOps
+from .gpu_hash_join import HashJoinOps
 from .gpu_join import JoinOps
 from .gpu_semi import SemiJoinOps
 # re-exported for tests and diagnostics scripts
@@ -84,7 +87,7 @@ def release_process_device_memory() -> None:
     torch.cuda.empty_cache()
 
 
-class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps):
+class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
     name = "gpu"
     # QueryExecution may submit a plan-cache entry's own plan with a query's literals bound in
     # place (plan/plan_cache.py): everything literal-dependent is read during collect_async
@@ -338,6 +341,10 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps):
             return self._repartition(self._rel(p.child), p.partitioning)
         if isinstance(p, X.SortMergeJoinExec):
             return self._join_rel(p)
+        if isinstance(p, X.BroadcastHashJoinExec):
+            return self._hash_join_rel(p)
+        if isinstance(p, X.LocalTableScanExec):
+            return self._local_table_rel(p)
         if isinstance(p, X.UnionExec):
             # UNION ALL: every child's rows (its pending filters applied) concatenated into one
             # flat device relation, columns by position

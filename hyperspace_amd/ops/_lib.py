@@ -261,6 +261,10 @@ def lib():
     _sig(L.hs_win_rank, I, P, I64, P, P, P, P, P)
     _sig(L.hs_win_frame_ends, I, P, I64, I, P, P, P)
     _sig(L.hs_win_agg, I, P, P, P, I64, I, P, P, P, P, P)
+    _sig(L.hs_hj_rows_per_lane, I)
+    _sig(L.hs_hj_build, I, P, I64, P, I64, P, P, P, I64, P)
+    _sig(L.hs_hj_probe, I, P, I64, P, I64, P, P, P, P, I64, I64, I, I, P, P, P, P, P)
+    _sig(L.hs_hj_emit, I, P, I64, P, P, I64, P, P, P, I64, I64, I, P, P, P)
     _lib = L
     return L
 

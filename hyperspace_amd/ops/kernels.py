@@ -395,6 +395,153 @@ def win_agg(col, flags, ends, kind: int, ws=None, with_count: bool = False):
 
 
 # ------------------------------------------------------------------------------------------------
+# Broadcast hash join (csrc/kernels/hash_join.hip)
+# ------------------------------------------------------------------------------------------------
+HJ_MIN_SLOTS = 64
+HJ_MAX_SLOTS = 1 << 30
+
+
+class HashJoinTable:
+    """The hash table of a join's build side (``hash_join_table``).  ``keys`` (int64, ~0 = empty)
+    has ``slots`` + 2 entries, slot ``slots`` being the key -1's; ``first`` / ``last`` (int32, -1
+    = unset) are positions into ``perm``, the ``nbuild`` build rows with a non-NULL key sorted
+    stably by key (int32 row ids): the matches of a key are ``perm[first[s] : last[s] + 1]``.
+    ``nkeys`` distinct keys; ``unique`` when every key has one row."""
+    __slots__ = ("keys", "first", "last", "perm", "slots", "nkeys", "nbuild", "unique", "n_src")
+
+    def __init__(self, keys, first, last, perm, slots, nkeys, nbuild, n_src):
+        self.keys, self.first, self.last, self.perm = keys, first, last, perm
+        self.slots, self.nkeys, self.nbuild, self.n_src = slots, nkeys, nbuild, n_src
+        self.unique = nkeys == nbuild
+
+
+def hash_join_slots(nbuild: int) -> int:
+    """Slots of the table over ``nbuild`` build rows: a power of two, at least twice the rows
+    (so at least twice the distinct keys: load <= 0.5, an insert always succeeds)."""
+    m = max(HJ_MIN_SLOTS, 1 << max(0, int(2 * nbuild - 1).bit_length()))
+    if m > HJ_MAX_SLOTS:
+        raise ValueError(f"hash join build side of {nbuild} rows is too large")
+    return m
+
+
+def _hj_check_key(col) -> None:
+    if col.is_float or col.hs_type == NL.U64:
+        raise ValueError("hash join keys are integers read as int64 (no float, no uint64)")
+
+
+def hash_join_table(key_col, rows=None) -> HashJoinTable:
+    """Build the join hash table over ``key_col`` (an integer ``DeviceColumn``): all its rows,
+    or the ascending int64 row ids ``rows``.  Rows with a NULL key are left out.  One host sync
+    (the distinct-key count).  An empty build side launches nothing."""
+    torch = _torch()
+    from ..exec.device_table import DeviceColumn
+    _hj_check_key(key_col)
+    dev = key_col.data.device
+    n_src = len(key_col)
+    sel = rows
+    if key_col.valid is not None:
+        if sel is None:
+            sel = torch.arange(n_src, dtype=torch.int64, device=dev)
+        sel = select_marked(sel, (key_col.valid != 0).to(torch.uint8), 1)
+    nb = int(sel.numel()) if sel is not None else n_src
+    if nb >= (1 << 31):
+        raise ValueError("hash join build side over 2^31 rows")
+    # the sort reads a column of exactly the build rows: the build side is the small one
+    if sel is not None:
+        kc = gather_columns([key_col], sel, want_valid=False)[0] if nb else None
+    else:
+        kc = DeviceColumn(key_col.data, None, key_col.atype)
+    if nb > 1:
+        perm = sort_permutation([kc])
+    else:
+        perm = torch.zeros(nb, dtype=torch.int32, device=dev)
+    if sel is not None and nb:
+        perm = sel.index_select(0, perm.long()).to(torch.int32)
+    M = hash_join_slots(nb)
+    keys = torch.full((M + 2,), -1, dtype=torch.int64, device=dev)
+    first = torch.full((M + 2,), -1, dtype=torch.int32, device=dev)
+    last = torch.full((M + 2,), -1, dtype=torch.int32, device=dev)
+    nkeys = 0
+    if nb:
+        desc = key_col.desc()
+        NL.check(NL.lib().hs_hj_build(C.byref(desc), n_src, NL.ptr(perm), nb, NL.ptr(keys),
+                                      NL.ptr(first), NL.ptr(last), M, NL.stream_ptr()),
+                 "hs_hj_build")
+        nkeys = int((first[:M + 1] >= 0).sum().item())
+    return HashJoinTable(keys, first, last, perm, M, nkeys, nb, n_src)
+
+
+def hash_join_probe(table: HashJoinTable, key_col, rows=None, how: str = "pairs",
+                    rows_per_lane: int = 0):
+    """Probe ``table`` with the stream rows of ``key_col`` (all of them, or the ascending int64
+    row ids ``rows``).  ``how``:
+
+    * ``"pairs"``: (stream row ids, build row ids), int64 - stream rows in their order, the
+      matches of one stream row in ascending build-row order;
+    * ``"preserve"``: the same plus (row, -1) for every stream row without a match, in place;
+    * ``"mark"``: uint8 per probed row, 1 = it has a match.
+
+    A NULL key matches nothing.  Empty inputs launch nothing."""
+    torch = _torch()
+    if how not in ("pairs", "preserve", "mark"):
+        raise ValueError(f"hash_join_probe: how={how!r}")
+    _hj_check_key(key_col)
+    dev = key_col.data.device
+    n_src = len(key_col)
+    n = int(rows.numel()) if rows is not None else n_src
+    L = NL.lib()
+
+    def stream_ids():
+        return rows if rows is not None else torch.arange(n, dtype=torch.int64, device=dev)
+
+    if n == 0 or table.nbuild == 0:
+        if how == "mark":
+            return torch.zeros(n, dtype=torch.uint8, device=dev)
+        if how == "preserve":
+            return stream_ids(), torch.full((n,), -1, dtype=torch.int64, device=dev)
+        e = torch.empty(0, dtype=torch.int64, device=dev)
+        return e, e.clone()
+    desc = key_col.desc()
+    preserve = 1 if how == "preserve" else 0
+
+    def probe(slot=None, count=None, mark=None, build=None):
+        NL.check(L.hs_hj_probe(C.byref(desc), n_src, NL.ptr(rows), n, NL.ptr(table.keys),
+                               NL.ptr(table.first), NL.ptr(table.last), NL.ptr(table.perm),
+                               table.slots, table.nbuild, preserve, int(rows_per_lane),
+                               NL.ptr(slot), NL.ptr(count), NL.ptr(mark), NL.ptr(build),
+                               NL.stream_ptr()), "hs_hj_probe")
+
+    if how == "mark":
+        mark = torch.empty(n, dtype=torch.uint8, device=dev)
+        probe(mark=mark)
+        return mark
+    if table.unique:
+        # the slot names the one build row: no count, scan or emit
+        build = torch.empty(n, dtype=torch.int64, device=dev)
+        if how == "preserve":
+            probe(build=build)
+            return stream_ids(), build
+        mark = torch.empty(n, dtype=torch.uint8, device=dev)
+        probe(mark=mark, build=build)
+        pos = select_marked(torch.arange(n, dtype=torch.int64, device=dev), mark, 1)
+        if int(pos.numel()) == n:       # every row found its key (a foreign key): nothing to drop
+            return (rows if rows is not None else pos), build
+        sid = rows.index_select(0, pos) if rows is not None else pos
+        return sid, build.index_select(0, pos)
+    slot = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(n, dtype=torch.int64, device=dev)
+    probe(slot=slot, count=count)
+    offs = exclusive_scan_i64(count)
+    total = int((offs[-1] + count[-1]).item())
+    out_s = torch.empty(total, dtype=torch.int64, device=dev)
+    out_b = torch.empty(total, dtype=torch.int64, device=dev)
+    NL.check(L.hs_hj_emit(NL.ptr(rows), n, NL.ptr(slot), NL.ptr(offs), total, NL.ptr(table.first),
+                          NL.ptr(table.last), NL.ptr(table.perm), table.slots, table.nbuild,
+                          preserve, NL.ptr(out_s), NL.ptr(out_b), NL.stream_ptr()), "hs_hj_emit")
+    return out_s, out_b
+
+
+# ------------------------------------------------------------------------------------------------
 # Gather
 # ------------------------------------------------------------------------------------------------
 # packed-row gather (hs_gather_packed, opt-in: HS_GATHER_PACKED=1): tables of at least this many
