@@ -197,9 +197,49 @@ __global__ __launch_bounds__(256) void hs_run_minmax16_kernel(const uint64_t* __
   }
 }
 
+// 16-bit form of a bucket-sorted int32 code array over 32-element groups (exec/encoding.py
+// group16_32: the four-run phase 1 of exec/jit_runs.py reads its key columns this way).  Per
+// group its smallest code goes to gbase and each element's uint16 offset from it to off, so
+// code = gbase[i >> 5] + off[i] exactly.  A group spanning 2^16 codes or more (one straddling a
+// bucket edge, or sparse keys) is wide: gbase = WIDE_GROUP and zero offsets, and readers take
+// the 32-bit codes.  Half a wavefront owns a group: one element per lane, a 5-step butterfly
+// that never leaves the half, one pass, no atomics.  Elements of [n, npad) are padding (npad a
+// multiple of 256): zero offsets, and a group without any real element is wide, so whole-block
+// vector loads of both arrays stay in bounds and never reconstruct a code from padding.
+constexpr int32_t WIDE_GROUP = INT32_MIN;
+
+__global__ __launch_bounds__(256) void hs_group16_32_kernel(const int32_t* __restrict__ x,
+                                                            int64_t n, int64_t npad,
+                                                            int32_t* __restrict__ gbase,
+                                                            uint16_t* __restrict__ off) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npad) return;   // (npad is a multiple of the block: never taken by part of a group)
+  const bool in = i < n;
+  const int32_t v = in ? x[i] : 0;
+  int32_t mn = in ? v : INT32_MAX, mx = in ? v : INT32_MIN;
+#pragma unroll
+  for (int o = 1; o < 32; o <<= 1) {
+    const int32_t a = __shfl_xor(mn, o, 64), b = __shfl_xor(mx, o, 64);
+    mn = a < mn ? a : mn;
+    mx = b > mx ? b : mx;
+  }
+  const bool wide = mn > mx || (int64_t)mx - (int64_t)mn >= 65536 || mn == WIDE_GROUP;
+  off[i] = (wide || !in) ? (uint16_t)0 : (uint16_t)((uint32_t)v - (uint32_t)mn);
+  if ((threadIdx.x & 31) == 0) gbase[i >> 5] = wide ? WIDE_GROUP : mn;
+}
+
 }  // namespace
 
 extern "C" {
+
+// gbase: npad / 32 int32, off: npad uint16; npad >= n, a multiple of 256
+int hs_group16_32(const int32_t* x, int64_t n, int64_t npad, int32_t* gbase, uint16_t* off,
+                  void* stream) {
+  if (npad <= 0 || (npad & 255) || npad < n) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(hs_group16_32_kernel, dim3((unsigned)(npad / 256)), dim3(256), 0,
+                     (hipStream_t)stream, x, n, npad, gbase, off);
+  return (int)hipGetLastError();
+}
 
 // mn / mx: one uint16 per run (the caller pads them); codes: n int16 rows of the run form's table
 int hs_run_minmax16(const uint64_t* gmask, const int32_t* gruns, const int16_t* codes, int64_t n,

@@ -172,8 +172,10 @@ struct Args {
   long long KLO;
   long long KSP;
   long long KOF;
-  const unsigned short* RMX1;
-  long long CL1;
+  const unsigned short* LO16;
+  const unsigned short* RO16;
+  const int* LG16;
+  const int* RG16;
   const int* c8;
   long long B8;
   const short* c9;
@@ -183,6 +185,7 @@ struct Args {
 };
 typedef int hs_i4 __attribute__((ext_vector_type(4)));
 typedef unsigned short hs_us4 __attribute__((ext_vector_type(4)));
+typedef unsigned short hs_ro4 __attribute__((ext_vector_type(4), aligned(2)));
 typedef int hs_rk4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef int hs_c8x4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef short hs_c9x4 __attribute__((ext_vector_type(4), aligned(2)));
@@ -208,8 +211,9 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
   int lr0 = (int)RG[4 * rg], lr1 = (int)RG[4 * rg + 1], s0 = (int)RG[4 * rg + 2], s1 = (int)RG[4 * rg + 3];
   i64 nxt0 = rg + 1 < a.NRG ? RG[4 * (rg + 1)] : 0x7fffffffffffffffll;
   int gbase = -1;   // right row of the next stage's first run (-1: range-relative)
-  int pbA = 0; hs_v4u LA0 = {}; hs_rk4 RA0 = {}; hs_us4 M0A0 = {}; hs_c8x4 C8A0 = {}; hs_c9x4 C9A0 = {}; hs_v4u LA1 = {}; hs_rk4 RA1 = {}; hs_us4 M0A1 = {}; hs_c8x4 C8A1 = {}; hs_c9x4 C9A1 = {};
-  int pbB = 0; hs_v4u LB0 = {}; hs_rk4 RB0 = {}; hs_us4 M0B0 = {}; hs_c8x4 C8B0 = {}; hs_c9x4 C9B0 = {}; hs_v4u LB1 = {}; hs_rk4 RB1 = {}; hs_us4 M0B1 = {}; hs_c8x4 C8B1 = {}; hs_c9x4 C9B1 = {};
+  int pbA = 0; hs_us4 LA0 = {}; hs_ro4 RA0 = {}; int LGA0 = 0, RGA0 = 0, RHA0 = 0; hs_c8x4 C8A0 = {}; hs_c9x4 C9A0 = {}; hs_us4 LA1 = {}; hs_ro4 RA1 = {}; int LGA1 = 0, RGA1 = 0, RHA1 = 0; hs_c8x4 C8A1 = {}; hs_c9x4 C9A1 = {};
+  int pbB = 0; hs_us4 LB0 = {}; hs_ro4 RB0 = {}; int LGB0 = 0, RGB0 = 0, RHB0 = 0; hs_c8x4 C8B0 = {}; hs_c9x4 C9B0 = {}; hs_us4 LB1 = {}; hs_ro4 RB1 = {}; int LGB1 = 0, RGB1 = 0, RHB1 = 0; hs_c8x4 C8B1 = {}; hs_c9x4 C9B1 = {};
+  int slow_ = 0;
   int nb = bbeg;
   while (nb < bend) {
     while (nxt0 <= ((i64)nb << 8)) {
@@ -219,7 +223,7 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
     }
     const int rb_ = (nb) << 8;
     const int base_ = gbase >= 0 ? gbase + 0 : s0 + (rb_ - lr0);
-    const bool f_ = (nb) + 2 <= bend && rb_ >= lr0 && rb_ + 512 <= lr1 && rb_ + 512 <= NR && (i64)rb_ + 512 <= nxt0 && base_ >= s0 && base_ + 512 <= s1;
+    const bool f_ = slow_ == 0 && (nb) + 2 <= bend && rb_ >= lr0 && rb_ + 512 <= lr1 && rb_ + 512 <= NR && (i64)rb_ + 512 <= nxt0 && base_ >= s0 && base_ + 512 <= s1;
     if (!f_) {   // slow block: its 64-run groups one at a time
 #pragma unroll 1
       for (i64 gi = (i64)nb << 2; gi < (((i64)nb + 1) << 2) && gi < gend; ++gi) {
@@ -239,7 +243,6 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
         j0 = act0 ? (j0 < a0_0 ? a0_0 : (j0 >= a1_0 ? a1_0 - 1 : j0)) : 0;
         const unsigned key0 = (unsigned)a.RK0[act0 ? r0 : 0] + (unsigned)a.KOF;
         const unsigned k0 = IMGF(j0);
-        const int bm0_0 = (int)a.RMX1[act0 ? r0 : 0];
         const int w8_g0 = a.c8[j0];
         const int r8_g0 = (int)w8_g0;
         const long long x8_g0 = (long long)(a.B8 + (i64)w8_g0);
@@ -274,48 +277,52 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
           const int x9_h0 = (int)(a.B9 + (i64)w9_h0);
           tg0 = ((hit0) && ((true)) && ((true)) && ((true && (r9_h0 >= (int)a.CL4 && r9_h0 <= (int)a.CH4))) ? 1u : 0u);
         }
-        tg0 = ((bm0_0 >= hs_c20(a.CL1) + 32768)) ? tg0 : 0u;
         { const u64 bal_ = __ballot(tg0 != 0u);
           if (in0 && lane < 2) a.tags[((gi + 0) << 1) + lane] = (unsigned)(bal_ >> (32 * lane)); }
         gbase = __builtin_amdgcn_readlane((hit0 && own0) ? m0 + 1 : -1, 63);
       }
+      slow_ -= slow_ > 0 ? 1 : 0;
       ++nb; continue;
     }
     pbA = base_;
-    LA0 = *(const hs_v4u*)(a.RK0 + (rb_ + 0 + 4 * lane));
-    RA0 = *(const hs_rk4*)(a.c8 + (base_ + 0 + 4 * lane));
-    M0A0 = *(const hs_us4*)(a.RMX1 + (rb_ + 0 + 4 * lane));
+    LA0 = *(const hs_us4*)(a.LO16 + (rb_ + 0 + 4 * lane));
+    RA0 = *(const hs_ro4*)(a.RO16 + (base_ + 0 + 4 * lane));
+    LGA0 = a.LG16[(rb_ + 0 + 4 * lane) >> 5];
+    RGA0 = a.RG16[(base_ + 0 + 4 * lane) >> 5]; RHA0 = a.RG16[((base_ + 0 + 4 * lane) + 3) >> 5];
     C8A0 = *(const hs_c8x4*)(a.c8 + (base_ + 0 + 4 * lane));
     C9A0 = *(const hs_c9x4*)(a.c9 + (base_ + 0 + 4 * lane));
-    LA1 = *(const hs_v4u*)(a.RK0 + (rb_ + 256 + 4 * lane));
-    RA1 = *(const hs_rk4*)(a.c8 + (base_ + 256 + 4 * lane));
-    M0A1 = *(const hs_us4*)(a.RMX1 + (rb_ + 256 + 4 * lane));
+    LA1 = *(const hs_us4*)(a.LO16 + (rb_ + 256 + 4 * lane));
+    RA1 = *(const hs_ro4*)(a.RO16 + (base_ + 256 + 4 * lane));
+    LGA1 = a.LG16[(rb_ + 256 + 4 * lane) >> 5];
+    RGA1 = a.RG16[(base_ + 256 + 4 * lane) >> 5]; RHA1 = a.RG16[((base_ + 256 + 4 * lane) + 3) >> 5];
     C8A1 = *(const hs_c8x4*)(a.c8 + (base_ + 256 + 4 * lane));
     C9A1 = *(const hs_c9x4*)(a.c9 + (base_ + 256 + 4 * lane));
     for (;;) {
       {
         const int rb_ = (nb + 2) << 8;
         const int base_ = gbase >= 0 ? gbase + 512 : s0 + (rb_ - lr0);
-        const bool f_ = (nb + 2) + 2 <= bend && rb_ >= lr0 && rb_ + 512 <= lr1 && rb_ + 512 <= NR && (i64)rb_ + 512 <= nxt0 && base_ >= s0 && base_ + 512 <= s1;
+        const bool f_ = slow_ == 0 && (nb + 2) + 2 <= bend && rb_ >= lr0 && rb_ + 512 <= lr1 && rb_ + 512 <= NR && (i64)rb_ + 512 <= nxt0 && base_ >= s0 && base_ + 512 <= s1;
         const int nr_ = f_ ? rb_ : (nb << 8), nj_ = f_ ? base_ : pbA;
         pbB = nj_;
-        LB0 = *(const hs_v4u*)(a.RK0 + (nr_ + 0 + 4 * lane));
-        RB0 = *(const hs_rk4*)(a.c8 + (nj_ + 0 + 4 * lane));
-        M0B0 = *(const hs_us4*)(a.RMX1 + (nr_ + 0 + 4 * lane));
+        LB0 = *(const hs_us4*)(a.LO16 + (nr_ + 0 + 4 * lane));
+        RB0 = *(const hs_ro4*)(a.RO16 + (nj_ + 0 + 4 * lane));
+        LGB0 = a.LG16[(nr_ + 0 + 4 * lane) >> 5];
+        RGB0 = a.RG16[(nj_ + 0 + 4 * lane) >> 5]; RHB0 = a.RG16[((nj_ + 0 + 4 * lane) + 3) >> 5];
         C8B0 = *(const hs_c8x4*)(a.c8 + (nj_ + 0 + 4 * lane));
         C9B0 = *(const hs_c9x4*)(a.c9 + (nj_ + 0 + 4 * lane));
-        LB1 = *(const hs_v4u*)(a.RK0 + (nr_ + 256 + 4 * lane));
-        RB1 = *(const hs_rk4*)(a.c8 + (nj_ + 256 + 4 * lane));
-        M0B1 = *(const hs_us4*)(a.RMX1 + (nr_ + 256 + 4 * lane));
+        LB1 = *(const hs_us4*)(a.LO16 + (nr_ + 256 + 4 * lane));
+        RB1 = *(const hs_ro4*)(a.RO16 + (nj_ + 256 + 4 * lane));
+        LGB1 = a.LG16[(nr_ + 256 + 4 * lane) >> 5];
+        RGB1 = a.RG16[(nj_ + 256 + 4 * lane) >> 5]; RHB1 = a.RG16[((nj_ + 256 + 4 * lane) + 3) >> 5];
         C8B1 = *(const hs_c8x4*)(a.c8 + (nj_ + 256 + 4 * lane));
         C9B1 = *(const hs_c9x4*)(a.c9 + (nj_ + 256 + 4 * lane));
+        if (__ballot(LGA0 == (int)0x80000000 || RGA0 == (int)0x80000000 || RHA0 == (int)0x80000000 || LGA1 == (int)0x80000000 || RGA1 == (int)0x80000000 || RHA1 == (int)0x80000000) != 0ull) { slow_ = 2; __builtin_amdgcn_s_waitcnt(0x0F70); break; }
         int nx_ = -1;
         { unsigned pk_ = 0u;
           { const int jA0_0 = pbA + 0 + 4 * lane;
           const int a0_A0_0 = s0, a1_A0_0 = s1; const bool actA0_0 = true;
-          const unsigned keyA0_0 = LA0[0] + (unsigned)a.KOF;
-          const unsigned kA0_0 = IMGV(RA0[0]);
-          const int bm0_A0_0 = (int)M0A0[0];
+          const unsigned keyA0_0 = (unsigned)LGA0 + (unsigned)LA0[0] + (unsigned)a.KOF;
+          const unsigned kA0_0 = IMGV((int)((unsigned)((((pbA + 0 + 4 * lane) & 31) + 0) < 32 ? RGA0 : RHA0) + (unsigned)RA0[0]));
           const int r8_gA0_0 = (int)C8A0[0];
           const long long x8_gA0_0 = (long long)(a.B8 + (i64)C8A0[0]);
           const int r9_gA0_0 = (int)C9A0[0];
@@ -348,14 +355,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hA0_0 = (int)(a.B9 + (i64)w9_hA0_0);
             tgA0_0 = ((hitA0_0) && ((true)) && ((true)) && ((true && (r9_hA0_0 >= (int)a.CL4 && r9_hA0_0 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgA0_0 = ((bm0_A0_0 >= hs_c20(a.CL1) + 32768)) ? tgA0_0 : 0u;
           pk_ |= (tgA0_0 & 1u) << 0;
           }
           { const int jA0_1 = pbA + 1 + 4 * lane;
           const int a0_A0_1 = s0, a1_A0_1 = s1; const bool actA0_1 = true;
-          const unsigned keyA0_1 = LA0[1] + (unsigned)a.KOF;
-          const unsigned kA0_1 = IMGV(RA0[1]);
-          const int bm0_A0_1 = (int)M0A0[1];
+          const unsigned keyA0_1 = (unsigned)LGA0 + (unsigned)LA0[1] + (unsigned)a.KOF;
+          const unsigned kA0_1 = IMGV((int)((unsigned)((((pbA + 0 + 4 * lane) & 31) + 1) < 32 ? RGA0 : RHA0) + (unsigned)RA0[1]));
           const int r8_gA0_1 = (int)C8A0[1];
           const long long x8_gA0_1 = (long long)(a.B8 + (i64)C8A0[1]);
           const int r9_gA0_1 = (int)C9A0[1];
@@ -388,14 +393,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hA0_1 = (int)(a.B9 + (i64)w9_hA0_1);
             tgA0_1 = ((hitA0_1) && ((true)) && ((true)) && ((true && (r9_hA0_1 >= (int)a.CL4 && r9_hA0_1 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgA0_1 = ((bm0_A0_1 >= hs_c20(a.CL1) + 32768)) ? tgA0_1 : 0u;
           pk_ |= (tgA0_1 & 1u) << 1;
           }
           { const int jA0_2 = pbA + 2 + 4 * lane;
           const int a0_A0_2 = s0, a1_A0_2 = s1; const bool actA0_2 = true;
-          const unsigned keyA0_2 = LA0[2] + (unsigned)a.KOF;
-          const unsigned kA0_2 = IMGV(RA0[2]);
-          const int bm0_A0_2 = (int)M0A0[2];
+          const unsigned keyA0_2 = (unsigned)LGA0 + (unsigned)LA0[2] + (unsigned)a.KOF;
+          const unsigned kA0_2 = IMGV((int)((unsigned)((((pbA + 0 + 4 * lane) & 31) + 2) < 32 ? RGA0 : RHA0) + (unsigned)RA0[2]));
           const int r8_gA0_2 = (int)C8A0[2];
           const long long x8_gA0_2 = (long long)(a.B8 + (i64)C8A0[2]);
           const int r9_gA0_2 = (int)C9A0[2];
@@ -428,14 +431,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hA0_2 = (int)(a.B9 + (i64)w9_hA0_2);
             tgA0_2 = ((hitA0_2) && ((true)) && ((true)) && ((true && (r9_hA0_2 >= (int)a.CL4 && r9_hA0_2 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgA0_2 = ((bm0_A0_2 >= hs_c20(a.CL1) + 32768)) ? tgA0_2 : 0u;
           pk_ |= (tgA0_2 & 1u) << 2;
           }
           { const int jA0_3 = pbA + 3 + 4 * lane;
           const int a0_A0_3 = s0, a1_A0_3 = s1; const bool actA0_3 = true;
-          const unsigned keyA0_3 = LA0[3] + (unsigned)a.KOF;
-          const unsigned kA0_3 = IMGV(RA0[3]);
-          const int bm0_A0_3 = (int)M0A0[3];
+          const unsigned keyA0_3 = (unsigned)LGA0 + (unsigned)LA0[3] + (unsigned)a.KOF;
+          const unsigned kA0_3 = IMGV((int)((unsigned)((((pbA + 0 + 4 * lane) & 31) + 3) < 32 ? RGA0 : RHA0) + (unsigned)RA0[3]));
           const int r8_gA0_3 = (int)C8A0[3];
           const long long x8_gA0_3 = (long long)(a.B8 + (i64)C8A0[3]);
           const int r9_gA0_3 = (int)C9A0[3];
@@ -468,7 +469,6 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hA0_3 = (int)(a.B9 + (i64)w9_hA0_3);
             tgA0_3 = ((hitA0_3) && ((true)) && ((true)) && ((true && (r9_hA0_3 >= (int)a.CL4 && r9_hA0_3 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgA0_3 = ((bm0_A0_3 >= hs_c20(a.CL1) + 32768)) ? tgA0_3 : 0u;
           pk_ |= (tgA0_3 & 1u) << 3;
           }
           pk_ <<= (unsigned)(4 * (lane & 7));
@@ -480,9 +480,8 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
         { unsigned pk_ = 0u;
           { const int jA1_0 = pbA + 256 + 4 * lane;
           const int a0_A1_0 = s0, a1_A1_0 = s1; const bool actA1_0 = true;
-          const unsigned keyA1_0 = LA1[0] + (unsigned)a.KOF;
-          const unsigned kA1_0 = IMGV(RA1[0]);
-          const int bm0_A1_0 = (int)M0A1[0];
+          const unsigned keyA1_0 = (unsigned)LGA1 + (unsigned)LA1[0] + (unsigned)a.KOF;
+          const unsigned kA1_0 = IMGV((int)((unsigned)((((pbA + 256 + 4 * lane) & 31) + 0) < 32 ? RGA1 : RHA1) + (unsigned)RA1[0]));
           const int r8_gA1_0 = (int)C8A1[0];
           const long long x8_gA1_0 = (long long)(a.B8 + (i64)C8A1[0]);
           const int r9_gA1_0 = (int)C9A1[0];
@@ -515,14 +514,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hA1_0 = (int)(a.B9 + (i64)w9_hA1_0);
             tgA1_0 = ((hitA1_0) && ((true)) && ((true)) && ((true && (r9_hA1_0 >= (int)a.CL4 && r9_hA1_0 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgA1_0 = ((bm0_A1_0 >= hs_c20(a.CL1) + 32768)) ? tgA1_0 : 0u;
           pk_ |= (tgA1_0 & 1u) << 0;
           }
           { const int jA1_1 = pbA + 257 + 4 * lane;
           const int a0_A1_1 = s0, a1_A1_1 = s1; const bool actA1_1 = true;
-          const unsigned keyA1_1 = LA1[1] + (unsigned)a.KOF;
-          const unsigned kA1_1 = IMGV(RA1[1]);
-          const int bm0_A1_1 = (int)M0A1[1];
+          const unsigned keyA1_1 = (unsigned)LGA1 + (unsigned)LA1[1] + (unsigned)a.KOF;
+          const unsigned kA1_1 = IMGV((int)((unsigned)((((pbA + 256 + 4 * lane) & 31) + 1) < 32 ? RGA1 : RHA1) + (unsigned)RA1[1]));
           const int r8_gA1_1 = (int)C8A1[1];
           const long long x8_gA1_1 = (long long)(a.B8 + (i64)C8A1[1]);
           const int r9_gA1_1 = (int)C9A1[1];
@@ -555,14 +552,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hA1_1 = (int)(a.B9 + (i64)w9_hA1_1);
             tgA1_1 = ((hitA1_1) && ((true)) && ((true)) && ((true && (r9_hA1_1 >= (int)a.CL4 && r9_hA1_1 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgA1_1 = ((bm0_A1_1 >= hs_c20(a.CL1) + 32768)) ? tgA1_1 : 0u;
           pk_ |= (tgA1_1 & 1u) << 1;
           }
           { const int jA1_2 = pbA + 258 + 4 * lane;
           const int a0_A1_2 = s0, a1_A1_2 = s1; const bool actA1_2 = true;
-          const unsigned keyA1_2 = LA1[2] + (unsigned)a.KOF;
-          const unsigned kA1_2 = IMGV(RA1[2]);
-          const int bm0_A1_2 = (int)M0A1[2];
+          const unsigned keyA1_2 = (unsigned)LGA1 + (unsigned)LA1[2] + (unsigned)a.KOF;
+          const unsigned kA1_2 = IMGV((int)((unsigned)((((pbA + 256 + 4 * lane) & 31) + 2) < 32 ? RGA1 : RHA1) + (unsigned)RA1[2]));
           const int r8_gA1_2 = (int)C8A1[2];
           const long long x8_gA1_2 = (long long)(a.B8 + (i64)C8A1[2]);
           const int r9_gA1_2 = (int)C9A1[2];
@@ -595,14 +590,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hA1_2 = (int)(a.B9 + (i64)w9_hA1_2);
             tgA1_2 = ((hitA1_2) && ((true)) && ((true)) && ((true && (r9_hA1_2 >= (int)a.CL4 && r9_hA1_2 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgA1_2 = ((bm0_A1_2 >= hs_c20(a.CL1) + 32768)) ? tgA1_2 : 0u;
           pk_ |= (tgA1_2 & 1u) << 2;
           }
           { const int jA1_3 = pbA + 259 + 4 * lane;
           const int a0_A1_3 = s0, a1_A1_3 = s1; const bool actA1_3 = true;
-          const unsigned keyA1_3 = LA1[3] + (unsigned)a.KOF;
-          const unsigned kA1_3 = IMGV(RA1[3]);
-          const int bm0_A1_3 = (int)M0A1[3];
+          const unsigned keyA1_3 = (unsigned)LGA1 + (unsigned)LA1[3] + (unsigned)a.KOF;
+          const unsigned kA1_3 = IMGV((int)((unsigned)((((pbA + 256 + 4 * lane) & 31) + 3) < 32 ? RGA1 : RHA1) + (unsigned)RA1[3]));
           const int r8_gA1_3 = (int)C8A1[3];
           const long long x8_gA1_3 = (long long)(a.B8 + (i64)C8A1[3]);
           const int r9_gA1_3 = (int)C9A1[3];
@@ -635,7 +628,6 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hA1_3 = (int)(a.B9 + (i64)w9_hA1_3);
             tgA1_3 = ((hitA1_3) && ((true)) && ((true)) && ((true && (r9_hA1_3 >= (int)a.CL4 && r9_hA1_3 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgA1_3 = ((bm0_A1_3 >= hs_c20(a.CL1) + 32768)) ? tgA1_3 : 0u;
           pk_ |= (tgA1_3 & 1u) << 3;
           nx_ = hitA1_3 ? mA1_3 + 1 : -1;
           }
@@ -652,26 +644,28 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
       {
         const int rb_ = (nb + 2) << 8;
         const int base_ = gbase >= 0 ? gbase + 512 : s0 + (rb_ - lr0);
-        const bool f_ = (nb + 2) + 2 <= bend && rb_ >= lr0 && rb_ + 512 <= lr1 && rb_ + 512 <= NR && (i64)rb_ + 512 <= nxt0 && base_ >= s0 && base_ + 512 <= s1;
+        const bool f_ = slow_ == 0 && (nb + 2) + 2 <= bend && rb_ >= lr0 && rb_ + 512 <= lr1 && rb_ + 512 <= NR && (i64)rb_ + 512 <= nxt0 && base_ >= s0 && base_ + 512 <= s1;
         const int nr_ = f_ ? rb_ : (nb << 8), nj_ = f_ ? base_ : pbB;
         pbA = nj_;
-        LA0 = *(const hs_v4u*)(a.RK0 + (nr_ + 0 + 4 * lane));
-        RA0 = *(const hs_rk4*)(a.c8 + (nj_ + 0 + 4 * lane));
-        M0A0 = *(const hs_us4*)(a.RMX1 + (nr_ + 0 + 4 * lane));
+        LA0 = *(const hs_us4*)(a.LO16 + (nr_ + 0 + 4 * lane));
+        RA0 = *(const hs_ro4*)(a.RO16 + (nj_ + 0 + 4 * lane));
+        LGA0 = a.LG16[(nr_ + 0 + 4 * lane) >> 5];
+        RGA0 = a.RG16[(nj_ + 0 + 4 * lane) >> 5]; RHA0 = a.RG16[((nj_ + 0 + 4 * lane) + 3) >> 5];
         C8A0 = *(const hs_c8x4*)(a.c8 + (nj_ + 0 + 4 * lane));
         C9A0 = *(const hs_c9x4*)(a.c9 + (nj_ + 0 + 4 * lane));
-        LA1 = *(const hs_v4u*)(a.RK0 + (nr_ + 256 + 4 * lane));
-        RA1 = *(const hs_rk4*)(a.c8 + (nj_ + 256 + 4 * lane));
-        M0A1 = *(const hs_us4*)(a.RMX1 + (nr_ + 256 + 4 * lane));
+        LA1 = *(const hs_us4*)(a.LO16 + (nr_ + 256 + 4 * lane));
+        RA1 = *(const hs_ro4*)(a.RO16 + (nj_ + 256 + 4 * lane));
+        LGA1 = a.LG16[(nr_ + 256 + 4 * lane) >> 5];
+        RGA1 = a.RG16[(nj_ + 256 + 4 * lane) >> 5]; RHA1 = a.RG16[((nj_ + 256 + 4 * lane) + 3) >> 5];
         C8A1 = *(const hs_c8x4*)(a.c8 + (nj_ + 256 + 4 * lane));
         C9A1 = *(const hs_c9x4*)(a.c9 + (nj_ + 256 + 4 * lane));
+        if (__ballot(LGB0 == (int)0x80000000 || RGB0 == (int)0x80000000 || RHB0 == (int)0x80000000 || LGB1 == (int)0x80000000 || RGB1 == (int)0x80000000 || RHB1 == (int)0x80000000) != 0ull) { slow_ = 2; __builtin_amdgcn_s_waitcnt(0x0F70); break; }
         int nx_ = -1;
         { unsigned pk_ = 0u;
           { const int jB0_0 = pbB + 0 + 4 * lane;
           const int a0_B0_0 = s0, a1_B0_0 = s1; const bool actB0_0 = true;
-          const unsigned keyB0_0 = LB0[0] + (unsigned)a.KOF;
-          const unsigned kB0_0 = IMGV(RB0[0]);
-          const int bm0_B0_0 = (int)M0B0[0];
+          const unsigned keyB0_0 = (unsigned)LGB0 + (unsigned)LB0[0] + (unsigned)a.KOF;
+          const unsigned kB0_0 = IMGV((int)((unsigned)((((pbB + 0 + 4 * lane) & 31) + 0) < 32 ? RGB0 : RHB0) + (unsigned)RB0[0]));
           const int r8_gB0_0 = (int)C8B0[0];
           const long long x8_gB0_0 = (long long)(a.B8 + (i64)C8B0[0]);
           const int r9_gB0_0 = (int)C9B0[0];
@@ -704,14 +698,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hB0_0 = (int)(a.B9 + (i64)w9_hB0_0);
             tgB0_0 = ((hitB0_0) && ((true)) && ((true)) && ((true && (r9_hB0_0 >= (int)a.CL4 && r9_hB0_0 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgB0_0 = ((bm0_B0_0 >= hs_c20(a.CL1) + 32768)) ? tgB0_0 : 0u;
           pk_ |= (tgB0_0 & 1u) << 0;
           }
           { const int jB0_1 = pbB + 1 + 4 * lane;
           const int a0_B0_1 = s0, a1_B0_1 = s1; const bool actB0_1 = true;
-          const unsigned keyB0_1 = LB0[1] + (unsigned)a.KOF;
-          const unsigned kB0_1 = IMGV(RB0[1]);
-          const int bm0_B0_1 = (int)M0B0[1];
+          const unsigned keyB0_1 = (unsigned)LGB0 + (unsigned)LB0[1] + (unsigned)a.KOF;
+          const unsigned kB0_1 = IMGV((int)((unsigned)((((pbB + 0 + 4 * lane) & 31) + 1) < 32 ? RGB0 : RHB0) + (unsigned)RB0[1]));
           const int r8_gB0_1 = (int)C8B0[1];
           const long long x8_gB0_1 = (long long)(a.B8 + (i64)C8B0[1]);
           const int r9_gB0_1 = (int)C9B0[1];
@@ -744,14 +736,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hB0_1 = (int)(a.B9 + (i64)w9_hB0_1);
             tgB0_1 = ((hitB0_1) && ((true)) && ((true)) && ((true && (r9_hB0_1 >= (int)a.CL4 && r9_hB0_1 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgB0_1 = ((bm0_B0_1 >= hs_c20(a.CL1) + 32768)) ? tgB0_1 : 0u;
           pk_ |= (tgB0_1 & 1u) << 1;
           }
           { const int jB0_2 = pbB + 2 + 4 * lane;
           const int a0_B0_2 = s0, a1_B0_2 = s1; const bool actB0_2 = true;
-          const unsigned keyB0_2 = LB0[2] + (unsigned)a.KOF;
-          const unsigned kB0_2 = IMGV(RB0[2]);
-          const int bm0_B0_2 = (int)M0B0[2];
+          const unsigned keyB0_2 = (unsigned)LGB0 + (unsigned)LB0[2] + (unsigned)a.KOF;
+          const unsigned kB0_2 = IMGV((int)((unsigned)((((pbB + 0 + 4 * lane) & 31) + 2) < 32 ? RGB0 : RHB0) + (unsigned)RB0[2]));
           const int r8_gB0_2 = (int)C8B0[2];
           const long long x8_gB0_2 = (long long)(a.B8 + (i64)C8B0[2]);
           const int r9_gB0_2 = (int)C9B0[2];
@@ -784,14 +774,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hB0_2 = (int)(a.B9 + (i64)w9_hB0_2);
             tgB0_2 = ((hitB0_2) && ((true)) && ((true)) && ((true && (r9_hB0_2 >= (int)a.CL4 && r9_hB0_2 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgB0_2 = ((bm0_B0_2 >= hs_c20(a.CL1) + 32768)) ? tgB0_2 : 0u;
           pk_ |= (tgB0_2 & 1u) << 2;
           }
           { const int jB0_3 = pbB + 3 + 4 * lane;
           const int a0_B0_3 = s0, a1_B0_3 = s1; const bool actB0_3 = true;
-          const unsigned keyB0_3 = LB0[3] + (unsigned)a.KOF;
-          const unsigned kB0_3 = IMGV(RB0[3]);
-          const int bm0_B0_3 = (int)M0B0[3];
+          const unsigned keyB0_3 = (unsigned)LGB0 + (unsigned)LB0[3] + (unsigned)a.KOF;
+          const unsigned kB0_3 = IMGV((int)((unsigned)((((pbB + 0 + 4 * lane) & 31) + 3) < 32 ? RGB0 : RHB0) + (unsigned)RB0[3]));
           const int r8_gB0_3 = (int)C8B0[3];
           const long long x8_gB0_3 = (long long)(a.B8 + (i64)C8B0[3]);
           const int r9_gB0_3 = (int)C9B0[3];
@@ -824,7 +812,6 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hB0_3 = (int)(a.B9 + (i64)w9_hB0_3);
             tgB0_3 = ((hitB0_3) && ((true)) && ((true)) && ((true && (r9_hB0_3 >= (int)a.CL4 && r9_hB0_3 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgB0_3 = ((bm0_B0_3 >= hs_c20(a.CL1) + 32768)) ? tgB0_3 : 0u;
           pk_ |= (tgB0_3 & 1u) << 3;
           }
           pk_ <<= (unsigned)(4 * (lane & 7));
@@ -836,9 +823,8 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
         { unsigned pk_ = 0u;
           { const int jB1_0 = pbB + 256 + 4 * lane;
           const int a0_B1_0 = s0, a1_B1_0 = s1; const bool actB1_0 = true;
-          const unsigned keyB1_0 = LB1[0] + (unsigned)a.KOF;
-          const unsigned kB1_0 = IMGV(RB1[0]);
-          const int bm0_B1_0 = (int)M0B1[0];
+          const unsigned keyB1_0 = (unsigned)LGB1 + (unsigned)LB1[0] + (unsigned)a.KOF;
+          const unsigned kB1_0 = IMGV((int)((unsigned)((((pbB + 256 + 4 * lane) & 31) + 0) < 32 ? RGB1 : RHB1) + (unsigned)RB1[0]));
           const int r8_gB1_0 = (int)C8B1[0];
           const long long x8_gB1_0 = (long long)(a.B8 + (i64)C8B1[0]);
           const int r9_gB1_0 = (int)C9B1[0];
@@ -871,14 +857,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hB1_0 = (int)(a.B9 + (i64)w9_hB1_0);
             tgB1_0 = ((hitB1_0) && ((true)) && ((true)) && ((true && (r9_hB1_0 >= (int)a.CL4 && r9_hB1_0 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgB1_0 = ((bm0_B1_0 >= hs_c20(a.CL1) + 32768)) ? tgB1_0 : 0u;
           pk_ |= (tgB1_0 & 1u) << 0;
           }
           { const int jB1_1 = pbB + 257 + 4 * lane;
           const int a0_B1_1 = s0, a1_B1_1 = s1; const bool actB1_1 = true;
-          const unsigned keyB1_1 = LB1[1] + (unsigned)a.KOF;
-          const unsigned kB1_1 = IMGV(RB1[1]);
-          const int bm0_B1_1 = (int)M0B1[1];
+          const unsigned keyB1_1 = (unsigned)LGB1 + (unsigned)LB1[1] + (unsigned)a.KOF;
+          const unsigned kB1_1 = IMGV((int)((unsigned)((((pbB + 256 + 4 * lane) & 31) + 1) < 32 ? RGB1 : RHB1) + (unsigned)RB1[1]));
           const int r8_gB1_1 = (int)C8B1[1];
           const long long x8_gB1_1 = (long long)(a.B8 + (i64)C8B1[1]);
           const int r9_gB1_1 = (int)C9B1[1];
@@ -911,14 +895,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hB1_1 = (int)(a.B9 + (i64)w9_hB1_1);
             tgB1_1 = ((hitB1_1) && ((true)) && ((true)) && ((true && (r9_hB1_1 >= (int)a.CL4 && r9_hB1_1 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgB1_1 = ((bm0_B1_1 >= hs_c20(a.CL1) + 32768)) ? tgB1_1 : 0u;
           pk_ |= (tgB1_1 & 1u) << 1;
           }
           { const int jB1_2 = pbB + 258 + 4 * lane;
           const int a0_B1_2 = s0, a1_B1_2 = s1; const bool actB1_2 = true;
-          const unsigned keyB1_2 = LB1[2] + (unsigned)a.KOF;
-          const unsigned kB1_2 = IMGV(RB1[2]);
-          const int bm0_B1_2 = (int)M0B1[2];
+          const unsigned keyB1_2 = (unsigned)LGB1 + (unsigned)LB1[2] + (unsigned)a.KOF;
+          const unsigned kB1_2 = IMGV((int)((unsigned)((((pbB + 256 + 4 * lane) & 31) + 2) < 32 ? RGB1 : RHB1) + (unsigned)RB1[2]));
           const int r8_gB1_2 = (int)C8B1[2];
           const long long x8_gB1_2 = (long long)(a.B8 + (i64)C8B1[2]);
           const int r9_gB1_2 = (int)C9B1[2];
@@ -951,14 +933,12 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hB1_2 = (int)(a.B9 + (i64)w9_hB1_2);
             tgB1_2 = ((hitB1_2) && ((true)) && ((true)) && ((true && (r9_hB1_2 >= (int)a.CL4 && r9_hB1_2 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgB1_2 = ((bm0_B1_2 >= hs_c20(a.CL1) + 32768)) ? tgB1_2 : 0u;
           pk_ |= (tgB1_2 & 1u) << 2;
           }
           { const int jB1_3 = pbB + 259 + 4 * lane;
           const int a0_B1_3 = s0, a1_B1_3 = s1; const bool actB1_3 = true;
-          const unsigned keyB1_3 = LB1[3] + (unsigned)a.KOF;
-          const unsigned kB1_3 = IMGV(RB1[3]);
-          const int bm0_B1_3 = (int)M0B1[3];
+          const unsigned keyB1_3 = (unsigned)LGB1 + (unsigned)LB1[3] + (unsigned)a.KOF;
+          const unsigned kB1_3 = IMGV((int)((unsigned)((((pbB + 256 + 4 * lane) & 31) + 3) < 32 ? RGB1 : RHB1) + (unsigned)RB1[3]));
           const int r8_gB1_3 = (int)C8B1[3];
           const long long x8_gB1_3 = (long long)(a.B8 + (i64)C8B1[3]);
           const int r9_gB1_3 = (int)C9B1[3];
@@ -991,7 +971,6 @@ extern "C" __global__ __launch_bounds__(256) void hs_jit_run_tags2(Args a) {
             const int x9_hB1_3 = (int)(a.B9 + (i64)w9_hB1_3);
             tgB1_3 = ((hitB1_3) && ((true)) && ((true)) && ((true && (r9_hB1_3 >= (int)a.CL4 && r9_hB1_3 <= (int)a.CH4))) ? 1u : 0u);
           }
-          tgB1_3 = ((bm0_B1_3 >= hs_c20(a.CL1) + 32768)) ? tgB1_3 : 0u;
           pk_ |= (tgB1_3 & 1u) << 3;
           nx_ = hitB1_3 ? mB1_3 + 1 : -1;
           }

@@ -116,6 +116,43 @@ def group16(x, max_wide: float):
     return codes.contiguous(), gbase.contiguous()
 
 
+GROUP32 = 32
+
+
+def group16_32(x, max_wide: float):
+    """(offsets16, gbase) of a sorted-within-buckets int32 code array ``x`` over 32-element
+    groups - the form the four-run phase 1 of the run-keyed join reads (``jit_runs``,
+    ``rt2_k16``): ``x[i] == gbase[i >> 5] + offset[i]`` outside wide groups (``WIDE_GROUP``
+    base, zero offsets, as in ``group16``), both arrays padded to a multiple of 256 elements
+    (zero offsets; a group of padding only is wide).  One native pass on the device
+    (``ops.kernels.group16_32``), the same arrays from PyTorch on the host.  None when more than
+    ``max_wide`` of the real groups are wide.  (TPC-H SF100 keys lie ~800 apart inside a
+    bucket: 1.3 % of 64-key groups span 2^16, none of 32-key groups did.)"""
+    import torch
+    n = x.numel()
+    if n == 0:
+        return None
+    ng = (n + GROUP32 - 1) // GROUP32
+    if x.is_cuda:
+        from ..ops import kernels as K
+        off, gbase = K.group16_32(x.contiguous())
+    else:
+        npad = max(256, (n + 255) // 256 * 256)
+        xl = x.long()
+        g = torch.cat([xl, xl[-1:].expand(ng * GROUP32 - n)]).view(ng, GROUP32)
+        gmin = g.amin(dim=1)
+        wide = ((g.amax(dim=1) - gmin) >= (1 << 16)) | (gmin == WIDE_GROUP)
+        d = torch.where(wide.unsqueeze(1), torch.zeros_like(g), g - gmin.unsqueeze(1))
+        d = d.reshape(-1)[:n]
+        off = torch.zeros(npad, dtype=torch.int16)
+        off[:n] = torch.where(d >= (1 << 15), d - (1 << 16), d).to(torch.int16)  # uint16 bits
+        gbase = torch.full((npad // GROUP32,), WIDE_GROUP, dtype=torch.int32)
+        gbase[:ng] = torch.where(wide, torch.full_like(gmin, WIDE_GROUP), gmin).to(torch.int32)
+    if int((gbase[:ng] == WIDE_GROUP).sum().item()) > max_wide * ng:
+        return None
+    return off, gbase
+
+
 class RunCompact(Compact):
     """Run-length form of a bucket-sorted 32-bit integer key (csrc/kernels/key_runs.hip): a
     covering index is sorted by its indexed columns inside each bucket, so its leading key is a
@@ -128,7 +165,7 @@ class RunCompact(Compact):
 
     ~1.2 instead of 4 bytes per row at 4 rows per run.  ``codes`` stays the parent's full 32-bit
     codes, so every other reader (spans, aggregate tails, group keys) is unchanged."""
-    __slots__ = ("runkeys", "gmask", "gruns", "nruns", "k16")
+    __slots__ = ("runkeys", "gmask", "gruns", "nruns", "k16", "k32")
 
     def __init__(self, parent: Compact, runkeys, gmask, gruns):
         super().__init__(parent.codes, parent.width, parent.base, parent.scale,
@@ -136,10 +173,25 @@ class RunCompact(Compact):
         self.runkeys, self.gmask, self.gruns = runkeys, gmask, gruns
         self.nruns = int(runkeys.numel())
         self.k16 = False
+        self.k32 = False
 
-    def keys16(self, max_wide: float = 0.1):
-        """(runkeys16, group bases) of the run keys, per 64-run group (``group16``; computed
-        once): the run-keyed join's phase 1 reads 2 instead of 4 bytes per run."""
+    def keys16(self, max_wide: float = 0.1, group: int = GROUP_ROWS):
+        """(runkeys16, group bases) of the run keys, per ``group``-run group (computed once per
+        group size): the run-keyed join's phase 1 reads 2 instead of 4 bytes per run.  64:
+        ``group16``; 32: ``group16_32`` (padded, built natively on the device).  The result of
+        the first call per group size is kept, refusal included: ``max_wide`` of a later call is
+        not looked at (each form has one caller with one threshold)."""
+        if group == GROUP32:
+            if self.k32 is False:
+                self.k32 = group16_32(self.runkeys, max_wide)
+                if self.k32 is not None and self.runkeys.is_cuda:
+                    # derived by a lowered join, like its per-run bounds: counted against the
+                    # table caches' budgets while it lives, not in ``extra_bytes``
+                    from .device_cache import track_derived
+                    for t in self.k32:
+                        track_derived(t)
+            return self.k32
+        assert group == GROUP_ROWS
         if self.k16 is False:
             self.k16 = group16(self.runkeys, max_wide)
         return self.k16

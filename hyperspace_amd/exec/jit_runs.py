@@ -32,7 +32,14 @@ drops its row stream - the 0.9 GB 12-bit ``l_shipdate`` copy - and gathers the t
 tagged runs' rows only (1.35 instead of 1.27 128-byte lines per 100 left rows): ~1.0 GB
 instead of ~1.9.  The step moves ~3.45 GB in 0.68 ms (5.1 TB/s): phase 1 369 us (4.9 TB/s),
 phase 2 256 us - a gather, not a stream, so below the streaming rate
-(``profiles/run_prune.txt``).  The two-phase
+(``profiles/run_prune.txt``).
+
+With 16-bit key offsets (RT2_K16, ``tags2_k16``; the default) the four-run phase 1 reads both
+key columns as uint16 offsets from the bases of 32-element groups (``encoding.group16_32``,
+built natively by ``hs_group16_32``; exact: code = base + offset): 8.25 instead of 12 B per run,
+1.24 GB, and the step moves ~2.9 GB in 0.585 ms (5.0 TB/s; phase 1 377 -> 264 us at 4.7 TB/s,
+``profiles/tags2_keys16.txt``).  The 32-bit arrays stay resident for the gallop and for stages
+that meet a wide group.  The two-phase
 form applies when no aggregate input comes from the right side, every right predicate reads
 only right columns, and a right-side group key (if any) has at most 255 groups."""
 from __future__ import annotations
@@ -50,7 +57,7 @@ _CFG = _KC.active()
 MJ_2P, RS_ITEMS = _CFG.mj_2p, _CFG.rs_items
 RT2_UNROLL, RT2_GRID, RT2_I32 = _CFG.rt2_unroll, _CFG.rt2_grid, _CFG.rt2_i32
 RT2_MATCH, RT2_COPY, RT2_LO16 = _CFG.rt2_match, _CFG.rt2_copy, _CFG.rt2_lo16
-RT2_WIDE, RT2_WIDE_GRID = _CFG.rt2_wide, _CFG.rt2_wide_grid
+RT2_WIDE, RT2_WIDE_GRID, RT2_K16 = _CFG.rt2_wide, _CFG.rt2_wide_grid, _CFG.rt2_k16
 RS_BITS, RS_BITS_GRID, RS_PACK = _CFG.rs_bits, _CFG.rs_bits_grid, _CFG.rs_pack
 RS_PIPE, RS_WALK, RS_LDS, RS_LUT = _CFG.rs_pipe, _CFG.rs_walk, _CFG.rs_lds, _CFG.rs_lut
 RS_PK16, RS_WAVES, RS_PACK12 = _CFG.rs_pk16, _CFG.rs_waves, _CFG.rs_pack12
@@ -109,14 +116,67 @@ def tags2_wide(p: NL.JoinParams, compacts, ix32: bool, mode: str = "") -> int:
     return 4
 
 
+# the share of a key column's 32-element groups that may be wide before its 16-bit form is
+# refused (``key_forms16``): a stage that meets a wide group falls back to the 64-run code
+K16_MAX_WIDE = 0.03
+
+
+def tags2_k16(p: NL.JoinParams, compacts, ix32: bool, mode: str = "") -> bool:
+    """Whether phase 1 of this join may read its two key columns as 16-bit offsets from
+    32-element group bases (RT2_K16): the four-run form in mode "" whose right key is a plain
+    32-bit compact code (not nullable, not already stored grouped: ``tags2_wide`` refuses
+    those) and whose left key has the run form.  The lowering still needs both derived forms
+    (``key_forms16``) before it picks the variant."""
+    if not RT2_K16 or RT2_LO16 or mode != "" or tags2_wide(p, compacts, ix32, mode) != 4:
+        return False
+    lc, rc = (compacts or {}).get(p.lkey), (compacts or {}).get(p.rkey)
+    return lc is not None and lc.signature() == (4, False, "runs") and \
+        rc is not None and rc.signature() == (4, False)
+
+
+# the right key's 16-bit form: id of its codes -> (weak reference to the codes, (offsets, bases)
+# or None).  Derived once per resident table, like the per-run bounds below, and dropped with the
+# codes (an evicted table's are not kept alive here); the left key's is kept on its RunCompact
+# (``keys16``).
+_KEYS16: dict = {}
+
+
+def key_forms16(runs, rc) -> Optional[tuple]:
+    """((left offsets, left bases), (right offsets, right bases)) of the run keys of ``runs``
+    and the right key compact ``rc`` over 32-element groups (``encoding.group16_32``), or None
+    when either side has more than K16_MAX_WIDE wide groups."""
+    from . import encoding as E
+    from .device_cache import track_derived
+    lf = runs.keys16(K16_MAX_WIDE, E.GROUP32)
+    if lf is None:
+        return None
+    import weakref
+    key = id(rc.codes)
+    hit = _KEYS16.get(key)
+    if hit is None or hit[0]() is not rc.codes:
+        rf = E.group16_32(rc.codes, K16_MAX_WIDE)
+        if rf is not None and rc.codes.is_cuda:
+            for t in rf:
+                track_derived(t)
+        hit = _KEYS16[key] = (weakref.ref(rc.codes), rf)
+        weakref.finalize(rc.codes, _drop_keys16, key, hit)
+    return None if hit[1] is None else (lf, hit[1])
+
+
+def _drop_keys16(key: int, entry: tuple) -> None:
+    if _KEYS16.get(key) is entry:       # (the id may have been reused by a live tensor)
+        del _KEYS16[key]
+
+
 def tags2_shape(p: NL.JoinParams, compacts, W: int, ix32: bool = False, mode: str = "",
-                prune: tuple = ()) -> tuple:
+                prune: tuple = (), k16: bool = False) -> tuple:
     cols = tuple(sorted((s, c) for s, c in J._col_specs(p, compacts).items()
                         if s >= SPLIT or s == p.lkey))
     preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
                    p.preds[k].group) for k in range(p.nlp, p.npreds))
     return ("run_tags2", cols, preds, p.nlp, p.lkey, p.rkey, _tags_grouped(p) and p.group_col,
             W, RT2_UNROLL, J.BLOCK, ix32, mode, tuple(prune),
+            bool(k16) and tags2_k16(p, compacts, ix32, mode),
             tags2_wide(p, compacts, ix32, mode))
 
 
@@ -173,7 +233,7 @@ def _tags_grouped(p: NL.JoinParams) -> bool:
 
 
 def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
-                  mode: str = "", prune: tuple = ()) -> J.Kernel:
+                  mode: str = "", prune: tuple = (), k16: bool = False) -> J.Kernel:
     """Phase 1, direct form: no tiles and no LDS.  Each wavefront owns a contiguous chunk of
     64-run groups of the left run list (so it owns whole 2W-word stretches of the tag bitmap
     and stores them without atomics).  Lane l of a group guesses the right row of its run: the
@@ -212,8 +272,19 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
     ``prune`` (``prune_plan``; mode ""): per listed left conjunct the run's bound - ``RMX<slot>``
     or ``RMN<slot>``, one uint16 per run (code + 32768, ``run_bounds``) - is loaded with the run
     key (the four-run form: one 8-byte load per lane) and the tag is cleared when the bound
-    fails the conjunct's code range [CL<k>, CH<k>]."""
+    fails the conjunct's code range [CL<k>, CH<k>].
+
+    ``k16`` (``tags2_k16``; the four-run form, mode ""): a fast stage reads both key columns as
+    uint16 offsets (``LO16`` per run, ``RO16`` per right row: one 8-byte load each per lane and
+    block) plus the bases of their 32-element groups (``LG16`` / ``RG16``: one dword for the
+    lane's four runs, two for its four right rows, which can straddle one group edge; the group
+    index comes from the run / guessed row, so nothing depends on a load) and rebuilds
+    code = base + offset for the eight keys - 8.25 instead of 12 B per run with one bound.
+    Compare, key frame, miss path and tags are the 32-bit form's.  A stage in which any lane
+    loaded a ``WIDE_GROUP`` base (a ballot after the loads) leaves the pipeline and takes the
+    64-run code on the 32-bit arrays, as the gallop always does."""
     assert not prune or mode == ""
+    assert not k16 or tags2_k16(p, compacts, ix32, mode)
     IX = "int" if ix32 else "i64"  # noqa: N806 — run / right-row index type
     wide = tags2_wide(p, compacts, ix32, mode)
     args = J.Args()
@@ -242,6 +313,11 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
         bounds.append(args.add("p", f"RMX{sl}" if mx else f"RMN{sl}", "const unsigned short*"))
         lit = args.add("q", f"CL{k}" if mx else f"CH{k}", "long long")
         btests.append(f"bm{i}_@U@ {'>=' if mx else '<='} hs_c20({lit}) + 32768")
+    if k16:
+        for n in ("LO16", "RO16"):
+            args.add("p", n, "const unsigned short*")
+        for n in ("LG16", "RG16"):
+            args.add("p", n, "const int*")
     lo16 = mode in ("lo16", "lo16prep")
     if lo16:
         assert ix32
@@ -457,7 +533,8 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
     if wide == 4:
         del b[:]
         return _gen_tags2_wide(p, args, cols, b, group, resolve,
-                               image(g.decode(rk, "w_"), False), img, imgf, W, mode, bounds)
+                               image(g.decode(rk, "w_"), False), img, imgf, W, mode, bounds,
+                               k16)
     iteration(True, ind)
     b.append("    } else {   // a range starts inside this iteration's groups")
     iteration(False, ind)
@@ -470,12 +547,13 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
 
 def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, resolve,
                     imgv: str, img: str, imgf: str, W: int, mode: str,
-                    bounds=()) -> J.Kernel:
+                    bounds=(), k16: bool = False) -> J.Kernel:
     """The four-runs-per-lane body of ``gen_run_tags2`` (its docstring; 32-bit indices).
     ``group`` / ``resolve`` are that generator's 64-run emitters (appending to ``b``): the slow
     blocks run them one group at a time, and a fast block's runs resolve through the same miss
     path, one instance per run.  ``bounds``: the pre-filter's per-run bound arrays (uint16), a
-    lane's four loaded with one 8-byte load beside its run keys."""
+    lane's four loaded with one 8-byte load beside its run keys.  ``k16``: the keys come as
+    16-bit offsets plus group bases (``gen_run_tags2``)."""
     lk, rk = p.lkey, p.rkey
     # 256-run blocks per pipeline stage (RT2_UNROLL counts blocks here): at most two - 84 VGPRs
     # at W = 1, six waves per SIMD; a third block's register sets would spill
@@ -489,8 +567,9 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
     rkt = g.raw_type(rk)
     # 4 consecutive elements at an element-aligned address (the guess is arbitrary): one load
     tdefs = ["typedef int hs_i4 __attribute__((ext_vector_type(4)));"] + \
-        (["typedef unsigned short hs_us4 __attribute__((ext_vector_type(4)));"] if bounds
-         else []) + [
+        (["typedef unsigned short hs_us4 __attribute__((ext_vector_type(4)));"] if bounds or k16
+         else []) + (["typedef unsigned short hs_ro4 __attribute__((ext_vector_type(4), "
+                      "aligned(2)));"] if k16 else []) + [
              f"typedef {rkt} hs_rk4 __attribute__((ext_vector_type(4), "
              f"aligned({J._SIZEOF[rkt]})));"]
     for sl in stage_slots:
@@ -511,7 +590,8 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
         address is formed."""
         b.extend([f"{ind}const int rb_ = ({blk}) << 8;",
                   f"{ind}const int base_ = gbase >= 0 ? gbase + {off} : s0 + (rb_ - lr0);",
-                  f"{ind}const bool f_ = ({blk}) + {U} <= bend && rb_ >= lr0 && "
+                  f"{ind}const bool f_ = {'slow_ == 0 && ' if k16 else ''}({blk}) + {U} <= bend && "
+                  f"rb_ >= lr0 && "
                   f"rb_ + {R} <= lr1 && rb_ + {R} <= NR && (i64)rb_ + {R} <= nxt0 && "
                   f"base_ >= s0 && base_ + {R} <= s1;"])
 
@@ -520,10 +600,18 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
         right row ``base``; the caller has tested both (``fast``)."""
         b.append(f"{ind}pb{s} = {base};")
         for u in range(U):
-            b.extend([f"{ind}L{s}{u} = *(const hs_v4u*)(a.RK{lk} + ({run0} + {256 * u} + "
-                      f"4 * lane));",
-                      f"{ind}R{s}{u} = *(const hs_rk4*)({g.ptr(rk)} + ({base} + {256 * u} + "
-                      f"4 * lane));"])
+            if k16:
+                lr_, rr_ = f"({run0} + {256 * u} + 4 * lane)", f"({base} + {256 * u} + 4 * lane)"
+                b.extend([f"{ind}L{s}{u} = *(const hs_us4*)(a.LO16 + {lr_});",
+                          f"{ind}R{s}{u} = *(const hs_ro4*)(a.RO16 + {rr_});",
+                          f"{ind}LG{s}{u} = a.LG16[{lr_} >> 5];",
+                          f"{ind}RG{s}{u} = a.RG16[{rr_} >> 5]; "
+                          f"RH{s}{u} = a.RG16[({rr_} + 3) >> 5];"])
+            else:
+                b.extend([f"{ind}L{s}{u} = *(const hs_v4u*)(a.RK{lk} + ({run0} + {256 * u} + "
+                          f"4 * lane));",
+                          f"{ind}R{s}{u} = *(const hs_rk4*)({g.ptr(rk)} + ({base} + {256 * u} + "
+                          f"4 * lane));"])
             for i, bp in enumerate(bounds):
                 b.append(f"{ind}M{i}{s}{u} = *(const hs_us4*)({bp} + ({run0} + {256 * u} + "
                          f"4 * lane));")
@@ -541,9 +629,18 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
             for k in range(4):
                 x = f"{s}{u}_{k}"
                 b.extend([f"{i2}{{ const int j{x} = pb{s} + {256 * u + k} + 4 * lane;",
-                          f"{i2}const int a0_{x} = s0, a1_{x} = s1; const bool act{x} = true;",
-                          f"{i2}const unsigned key{x} = L{s}{u}[{k}] + (unsigned)a.KOF;",
-                          f"{i2}const unsigned k{x} = IMGV(R{s}{u}[{k}]);"])
+                          f"{i2}const int a0_{x} = s0, a1_{x} = s1; const bool act{x} = true;"])
+                if k16:
+                    # code = group base + offset (exact); right row k is in the group of the
+                    # lane's first row or, past a group edge, of its last
+                    b.extend([f"{i2}const unsigned key{x} = (unsigned)LG{s}{u} + "
+                              f"(unsigned)L{s}{u}[{k}] + (unsigned)a.KOF;",
+                              f"{i2}const unsigned k{x} = IMGV((int)((unsigned)"
+                              f"((((pb{s} + {256 * u} + 4 * lane) & 31) + {k}) < 32"
+                              f" ? RG{s}{u} : RH{s}{u}) + (unsigned)R{s}{u}[{k}]));"])
+                else:
+                    b.extend([f"{i2}const unsigned key{x} = L{s}{u}[{k}] + (unsigned)a.KOF;",
+                              f"{i2}const unsigned k{x} = IMGV(R{s}{u}[{k}]);"])
                 for i in range(len(bounds)):
                     b.append(f"{i2}const int bm{i}_{x} = (int)M{i}{s}{u}[{k}];")
                 for sl in stage_slots:
@@ -597,10 +694,14 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
         "  int gbase = -1;   // right row of the next stage's first run (-1: range-relative)"])
     for s in sets:
         b.append(f"  int pb{s} = 0; " + " ".join(
-            f"hs_v4u L{s}{u} = {{}}; hs_rk4 R{s}{u} = {{}};" +
+            (f"hs_us4 L{s}{u} = {{}}; hs_ro4 R{s}{u} = {{}}; int LG{s}{u} = 0, RG{s}{u} = 0, "
+             f"RH{s}{u} = 0;" if k16 else f"hs_v4u L{s}{u} = {{}}; hs_rk4 R{s}{u} = {{}};") +
             "".join(f" hs_us4 M{i}{s}{u} = {{}};" for i in range(len(bounds))) +
             "".join(f" hs_c{sl}x4 C{sl}{s}{u} = {{}};" for sl in stage_slots)
             for u in range(U)))
+    if k16:
+        # blocks still to take the 64-run code after a stage met a wide group
+        b.append("  int slow_ = 0;")
     b.extend(["  int nb = bbeg;",
               "  while (nb < bend) {",
               "    while (nxt0 <= ((i64)nb << 8)) {"] + adv("      ") + ["    }"])
@@ -612,7 +713,7 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
     group(0, False, "        ")
     resolve(0, "        ")
     b.extend(["        gbase = __builtin_amdgcn_readlane((hit0 && own0) ? m0 + 1 : -1, 63);",
-              "      }",
+              "      }"] + (["      slow_ -= slow_ > 0 ? 1 : 0;"] if k16 else []) + [
               "      ++nb; continue;",
               "    }"])
     load("A", "rb_", "base_", "    ")
@@ -626,6 +727,13 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
         fast(f"nb + {U}", R, "        ")
         b.append(f"        const int nr_ = f_ ? rb_ : (nb << 8), nj_ = f_ ? base_ : pb{s};")
         load(t, "nr_", "nj_", "        ")
+        if k16:
+            # a wide group among this stage's loaded bases (wavefront-uniform): its blocks take
+            # the 64-run code on the 32-bit arrays (nb and gbase still name this stage)
+            wd = " || ".join(f"{r}{s}{u} == (int)0x80000000" for u in range(U)
+                             for r in ("LG", "RG", "RH"))
+            b.append(f"        if (__ballot({wd}) != 0ull) {{ slow_ = {U}; "
+                     "__builtin_amdgcn_s_waitcnt(0x0F70); break; }")
         resolve_stage(s, "        ")
         # (leaving the loop: drain the re-read, or the compiler's wait counts, which merge
         # every path into the loop head, would wait for it in every iteration: vmcnt(0))
@@ -1806,11 +1914,19 @@ def lower(p: NL.JoinParams, rstart, rlen, rbucket, roff, compacts, runs, nrows: 
                              __import__("numpy").zeros(4, "int64")).to(dev)
     # 32-bit run / right-row indices when both fit (with slack for the gallop's overshoot)
     ix32 = RT2_I32 and nruns < (1 << 31) - (1 << 20) and int(roff[-1].item()) < (1 << 31) - (1 << 20)
-    kt = J.kernel_for(tags2_shape(p, compacts, W, ix32, "", prune),
-                      lambda: gen_run_tags2(p, compacts, W, ix32, "", prune))
+    # both keys as 16-bit offsets from 32-element group bases, when both forms exist (else the
+    # 32-bit kernel and arguments; a launcher about to switch to a recorded match keeps it too)
+    kf = key_forms16(runs, compacts[p.rkey]) if tags2_k16(p, compacts, ix32) and \
+        runs is compacts.get(p.lkey) and not (record and RT2_MATCH) else None
+    kt = J.kernel_for(tags2_shape(p, compacts, W, ix32, "", prune, kf is not None),
+                      lambda: gen_run_tags2(p, compacts, W, ix32, "", prune, kf is not None))
     vt = {"RNG": rng_d.data_ptr(), "NRG": len(rng), "NRUNS": nruns, "tags": tags.data_ptr(),
           "num_groups": p.num_groups, "group_base": p.group_base}
     tr = rng_d
+    if kf is not None:
+        (vt["LO16"], vt["LG16"]), (vt["RO16"], vt["RG16"]) = \
+            ((t.data_ptr() for t in kf[0]), (t.data_ptr() for t in kf[1]))
+        tr = (rng_d, kf)
     bnd = []
     for _, sl, mx in prune:
         mn_t, mx_t = run_bounds(runs, compacts[sl])

@@ -81,6 +81,12 @@ class KernelConfig:
     #                              plain right columns: jit_runs.tags2_wide, else the 1 form).
     #                              SF100 step 0.714 -> 0.705 ms (profiles/bench_tags2_wide.jsonl)
     rt2_wide_grid: int = 16384   # grid of the four-run form (rt2_grid stays the one-run forms')
+    rt2_k16: bool = True         # the four-run form reads both key columns as uint16 offsets from
+    #                              32-element group bases (hs_group16_32; 8.25 instead of 12 B per
+    #                              run) when at most 3 % of either side's groups are wide
+    #                              (jit_runs.K16_MAX_WIDE), else the 32-bit form; a stage that
+    #                              meets a wide group takes the 64-run code.  SF100 step
+    #                              0.659 -> 0.585 ms (profiles/tags2_keys16.txt)
     rt2_i32: bool = True         # phase-1 run / right-row index math in 32 bits when tables fit
     rt2_match: bool = True       # phase 1 reads a per-run matched right row recorded at lowering
     #                              (literal-independent) instead of re-verifying the key match

@@ -220,6 +220,7 @@ def lib():
     _sig(L.hs_run_rowmask, I, P, P, P, I64, I64, P, P)
     _sig(L.hs_run_bitmap_tags, I, P, I64, I64, P, I64, P, P)
     _sig(L.hs_run_minmax16, I, P, P, P, I64, P, P, P)
+    _sig(L.hs_group16_32, I, P, I64, I64, P, P, P)
     _sig(L.hs_key_bitmap, I, P, I64, I64, I64, P, P, P)
     _sig(L.hs_bitmap_popcount, I, P, I64, P, P)
     _sig(L.hs_dict_like, I, P, P, I64, P, P, I, P, P)

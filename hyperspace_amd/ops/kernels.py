@@ -900,6 +900,23 @@ def run_minmax16(gmask, gruns, nruns: int, codes):
     return mn, mx
 
 
+def group16_32(x):
+    """16-bit form of a bucket-sorted int32 code array over 32-element groups
+    (``hs_group16_32``): (off, gbase) - int16 tensor holding uint16 bits and int32 group bases,
+    ``x[i] == gbase[i >> 5] + off[i]`` outside wide groups (base ``encoding.WIDE_GROUP``, zero
+    offsets).  Both are padded to a multiple of 256 elements (8 groups): zero offsets, and a
+    group of padding only is wide."""
+    torch = _torch()
+    assert x.dtype == torch.int32 and x.is_contiguous()
+    n = int(x.numel())
+    npad = max(256, (n + 255) // 256 * 256)
+    off = torch.empty(npad, dtype=torch.int16, device=x.device)
+    gbase = torch.empty(npad // 32, dtype=torch.int32, device=x.device)
+    NL.check(NL.lib().hs_group16_32(NL.ptr(x) if n else None, n, npad, NL.ptr(gbase),
+                                    NL.ptr(off), NL.stream_ptr()), "hs_group16_32")
+    return off, gbase
+
+
 def sortable_image(value, hs_type: int) -> int:
     """Host mirror of hs_sortable for a literal."""
     import struct

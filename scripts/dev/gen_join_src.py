@@ -69,6 +69,13 @@ def main(out):
                 kp = jit_runs.gen_run_tags2(p, comp, W, jit_runs.RT2_I32, "", pr)
                 kp.name += "_pruned"     # (file name only)
                 ks += [kp, jit_runs.gen_run_sparse_scan(p, comp, None, None, cand)]
+                # ... and its form over 16-bit key offsets (rt2_k16)
+                from hyperspace_amd.exec import kernel_config
+                with kernel_config.use(rt2_k16=True):
+                    if jit_runs.tags2_k16(p, comp, jit_runs.RT2_I32):
+                        k16 = jit_runs.gen_run_tags2(p, comp, W, jit_runs.RT2_I32, "", pr, True)
+                        k16.name += "_pruned_k16"
+                        ks.append(k16)
             # hash walk grouped by the left key (the functionally reduced Q3 GROUP BY)
             from hyperspace_amd.exec import hash_agg as H
             ph, _, _ = q3_params(ng)
