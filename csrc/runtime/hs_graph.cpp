@@ -24,6 +24,7 @@
 //   hs_event_destroy(ev)       (timing-disabled events of the replay slots)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -46,6 +47,52 @@ int fail(const char* what, hipError_t e) {
   return (int)e;
 }
 
+// Sorts ``all`` into dependency order: every node after the nodes it depends on (hipGraphGetNodes
+// promises no order).  Two kernel nodes of one function - the pair pipeline's two phase-2
+// launches - are then taken by hs_graph_capture_end in the order the captured chain runs them.
+bool sort_by_depth(std::vector<hipGraphNode_t>& all) {
+  const size_t n = all.size();
+  std::vector<std::vector<size_t>> deps(n);
+  for (size_t k = 0; k < n; ++k) {
+    size_t nd = 0;
+    if (hipGraphNodeGetDependencies(all[k], nullptr, &nd) != hipSuccess) return false;
+    std::vector<hipGraphNode_t> d(nd);
+    if (nd && hipGraphNodeGetDependencies(all[k], d.data(), &nd) != hipSuccess) return false;
+    for (size_t j = 0; j < nd; ++j) {
+      size_t at = 0;
+      while (at < n && all[at] != d[j]) ++at;
+      if (at == n) return false;
+      deps[k].push_back(at);
+    }
+  }
+  std::vector<int> depth(n, -1);   // longest chain of dependencies below the node
+  for (size_t done = 0, pass = 0; done < n; ++pass) {
+    if (pass > n) return false;    // (a cycle: not a captured graph)
+    for (size_t k = 0; k < n; ++k) {
+      if (depth[k] >= 0) continue;
+      int d = 0;
+      for (size_t j : deps[k]) {
+        if (d < 0 || depth[j] < 0) {
+          d = -1;   // a dependency not placed yet: next pass
+        } else if (depth[j] + 1 > d) {
+          d = depth[j] + 1;
+        }
+      }
+      if (d >= 0) {
+        depth[k] = d;
+        ++done;
+      }
+    }
+  }
+  std::vector<size_t> idx(n);
+  for (size_t k = 0; k < n; ++k) idx[k] = k;
+  std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return depth[a] < depth[b]; });
+  std::vector<hipGraphNode_t> out(n);
+  for (size_t k = 0; k < n; ++k) out[k] = all[idx[k]];
+  all.swap(out);
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -59,7 +106,8 @@ int hs_graph_capture_begin(void* stream) {
 
 // Ends the capture and instantiates.  funcs[i] (hipFunction_t of a generated kernel) names the
 // kernel node whose arguments hs_graph_set_args(.., i, ..) rewrites: the first captured kernel
-// node launching that function not already taken.  Returns nullptr on failure.
+// node, in dependency order, launching that function and not already taken.  Returns nullptr on
+// failure.
 void* hs_graph_capture_end(void* stream, void** funcs, int nfuncs) {
   hipGraph_t graph = nullptr;
   hipError_t e = hipStreamEndCapture((hipStream_t)stream, &graph);
@@ -75,6 +123,13 @@ void* hs_graph_capture_end(void* stream, void** funcs, int nfuncs) {
   if (e == hipSuccess && n) e = hipGraphGetNodes(graph, all.data(), &n);
   if (e != hipSuccess) {
     fail("hipGraphGetNodes", e);
+    hipGraphDestroy(graph);
+    delete g;
+    return nullptr;
+  }
+  all.resize(n);
+  if (!sort_by_depth(all)) {
+    g_err = "hs_graph_capture_end: could not order the captured nodes by dependency";
     hipGraphDestroy(graph);
     delete g;
     return nullptr;

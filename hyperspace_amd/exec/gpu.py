@@ -122,6 +122,9 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
         # plan object id -> (plan, _AggProgram): prepared re-submission of plan-cache hits
         self._programs: Dict[int, tuple] = {}
         self._prog_candidate = None
+        # in-flight merge-join queries of one shape share a phase-1 pass (exec/pairing.py)
+        from .pairing import PairGate
+        self.pair_gate = PairGate(self.metrics, lambda: self.cache.epoch)
         from .hash_agg import TablePool
         self.htables = TablePool()
         # engine start: size the pinned staging pool once (pinning GBs is the slow part of a
@@ -137,6 +140,7 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
         indexes and packed columns (with the tables), captured graphs, prepared lowerings - so
         another session of the same process can use the device.  The next query reloads."""
         import torch
+        self.pair_gate.release_all()
         torch.cuda.synchronize(self.device)
         self.cache.clear()
         self._programs.clear()
@@ -195,17 +199,34 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
         return d
 
     def collect(self, plan: X.SparkPlan) -> pa.Table:
-        return self.collect_async(plan).result()
+        return self.collect_async(plan, hold=False).result()
 
-    def collect_async(self, plan: X.SparkPlan) -> "QueryFuture":
+    def _may_hold(self) -> bool:
+        """Whether an asynchronous submission may wait for a pair partner (exec/pairing.py): the
+        conf key is on and the session has one rank (with several, a timing-based hold could
+        order the ranks' collectives differently)."""
+        d = getattr(self.session, "dist", None)
+        return (d is None or d.world <= 1) and \
+            HyperspaceConf.join_pair_in_flight(self.session.conf)
+
+    def collect_async(self, plan: X.SparkPlan, hold: bool = True) -> "QueryFuture":
         """Submit a query; ``.result()`` returns its table.  Fused aggregates (the indexed
         filter / join hot paths) return before the device finishes, so a caller that keeps
         several queries in flight overlaps host planning with device execution.  A shape the
-        device cannot run falls back to the host oracle (recorded in ``path``)."""
+        device cannot run falls back to the host oracle (recorded in ``path``).  ``hold``
+        false (a synchronous collect): nothing is held for a pair partner, here or before.
+        Only a prepared program's re-submission (``_AggProgram.submit``) takes ``hold`` on; a
+        query that goes through planning launches at once."""
+        gate = self.pair_gate
+        if gate.held:       # an engine entry (exec/pairing.py)
+            if hold:
+                gate.poll()
+            else:
+                gate.release_all()
         t0 = time.perf_counter()
         hit = self._programs.get(id(plan))
         if hit is not None and hit[0] is plan:
-            fut = hit[1].submit(self, plan, t0)
+            fut = hit[1].submit(self, plan, t0, hold)
             if fut is not None:
                 self.last_path, self.fallback_reason = "native", None
                 return fut

@@ -16,6 +16,7 @@ from . import compile as CP, jit
 from .arrow_eval import key
 from .device_table import DeviceColumn
 from .graphs import _cbuf, GraphPending as _GraphPending, range_bounds, ScanAggGraph
+from .pairing import HeldQuery
 from .gpu_common import (arrow_table, _compact_buffers, _eval_scalar, _GraphPrep, _group_limit,
                          _JoinPrep, _NeedHash, _ScanPrep, _Stale, _use_on, bucket_chunks, DRel,
                          GROUP_LDS_SCAN, log, MAX_GROUPS_SCAN, Unsupported)
@@ -337,6 +338,7 @@ class AggOps:
                 res = prep.run(self, fns, group)
             except _Stale:
                 self._agg_preps.pop(id(final), None)
+                self.pair_gate.release_all()
                 res = None
             if res is not None:
                 self._prog_candidate = (final, fns, group, prep, self.cache.epoch)
@@ -379,8 +381,9 @@ class AggOps:
                 # the replay ran on the side stream: the collective on this stream waits for it
                 torch.cuda.current_stream().wait_stream(self._side)
             sums, cnts, mins, maxs = sums.graph.out
-        if isinstance(sums, _GraphPending):
-            fetch = sums.result
+        pending = None
+        if isinstance(sums, (_GraphPending, HeldQuery)):
+            pending, fetch = sums, sums.result
         elif d is not None and d.world > 1:
             with stage("agg.combine_ranks"):
                 if group is not None and not self._groups_agreed:
@@ -397,6 +400,7 @@ class AggOps:
             with stage("agg.result"):
                 host = fetch()
             return self._agg_table(final, fns, group, host, G, A, gbase, gdict, gtype)
+        finish.pending = pending      # (QueryFuture.done)
         return finish
 
     def _agg_table(self, final, fns, group, host, G, A, gbase, gdict, gtype) -> pa.Table:

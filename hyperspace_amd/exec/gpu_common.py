@@ -362,10 +362,10 @@ class _ScanPrep:
     def tables(self):
         return (self.r.table,)
 
-    def run(self, be, fns, group):
+    def run(self, be, fns, group, hold=False):
         return be._scan_agg(self.r, fns, group, self)
 
-    def fast(self, be, fns, group):
+    def fast(self, be, fns, group, hold=False):
         """``run`` for a literal vector whose lowering and graph block are cached, with no
         re-validation beyond the graph's (``_AggProgram`` checked residency); None otherwise."""
         gp = self.graph
@@ -418,7 +418,7 @@ class _JoinPrep:
     def tables(self):
         return (self.left.table, self.right.table)
 
-    def run(self, be, fns, group):
+    def run(self, be, fns, group, hold=False):
         left = self.left
         lkey = self.literal_key()
         low = self.lowered.get(lkey) if lkey is not None else None
@@ -464,16 +464,20 @@ class _JoinPrep:
                     jp.group_col = col_info(group).slot if G > 1 else -1
                     jp.num_groups, jp.group_base = G, gbase
                 if isinstance(self.launcher, jit_runs.TwoPhaseLauncher):
-                    out = self.launcher.launch(
-                        jp, lkey, graph=HyperspaceConf.join_graph_enabled(be.session.conf))
-                    if isinstance(out, _GraphPending):
-                        out = (out, None, None, None)
+                    if lkey is not None and self.launcher.graphable() and \
+                            HyperspaceConf.join_graph_enabled(be.session.conf):
+                        # a graph replay: alone, held for a partner or as a pair (pairing.py)
+                        out = (be.pair_gate.submit(self.launcher, jp, lkey,
+                                                   hold and be._may_hold()),
+                               None, None, None)
+                    else:
+                        out = self.launcher.launch(jp, lkey)
                 else:
                     out = self.launcher.launch(jp)
         be._groups_agreed = self.agreed
         return (*out, *self.gtail)
 
-    def fast(self, be, fns, group):
+    def fast(self, be, fns, group, hold=False):
         """``run`` replaying the captured two-phase pipeline for a cached literal vector; None
         when that does not apply (the full ``run`` / planning path runs instead)."""
         launcher = self.launcher
@@ -486,7 +490,7 @@ class _JoinPrep:
         jp, keep, specs = low
         if keep[0].always_false or keep[1].always_false:
             return None
-        out = launcher.launch(jp, lkey, graph=True)
+        out = be.pair_gate.submit(launcher, jp, lkey, hold and be._may_hold())
         be._groups_agreed = self.agreed
         return (out, None, None, None, *self.gtail)
 
@@ -540,13 +544,21 @@ class _AggProgram:
         self.final, self.fns, self.group, self.prep, self.epoch = final, fns, group, prep, epoch
         self.n = 0
 
-    def submit(self, be, plan, t0):
+    def submit(self, be, plan, t0, hold=False):
+        """``hold``: the query may wait for a pair partner (an asynchronous submission)."""
+        fut = self._submit(be, plan, t0, hold)
+        if fut is None:
+            # the lowerings may be about to change: nothing stays held over that
+            be.pair_gate.release_all()
+        return fut
+
+    def _submit(self, be, plan, t0, hold=False):
         if be.cache.epoch != self.epoch:
             return None
         self.n += 1
         if self.n % 64 == 0 and not all(be._holds(t) for t in self.prep.tables()):
             return None      # (also keeps the tables recent in the cache's LRU)
-        res = self.prep.fast(be, self.fns, self.group)
+        res = self.prep.fast(be, self.fns, self.group, hold)
         if res is None:
             # a literal vector this program has not lowered yet: its literal-dependent lowering
             # runs here (what the executor's _dense_agg would run for this prep) instead of
@@ -555,7 +567,7 @@ class _AggProgram:
                 return None
             be._groups_agreed = False
             try:
-                res = self.prep.run(be, self.fns, self.group)
+                res = self.prep.run(be, self.fns, self.group, hold)
             except _Stale:
                 return None
             if res is None:
@@ -684,8 +696,25 @@ class QueryFuture:
         self._value = None
         self._done = False
 
+    def done(self) -> bool:
+        """Whether ``result()`` returns without waiting for the device.  A captured pipeline's
+        completion event answers; a query whose launch is held for a pair partner is launched
+        first, so polling ends.  Other paths have no event: their ``result()`` is the wait."""
+        if self._done:
+            return True
+        gate = self.backend.pair_gate
+        if gate.held:
+            gate.poll()
+        p = getattr(self._finish, "pending", None)
+        return True if p is None else p.done()
+
     def result(self) -> pa.Table:
         if not self._done:
+            # a wait is an engine entry (pairing.py): before it, and once it returns, a held
+            # query whose predecessor has finished is launched
+            gate = self.backend.pair_gate
+            if gate.held:
+                gate.poll()
             try:
                 self._value = self._finish()
             except Unsupported as e:   # e.g. a result expression the device path cannot finish
@@ -695,6 +724,8 @@ class QueryFuture:
                 self.backend.last_path, self.backend.fallback_reason = self.path, self.reason
             self._done = True
             self._finish = None
+            if gate.held:
+                gate.poll()
             self.backend.metrics["last_query_s"] = time.perf_counter() - self._t0
         return self._value
 

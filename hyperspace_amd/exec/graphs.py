@@ -140,21 +140,46 @@ class _RingGraph:
         return self.slots[0].graph
 
     def _capture(self, slot: _Slot, blocks, cur) -> None:
+        slot.graph = self._capture_of(lambda st: self._enqueue(slot, st, blocks), self.kernels,
+                                      cur)
+
+    def _capture_of(self, enqueue, kernels, cur):
+        """The executable graph (native handle) of what ``enqueue(stream)`` queues;
+        ``kernels``: the generated kernels whose argument blocks a replay rewrites, in launch
+        order."""
         import torch
         R = jit.runtime()
         side = torch.cuda.Stream()
         side.wait_stream(cur)
         _rt_check(R.hs_graph_capture_begin(side.cuda_stream), "hs_graph_capture_begin")
         try:
-            self._enqueue(slot, side.cuda_stream, blocks)
+            enqueue(side.cuda_stream)
         finally:
-            fns = [k.function() for k in self.kernels]
+            fns = [k.function() for k in kernels]
             arr = (C.c_void_p * len(fns))(*fns)
             h = R.hs_graph_capture_end(side.cuda_stream, arr, len(fns))
         if not h:
             raise RuntimeError(f"graph capture: {R.hs_graph_last_error().decode()}")
         cur.wait_stream(side)
-        slot.graph = h
+        return h
+
+    def _take_slot(self) -> _Slot:
+        """The ring's next slot, free for a new query: a slot still holding an unread earlier
+        result is drained first (wait for it and keep its result on the earlier handle), one
+        whose replay is still running is waited for."""
+        slot = self.slots[self._next]
+        self._next = (self._next + 1) % len(self.slots)
+        prev = slot.current
+        if prev is not None and prev.value is None:
+            prev.value = self._read(slot)
+        elif slot.launched and not slot.done():
+            slot.wait()    # back-pressure: the slot's replay is still running
+        return slot
+
+    def busy(self) -> bool:
+        """Whether the most recent launch has not finished on the device."""
+        slot = self.slots[self._next - 1]
+        return slot.launched and not slot.done()
 
     def _launch_slot(self, fill, blocks, stream=None, after=None) -> _Launch:
         """Queue one query on ``stream`` (default: the current stream), ordered after the work
@@ -165,13 +190,7 @@ class _RingGraph:
         new kernel arguments only once its previous replay has finished.  A replay is one native
         call (``hs_graph_replay``: ordering, argument rewrite, launch, completion event)."""
         import torch
-        slot = self.slots[self._next]
-        self._next = (self._next + 1) % len(self.slots)
-        prev = slot.current
-        if prev is not None and prev.value is None:
-            prev.value = self._read(slot)
-        elif slot.launched and not slot.done():
-            slot.wait()    # back-pressure: the slot's replay is still running
+        slot = self._take_slot()
         fill(slot.h_params)
         R = jit.runtime()
         if slot.graph is not None:
@@ -320,11 +339,78 @@ class TwoPhaseGraph(_RingGraph):
         self.parts = jit._partials(grid_s, GA, device)
         self.out = K.agg_outputs(GA, device)
         self._init_ring(0)
+        # captured pairs (``launch_pair``): index of the first query's slot -> native handle
+        self.pairs: dict = {}
+        self._pair_warm = False
+        self.pair_replays = 0
 
     def _enqueue(self, slot: _Slot, stream: int, blocks) -> None:
         self.kt.launch_packed(self.grid_t, blocks[0], stream, 0)
         self.ks.launch_packed(self.grid_s, blocks[1], stream, self.shmem)
         self._final_and_d2h(slot, stream, self.grid_s)
+
+    def _enqueue_pair(self, ktp: jit.Kernel, sa: _Slot, sb: _Slot, stream: int, blocks) -> None:
+        """One linear chain: pair phase 1, then per query phase 2, final reduction and the copy
+        into its own slot's result block (the partials and the device result block are reused
+        in stream order, as between two single queries)."""
+        ktp.launch_packed(self.grid_t, blocks[0], stream, 0)
+        for slot, blk in ((sa, blocks[1]), (sb, blocks[2])):
+            self.ks.launch_packed(self.grid_s, blk, stream, self.shmem)
+            self._final_and_d2h(slot, stream, self.grid_s)
+
+    def launch_pair(self, ktp: jit.Kernel, block_tp, block_sa, block_sb, single) -> tuple:
+        """Queue two queries behind one pass of the pair phase-1 kernel ``ktp`` (``_cbuf``
+        blocks: the pair kernel's, and each query's phase 2).  Each query takes its own ring
+        slot; both slots' events are recorded behind the whole chain.  The first pair runs
+        eagerly (that loads the pair kernel's module); a later one captures the chain for its
+        two slots, and from then on that slot pair replays it.
+
+        ``single``: the (phase 1, phase 2) blocks of either query alone.  A stream of pairs
+        never runs its slots alone, so their single-query graphs would be captured by the
+        first queries that do - synchronous collects, which wait for each capture.  Instead
+        each pair launch captures one missing single-query graph of its slots, after the pair
+        is queued: the host does it while the device runs the pair."""
+        import torch
+        ia = self._next
+        sa, sb = self._take_slot(), self._take_slot()
+        blocks = (block_tp, block_sa, block_sb)
+        R = jit.runtime()
+        h = self.pairs.get(ia)
+        if h is not None:
+            st = NL.raw_stream()
+            ptrs = (C.c_void_p * 3)(*[C.addressof(b) for b in blocks])
+            _rt_check(R.hs_graph_replay(h, 3, ptrs, st, None, sa.event), "hs_graph_replay")
+            self.pair_replays += 1
+        else:
+            cur = torch.cuda.current_stream()
+            st = cur.cuda_stream
+            if not self._pair_warm:
+                self._enqueue_pair(ktp, sa, sb, st, blocks)
+                self._pair_warm = True
+            else:
+                # (``ks`` twice: the native side takes kernel nodes of one function in
+                # dependency order, so blocks[1] is A's phase 2 and blocks[2] is B's)
+                h = self.pairs[ia] = self._capture_of(
+                    lambda s_: self._enqueue_pair(ktp, sa, sb, s_, blocks),
+                    (ktp, self.ks, self.ks), cur)
+                _rt_check(R.hs_graph_launch(h, st), "hs_graph_launch")
+                self.pair_replays += 1
+            _rt_check(R.hs_event_record(sa.event, st), "hs_event_record")
+        _rt_check(R.hs_event_record(sb.event, st), "hs_event_record")
+        out = []
+        for slot in (sa, sb):
+            slot.launched = True
+            slot.current = _Launch(slot)
+            out.append(slot.current)
+        if self._warm and (sa.graph is None or sb.graph is None):
+            # (captured, not launched: a replay rewrites both kernels' argument blocks)
+            self._capture(sa if sa.graph is None else sb, single, torch.cuda.current_stream())
+        return tuple(out)
+
+    def __del__(self):
+        pairs = getattr(self, "pairs", None)
+        while pairs:
+            jit.runtime().hs_graph_destroy(pairs.popitem()[1])
 
     def buffers(self) -> list:
         return [*self.parts, self.out[0].hs_buf]
@@ -347,6 +433,11 @@ class GraphPending:
 
     def result(self):
         return self.graph.result(self.handle)
+
+    def done(self) -> bool:
+        """Whether ``result()`` returns without waiting for the device."""
+        h = self.handle
+        return h.value is not None or h.slot.current is not h or h.slot.done()
 
 
 class GraphCache:

@@ -39,11 +39,21 @@ key columns as uint16 offsets from the bases of 32-element groups (``encoding.gr
 built natively by ``hs_group16_32``; exact: code = base + offset): 8.25 instead of 12 B per run,
 1.24 GB, and the step moves ~2.9 GB in 0.585 ms (5.0 TB/s; phase 1 377 -> 264 us at 4.7 TB/s,
 ``profiles/tags2_keys16.txt``).  The 32-bit arrays stay resident for the gallop and for stages
-that meet a wide group.  The two-phase
+that meet a wide group.
+
+Phase 1 streams the same 1.24 GB for every query of a shape - only the literal compares at its
+end differ - so that form can tag two queries in one pass (RT2_PAIR, ``tags2_pair``;
+``TwoPhaseLauncher.launch_pair``): a second set of literal slots, a second bitmap (19 MB), and
+everything literal-independent done once per run.  ``exec/pairing.py`` pairs a query submitted
+asynchronously while its predecessor still runs with the next one of the lowering; each keeps
+its own phase 2, final reduction and result copy, so its result is bit for bit the unpaired
+one.  Phase-1 dispatches per headline step 1.0 -> 0.55, step 0.592-0.595 -> 0.480-0.503 ms
+(medians 0.594 -> 0.486; ``profiles/tags2_pair.txt``).  The two-phase
 form applies when no aggregate input comes from the right side, every right predicate reads
 only right columns, and a right-side group key (if any) has at most 255 groups."""
 from __future__ import annotations
 
+import re
 from typing import List, Optional
 
 from ..ops import _lib as NL
@@ -58,6 +68,7 @@ MJ_2P, RS_ITEMS = _CFG.mj_2p, _CFG.rs_items
 RT2_UNROLL, RT2_GRID, RT2_I32 = _CFG.rt2_unroll, _CFG.rt2_grid, _CFG.rt2_i32
 RT2_MATCH, RT2_COPY, RT2_LO16 = _CFG.rt2_match, _CFG.rt2_copy, _CFG.rt2_lo16
 RT2_WIDE, RT2_WIDE_GRID, RT2_K16 = _CFG.rt2_wide, _CFG.rt2_wide_grid, _CFG.rt2_k16
+RT2_PAIR = _CFG.rt2_pair
 RS_BITS, RS_BITS_GRID, RS_PACK = _CFG.rs_bits, _CFG.rs_bits_grid, _CFG.rs_pack
 RS_PIPE, RS_WALK, RS_LDS, RS_LUT = _CFG.rs_pipe, _CFG.rs_walk, _CFG.rs_lds, _CFG.rs_lut
 RS_PK16, RS_WAVES, RS_PACK12 = _CFG.rs_pk16, _CFG.rs_waves, _CFG.rs_pack12
@@ -168,8 +179,23 @@ def _drop_keys16(key: int, entry: tuple) -> None:
         del _KEYS16[key]
 
 
+def tags2_pair(p: NL.JoinParams, compacts, W: int, ix32: bool, mode: str = "",
+               k16: bool = False) -> bool:
+    """Whether phase 1 of this join has the pair form (RT2_PAIR): one pass over the keys, the
+    right predicate columns and the run bounds tags two queries of the shape, each with its own
+    literal slots and bitmap.  Only the headline's form: the verifying four-run kernel over
+    16-bit key offsets (``tags2_k16``: mode ""), 1-bit tags, with or without ``prune_plan``
+    bounds."""
+    return bool(RT2_PAIR and W == 1 and mode == "" and k16 and
+                tags2_k16(p, compacts, ix32, mode))
+
+
+# the second literal set of the pair form: slot name + this suffix
+PAIR_SFX = "_b"
+
+
 def tags2_shape(p: NL.JoinParams, compacts, W: int, ix32: bool = False, mode: str = "",
-                prune: tuple = (), k16: bool = False) -> tuple:
+                prune: tuple = (), k16: bool = False, pair: bool = False) -> tuple:
     cols = tuple(sorted((s, c) for s, c in J._col_specs(p, compacts).items()
                         if s >= SPLIT or s == p.lkey))
     preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
@@ -177,6 +203,7 @@ def tags2_shape(p: NL.JoinParams, compacts, W: int, ix32: bool = False, mode: st
     return ("run_tags2", cols, preds, p.nlp, p.lkey, p.rkey, _tags_grouped(p) and p.group_col,
             W, RT2_UNROLL, J.BLOCK, ix32, mode, tuple(prune),
             bool(k16) and tags2_k16(p, compacts, ix32, mode),
+            bool(pair) and tags2_pair(p, compacts, W, ix32, mode, k16),
             tags2_wide(p, compacts, ix32, mode))
 
 
@@ -219,6 +246,10 @@ def prune_plan(p: NL.JoinParams, compacts, W: int, hk=None, record: bool = False
     return tuple(out)
 
 
+# a literal slot of ``fill_preds_aggs`` in generated source (predicate k's value / bounds / set)
+_LIT_SLOT = re.compile(r"\ba\.((?:CL|CH|L|F|T|U|S|N)\d+)\b")
+
+
 def _stage_slots(p: NL.JoinParams) -> list:
     """Right columns phase 1 reads at a matched row: predicate columns and the group key."""
     return list(dict.fromkeys(J._pred_slots(_rpreds(p)) +
@@ -233,7 +264,8 @@ def _tags_grouped(p: NL.JoinParams) -> bool:
 
 
 def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
-                  mode: str = "", prune: tuple = (), k16: bool = False) -> J.Kernel:
+                  mode: str = "", prune: tuple = (), k16: bool = False,
+                  pair: bool = False) -> J.Kernel:
     """Phase 1, direct form: no tiles and no LDS.  Each wavefront owns a contiguous chunk of
     64-run groups of the left run list (so it owns whole 2W-word stretches of the tag bitmap
     and stores them without atomics).  Lane l of a group guesses the right row of its run: the
@@ -282,9 +314,16 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
     code = base + offset for the eight keys - 8.25 instead of 12 B per run with one bound.
     Compare, key frame, miss path and tags are the 32-bit form's.  A stage in which any lane
     loaded a ``WIDE_GROUP`` base (a ballot after the loads) leaves the pipeline and takes the
-    64-run code on the 32-bit arrays, as the gallop always does."""
+    64-run code on the 32-bit arrays, as the gallop always does.
+
+    ``pair`` (``tags2_pair``; the k16 form with 1-bit tags): two queries of the shape are tagged
+    in one pass.  Loads, guess, key compare, gallop and the wide-group fall-back run once per
+    run; the right predicates and the bound tests run once per literal set (the second set's
+    slots carry ``PAIR_SFX``) and every tag word is stored twice, the second query's into
+    ``tags_b``.  Each bitmap is what the single kernel writes for that literal set."""
     assert not prune or mode == ""
     assert not k16 or tags2_k16(p, compacts, ix32, mode)
+    assert not pair or tags2_pair(p, compacts, W, ix32, mode, k16)
     IX = "int" if ix32 else "i64"  # noqa: N806 — run / right-row index type
     wide = tags2_wide(p, compacts, ix32, mode)
     args = J.Args()
@@ -294,6 +333,8 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
     args.add("p", f"RK{lk}", "const int*")
     args.add("p", "RNG", "const long long*")
     args.add("p", "tags", "unsigned*")
+    if pair:
+        args.add("p", "tags_b", "unsigned*")
     for n in ("NRG", "NRUNS", "KLO", "KSP", "KOF"):
         args.add("q", n, "long long")
     cols = J._col_specs(p, compacts)
@@ -354,6 +395,14 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
                 f"({guard}d_ < 0) ? 0u : (d_ > a.KSP ? 0xFFFFFFFFu : (unsigned)(d_ + 1)); }}))")
     img = image(rval, False)
     imgf = image(fval, fval is not rval)
+
+    def lit_b(expr: str) -> str:
+        """``expr`` over the pair's second literal set: every literal slot it names gets a
+        twin (same kind and type) with ``PAIR_SFX``."""
+        def twin(m):
+            kind, name, ct = args.slots[args._index[m.group(1)]]
+            return args.add(kind, name + PAIR_SFX, ct)
+        return _LIT_SLOT.sub(twin, expr)
 
     def tag_expr(gen: J._Gen, it, ok: str) -> str:
         cond = J._rename(gen.cnf(rpreds), stage_slots, it)
@@ -470,7 +519,9 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
         else:
             b.append(f"{ind}bool hit{u} = act{u} && k{u} == key{u};")
         b.extend([f"{ind}{IX} m{u} = j{u};",
-                  f"{ind}unsigned tg{u} = {tag_expr(gu, f'g{u}', f'hit{u}')};",
+                  f"{ind}unsigned tg{u} = {tag_expr(gu, f'g{u}', f'hit{u}')};"] +
+                 ([f"{ind}unsigned tgb{u} = {lit_b(tag_expr(gu, f'g{u}', f'hit{u}'))};"]
+                  if pair else []) + [
                   f"{ind}if (act{u} && !hit{u}) {{",
                   # gallop from the guess to the lower bound of key in [a0, a1)
                   f"{ind}  const unsigned key_ = {kfull}; {IX} lo_, hi_;",
@@ -495,19 +546,24 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
         gm = J._Gen(args, cols, SPLIT, (f"jm{u}", f"jm{u}"), frozenset(), True)
         for sl in stage_slots:
             J._uload(gm, sl, f"h{u}", b, ind + "  ")
-        b.extend([f"{ind}  tg{u} = {tag_expr(gm, f'h{u}', f'hit{u}')};",
-                  f"{ind}}}"])
+        b.append(f"{ind}  tg{u} = {tag_expr(gm, f'h{u}', f'hit{u}')};")
+        if pair:
+            b.append(f"{ind}  tgb{u} = {lit_b(tag_expr(gm, f'h{u}', f'hit{u}'))};")
+        b.append(f"{ind}}}")
         if btests:
             # a run whose bound fails a left conjunct holds no passing row
             ok = " && ".join(f"({t.replace('@U@', str(u))})" for t in btests)
             b.append(f"{ind}tg{u} = ({ok}) ? tg{u} : 0u;")
+            if pair:
+                b.append(f"{ind}tgb{u} = ({lit_b(ok)}) ? tgb{u} : 0u;")
         if not stores:
             return
         # the group's 2W tag words: whole words, plain stores
         if W == 1:
-            b.extend([f"{ind}{{ const u64 bal_ = __ballot(tg{u} != 0u);",
-                      f"{ind}  if (in{u} && lane < 2) a.tags[((gi + {u}) << 1) + lane] = "
-                      f"(unsigned)(bal_ >> (32 * lane)); }}"])
+            for tg, tags in (("tg", "tags"), ("tgb", "tags_b"))[:2 if pair else 1]:
+                b.extend([f"{ind}{{ const u64 bal_ = __ballot({tg}{u} != 0u);",
+                          f"{ind}  if (in{u} && lane < 2) a.{tags}[((gi + {u}) << 1) + lane] = "
+                          f"(unsigned)(bal_ >> (32 * lane)); }}"])
         else:
             per_w = 32 // W
             b.extend([f"{ind}{{ unsigned wd_ = 0u;",
@@ -534,7 +590,7 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
         del b[:]
         return _gen_tags2_wide(p, args, cols, b, group, resolve,
                                image(g.decode(rk, "w_"), False), img, imgf, W, mode, bounds,
-                               k16)
+                               k16, pair)
     iteration(True, ind)
     b.append("    } else {   // a range starts inside this iteration's groups")
     iteration(False, ind)
@@ -547,13 +603,14 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
 
 def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, resolve,
                     imgv: str, img: str, imgf: str, W: int, mode: str,
-                    bounds=(), k16: bool = False) -> J.Kernel:
+                    bounds=(), k16: bool = False, pair: bool = False) -> J.Kernel:
     """The four-runs-per-lane body of ``gen_run_tags2`` (its docstring; 32-bit indices).
     ``group`` / ``resolve`` are that generator's 64-run emitters (appending to ``b``): the slow
     blocks run them one group at a time, and a fast block's runs resolve through the same miss
     path, one instance per run.  ``bounds``: the pre-filter's per-run bound arrays (uint16), a
     lane's four loaded with one 8-byte load beside its run keys.  ``k16``: the keys come as
-    16-bit offsets plus group bases (``gen_run_tags2``)."""
+    16-bit offsets plus group bases (``gen_run_tags2``).  ``pair``: ``resolve`` also leaves
+    the second literal set's tag ``tgb<x>``; its words go to ``tags_b``."""
     lk, rk = p.lkey, p.rkey
     # 256-run blocks per pipeline stage (RT2_UNROLL counts blocks here): at most two - 84 VGPRs
     # at W = 1, six waves per SIMD; a third block's register sets would spill
@@ -624,7 +681,8 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
         loaded at guess base pb<s>; leaves the resolved next base in ``gbase``."""
         b.append(f"{ind}int nx_ = -1;")
         for u in range(U):
-            b.append(f"{ind}{{ unsigned pk_ = 0u;" + (" hs_i4 mo_;" if mode == "rec" else ""))
+            b.append(f"{ind}{{ unsigned pk_ = 0u;" + (" unsigned pkb_ = 0u;" if pair else "") +
+                     (" hs_i4 mo_;" if mode == "rec" else ""))
             i2 = ind + "  "
             for k in range(4):
                 x = f"{s}{u}_{k}"
@@ -647,20 +705,23 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
                     J._uload_raw(g, sl, f"g{x}", f"C{sl}{s}{u}[{k}]", "1", b, i2)
                 resolve(x, i2, False, False)
                 b.append(f"{i2}pk_ |= (tg{x} & {MASK}u) << {k * W};")
+                if pair:
+                    b.append(f"{i2}pkb_ |= (tgb{x} & {MASK}u) << {k * W};")
                 if mode == "rec":
                     b.append(f"{i2}mo_[{k}] = hit{x} ? m{x} : -1;")
                 if u == U - 1 and k == 3:
                     b.append(f"{i2}nx_ = hit{x} ? m{x} + 1 : -1;")
                 b.append(f"{i2}}}")
             # the lanes of one tag word hold disjoint bit fields: OR across them, one stores
-            if L > 1:
-                b.append(f"{i2}pk_ <<= (unsigned)({4 * W} * (lane & {L - 1}));")
-            o = 1
-            while o < L:
-                b.append(f"{i2}pk_ |= (unsigned)__shfl_xor((int)pk_, {o}, 64);")
-                o <<= 1
-            b.append(f"{i2}if ((lane & {L - 1}) == 0) a.tags[(nb + {u}) * {8 * W} + "
-                     f"(lane >> {L.bit_length() - 1})] = pk_;")
+            for pk, tags in (("pk_", "tags"), ("pkb_", "tags_b"))[:2 if pair else 1]:
+                if L > 1:
+                    b.append(f"{i2}{pk} <<= (unsigned)({4 * W} * (lane & {L - 1}));")
+                o = 1
+                while o < L:
+                    b.append(f"{i2}{pk} |= (unsigned)__shfl_xor((int){pk}, {o}, 64);")
+                    o <<= 1
+                b.append(f"{i2}if ((lane & {L - 1}) == 0) a.{tags}[(nb + {u}) * {8 * W} + "
+                         f"(lane >> {L.bit_length() - 1})] = {pk};")
             if mode == "rec":
                 b.append(f"{i2}*(hs_i4*)(a.MOUT + (((nb + {u}) << 8) + 4 * lane)) = mo_;")
             b.append(f"{ind}}}")
@@ -1735,7 +1796,7 @@ class TwoPhaseLauncher:
     ``launch(p)`` fills the literal slots and queues: bitmap clear, tags, scan, partials fold."""
     __slots__ = ("kt", "ks", "grid_t", "grid_s", "GA", "shmem", "vt", "vs", "compacts", "keep",
                  "tags", "dev", "blocks", "hk", "graph", "gblocks", "tk", "tpl", "match",
-                 "launches")
+                 "launches", "ktp", "tags_b", "tplp", "pblocks", "bblocks", "held")
 
     def __init__(self, kt, ks, grid_t, grid_s, GA, shmem, vt, vs, compacts, keep, tags, dev,
                  hk=None, tk=None):
@@ -1758,6 +1819,13 @@ class TwoPhaseLauncher:
         # (RT2_MATCH): on the launcher's second launch - a lowering that is reused - ``_record``
         self.match = None
         self.launches = 0
+        # the pair form of phase 1 (``tags2_pair``) from the lowering, or None; the second tag
+        # bitmap and the pair's packed blocks come with the first pair (``launch_pair``)
+        self.ktp, self.tags_b, self.tplp = None, None, None
+        self.pblocks: dict = {}    # (literal vector A, B) -> pair phase-1 block
+        self.bblocks: dict = {}    # literal vector -> phase-2 block reading the second bitmap
+        # a submitted query not launched yet (pairing.HeldQuery): it waits for a partner
+        self.held = None
 
     def _record(self) -> None:
         """Switch phase 1 to the recorded-match form: one verifying launch stores each run's
@@ -1766,6 +1834,8 @@ class TwoPhaseLauncher:
         caches' budgets while it lives (``device_cache.track_derived``)."""
         import torch
         from .device_cache import track_derived
+        if self.held is not None:       # (a launcher that may still record never holds)
+            self.held.release()
         W, nruns, p = self.match
         self.match = None
         need = ((nruns + 63) >> 6) * 64 * 16
@@ -1793,16 +1863,120 @@ class TwoPhaseLauncher:
         self.tpl, self.graph = None, None
         self.blocks.clear()
         self.gblocks.clear()
+        self.bblocks.clear()
+        # the recorded and copy forms have no pair form: from here on ``supports_pair`` is false
+        # (nothing is held or paired), and the second bitmap goes
+        self.ktp, self.tags_b, self.tplp = None, None, None
+        self.pblocks.clear()
 
     def graphable(self) -> bool:
         """Whether one query's launches can be captured: partials out (not the hash mode)."""
         return self.hk is None
+
+    def supports_pair(self) -> bool:
+        """Whether two queries can share one phase-1 pass (``launch_pair``): the lowering chose
+        the pair-capable kernel, partials out, and no switch to a recorded match is pending."""
+        return self.ktp is not None and self.hk is None and self.match is None
+
+    def busy(self) -> bool:
+        """Whether the captured pipeline's latest launch has not finished on the device."""
+        g = self.graph
+        return g is not None and g.busy()
+
+    def _blocks(self, p: NL.JoinParams, key) -> tuple:
+        """(phase-1 block, phase-2 block template) of one query's literals."""
+        hit = self.blocks.get(key) if key is not None else None
+        if hit is None:
+            preds = [(k_, p.preds[k_]) for k_ in range(p.npreds)]
+            aggs = [p.aggs[i] for i in range(p.naggs)]
+            if self.tpl is None:
+                vs0 = dict(self.vs)
+                vs0.update({"psum": 0, "pcnt": 0, "pmin": 0, "pmax": 0})
+                self.tpl = (bytes(self.kt.args.pack(self.vt, default=0)),
+                            bytes(self.ks.args.pack(vs0, default=0)))
+            lt: dict = {}
+            J.fill_preds_aggs(lt, preds, [], self.compacts)
+            ls: dict = {}
+            J.fill_preds_aggs(ls, preds, aggs, self.compacts)
+            hit = (bytes(self.kt.args.patch(bytearray(self.tpl[0]), lt)),
+                   self.ks.args.patch(bytearray(self.tpl[1]), ls))
+            if key is not None:
+                if len(self.blocks) >= 256:
+                    self.blocks.clear()
+                self.blocks[key] = hit
+        return hit
+
+    def _graph_blocks(self, key, hit) -> tuple:
+        """The captured pipeline (made on first use) and ``key``'s blocks for it."""
+        import struct
+        from .graphs import TwoPhaseGraph, _cbuf
+        g = self.graph
+        if g is None:
+            g = self.graph = TwoPhaseGraph(self.kt, self.ks, self.grid_t, self.grid_s,
+                                           self.GA, self.shmem, self.dev)
+        gb = self.gblocks.get(key)
+        if gb is None:
+            bs = bytearray(hit[1])
+            a = self.ks.args
+            for name, ptr in g.partial_ptrs().items():
+                struct.pack_into("<q", bs, a.offset(name), ptr)
+            gb = (_cbuf(hit[0]), _cbuf(bs))
+            if len(self.gblocks) >= 256:
+                self.gblocks.clear()
+                self.bblocks.clear()
+            self.gblocks[key] = gb
+        return g, gb
+
+    def launch_pair(self, p_a: NL.JoinParams, key_a, p_b: NL.JoinParams, key_b) -> tuple:
+        """Queue two queries of this lowering that share one phase-1 pass (``supports_pair``):
+        the pair kernel tags A into the launcher's bitmap and B into a second one, then each
+        query runs its own phase 2, final reduction and result copy, A first - one linear chain,
+        captured as one graph (``TwoPhaseGraph.launch_pair``).  Returns both queries'
+        ``graphs.GraphPending``; each result is bit for bit what ``launch`` gives."""
+        import struct
+        import torch
+        from .graphs import GraphPending, _cbuf
+        assert self.supports_pair() and key_a is not None and key_b is not None
+        if self.held is not None:
+            self.held.release()
+        self.launches += 2
+        g, gb_a = self._graph_blocks(key_a, self._blocks(p_a, key_a))
+        _, gb_b = self._graph_blocks(key_b, self._blocks(p_b, key_b))
+        if self.tags_b is None:
+            from .device_cache import track_derived
+            self.tags_b = torch.empty_like(self.tags)
+            track_derived(self.tags_b)
+            self.tplp = bytes(self.ktp.args.pack(dict(self.vt, tags_b=self.tags_b.data_ptr()),
+                                                 default=0))
+        pb = self.pblocks.get((key_a, key_b))
+        if pb is None:
+            la: dict = {}
+            J.fill_preds_aggs(la, [(k_, p_a.preds[k_]) for k_ in range(p_a.npreds)], [],
+                              self.compacts)
+            lb: dict = {}
+            J.fill_preds_aggs(lb, [(k_, p_b.preds[k_]) for k_ in range(p_b.npreds)], [],
+                              self.compacts)
+            blk = self.ktp.args.patch(bytearray(self.tplp), la)
+            pb = _cbuf(self.ktp.args.patch(blk, {n + PAIR_SFX: v for n, v in lb.items()}))
+            if len(self.pblocks) >= 256:
+                self.pblocks.clear()
+            self.pblocks[(key_a, key_b)] = pb
+        sb = self.bblocks.get(key_b)
+        if sb is None:
+            # B's phase 2 is the single query's block with the second bitmap for ``tags``
+            bs = bytearray(gb_b[1].raw)
+            struct.pack_into("<q", bs, self.ks.args.offset("tags"), self.tags_b.data_ptr())
+            sb = self.bblocks[key_b] = _cbuf(bs)
+        ha, hb = g.launch_pair(self.ktp, pb, gb_a[1], sb, gb_a)
+        return GraphPending(g, ha), GraphPending(g, hb)
 
     def launch(self, p: NL.JoinParams, key=None, htab=None, hk=None, graph: bool = False):
         """Queue one query.  Returns the (sum, count, min, max) device outputs, or with
         ``graph`` (and a literal vector ``key``) a ``graphs.GraphPending`` of one replay of the
         captured pipeline."""
         import struct
+        if self.held is not None:
+            self.held.release()     # submissions of one launcher launch in order
         self.launches += 1
         if self.match is not None and self.launches == 2:
             self._record()
@@ -1824,41 +1998,10 @@ class TwoPhaseLauncher:
             if self.tk is not None:
                 self.tk.finish(st)
             return None
-        hit = self.blocks.get(key) if key is not None else None
-        if hit is None:
-            preds = [(k_, p.preds[k_]) for k_ in range(p.npreds)]
-            aggs = [p.aggs[i] for i in range(p.naggs)]
-            if self.tpl is None:
-                vs0 = dict(self.vs)
-                vs0.update({"psum": 0, "pcnt": 0, "pmin": 0, "pmax": 0})
-                self.tpl = (bytes(self.kt.args.pack(self.vt, default=0)),
-                            bytes(self.ks.args.pack(vs0, default=0)))
-            lt: dict = {}
-            J.fill_preds_aggs(lt, preds, [], self.compacts)
-            ls: dict = {}
-            J.fill_preds_aggs(ls, preds, aggs, self.compacts)
-            hit = (bytes(self.kt.args.patch(bytearray(self.tpl[0]), lt)),
-                   self.ks.args.patch(bytearray(self.tpl[1]), ls))
-            if key is not None:
-                if len(self.blocks) >= 256:
-                    self.blocks.clear()
-                self.blocks[key] = hit
+        hit = self._blocks(p, key)
         if graph and key is not None and self.graphable():
-            from .graphs import GraphPending, TwoPhaseGraph, _cbuf
-            g = self.graph
-            if g is None:
-                g = self.graph = TwoPhaseGraph(self.kt, self.ks, self.grid_t, self.grid_s,
-                                               self.GA, self.shmem, self.dev)
-            gb = self.gblocks.get(key)
-            if gb is None:
-                bs = bytearray(hit[1])
-                a = self.ks.args
-                for name, ptr in g.partial_ptrs().items():
-                    struct.pack_into("<q", bs, a.offset(name), ptr)
-                gb = (_cbuf(hit[0]), _cbuf(bs))
-                if len(self.gblocks) >= 256:
-                    self.gblocks.clear()
-                self.gblocks[key] = gb
+            from .graphs import GraphPending
+            g, gb = self._graph_blocks(key, hit)
             return GraphPending(g, g.launch(*gb))
         # (phase 1 stores every word of every run group: no bitmap clear)
         self.kt.launch_packed(self.grid_t, hit[0], st)
@@ -1964,6 +2107,10 @@ def lower(p: NL.JoinParams, rstart, rlen, rbucket, roff, compacts, runs, nrows: 
     lz = TwoPhaseLauncher(kt, ks, grid_t, grid_s, GA, GA * 32 if _scan_grouped(p) else 0,
                           vt, vs, compacts, (rstart, rlen, rbucket, roff, tp, spans, tr, runs),
                           tags, dev, hk, tk if sparse else None)
+    if tags2_pair(p, compacts, W, ix32, "", kf is not None) and lo is None and hk is None:
+        # (its module loads, and the second bitmap is made, with the first pair)
+        lz.ktp = J.kernel_for(tags2_shape(p, compacts, W, ix32, "", prune, True, True),
+                              lambda: gen_run_tags2(p, compacts, W, ix32, "", prune, True, True))
     if record and RT2_MATCH and ix32:
         # the lowering's own parameters: a later launch's may bind other column slots
         lz.match = (W, nruns, NL.JoinParams.from_buffer_copy(p))

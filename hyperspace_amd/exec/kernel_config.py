@@ -87,6 +87,9 @@ class KernelConfig:
     #                              (jit_runs.K16_MAX_WIDE), else the 32-bit form; a stage that
     #                              meets a wide group takes the 64-run code.  SF100 step
     #                              0.659 -> 0.585 ms (profiles/tags2_keys16.txt)
+    rt2_pair: bool = True        # that form can tag two in-flight queries of one shape in one
+    #                              pass (jit_runs.tags2_pair; TwoPhaseLauncher.launch_pair): the
+    #                              second query's phase-1 bytes become one extra bitmap
     rt2_i32: bool = True         # phase-1 run / right-row index math in 32 bits when tables fit
     rt2_match: bool = True       # phase 1 reads a per-run matched right row recorded at lowering
     #                              (literal-independent) instead of re-verifying the key match

@@ -487,5 +487,11 @@ class RowsFuture:
     def reason(self):
         return self._fut.reason
 
+    def done(self) -> bool:
+        """Whether ``result()`` returns without waiting for the device (futures of paths that
+        cannot tell report True)."""
+        d = getattr(self._fut, "done", None)
+        return True if d is None else d()
+
     def result(self) -> List[Row]:
         return _rows(self._fut.result())

@@ -67,7 +67,7 @@ class QueryExecution:
             # a plan-cache hit runs the cached plan with its literals bound in place, the same
             # path as ``to_arrow_async``: the executor's prepared lowerings (and captured graphs)
             # are keyed by the cached plan's nodes, which a materialized copy would not share
-            fut = self._submit_bound(backend)
+            fut = self._submit_bound(backend, hold=False)
             if fut is not None:
                 return fut.result()
         return backend.collect(self.executed_plan)
@@ -86,7 +86,7 @@ class QueryExecution:
             return backend.collect_async(plan)
         return _Done(backend.collect(plan), getattr(backend, "last_path", "host"))
 
-    def _submit_bound(self, backend):
+    def _submit_bound(self, backend, hold: bool = True):
         """Plan-cache hit fast path: submit the cached plan itself with this query's literal
         values bound into it for the duration of the submission (plan_cache._Entry).  None when
         the query is not a hit that allows it (then ``executed_plan`` plans / materializes)."""
@@ -106,7 +106,9 @@ class QueryExecution:
         with entry.lock:
             saved = entry.bind_literals(ctx.lits)
             try:
-                fut = backend.collect_async(entry.plan)
+                # (``hold`` false: a synchronous collect is never held for a pair partner)
+                fut = backend.collect_async(entry.plan) if hold else \
+                    backend.collect_async(entry.plan, hold=False)
             finally:
                 entry.restore_literals(saved)
         # a result fallback later re-runs the query on the host: give it a plan of its own

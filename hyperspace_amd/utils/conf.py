@@ -142,6 +142,12 @@ class HyperspaceConf:
             _b(conf.get(C.JOIN_GRAPH_ENABLED, C.JOIN_GRAPH_ENABLED_DEFAULT))
 
     @staticmethod
+    def join_pair_in_flight(conf) -> bool:
+        """Two in-flight merge-join queries of one shape may share a phase-1 pass
+        (exec/pairing.py)."""
+        return _b(conf.get("spark.hyperspace.mi.join.pairInFlight", "true"))
+
+    @staticmethod
     def run_topk_enabled(conf) -> bool:
         return _b(conf.get(C.RUN_TOPK_ENABLED, C.RUN_TOPK_ENABLED_DEFAULT))
 

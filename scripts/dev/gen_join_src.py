@@ -76,6 +76,12 @@ def main(out):
                         k16 = jit_runs.gen_run_tags2(p, comp, W, jit_runs.RT2_I32, "", pr, True)
                         k16.name += "_pruned_k16"
                         ks.append(k16)
+                        # ... and the pair form of that (rt2_pair): two literal sets, two bitmaps
+                        if jit_runs.tags2_pair(p, comp, W, jit_runs.RT2_I32, "", True):
+                            kpair = jit_runs.gen_run_tags2(p, comp, W, jit_runs.RT2_I32, "", pr,
+                                                           True, True)
+                            kpair.name += "_pruned_k16_pair"
+                            ks.append(kpair)
             # hash walk grouped by the left key (the functionally reduced Q3 GROUP BY)
             from hyperspace_amd.exec import hash_agg as H
             ph, _, _ = q3_params(ng)
