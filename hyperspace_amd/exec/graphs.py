@@ -231,10 +231,12 @@ class _RingGraph:
         return (h[0:n].view(np.float64).copy(), h[n:2 * n].view(np.int64).copy(),
                 h[2 * n:3 * n].view(np.float64).copy(), h[3 * n:4 * n].view(np.float64).copy())
 
-    def _final_and_d2h(self, slot: _Slot, stream: int, grid: int) -> None:
+    def _final_and_d2h(self, slot: _Slot, stream: int, grid: int, parts=None) -> None:
+        """Fold ``parts`` (default: the graph's partials) into the device result block and copy
+        it to ``slot``'s pinned result block."""
         L = jit.runtime()
         K = NL.lib()
-        p = self.parts
+        p = self.parts if parts is None else parts
         o = self.out
         NL.check(K.hs_agg_final(NL.ptr(p[0]), NL.ptr(p[1]), NL.ptr(p[2]), NL.ptr(p[3]),
                                 grid, self.GA, NL.ptr(o[0]), NL.ptr(o[1]), NL.ptr(o[2]),
@@ -337,6 +339,9 @@ class TwoPhaseGraph(_RingGraph):
         self.kernels = (kt, ks)
         self.grid_t, self.grid_s, self.GA, self.shmem = grid_t, grid_s, GA, shmem
         self.parts = jit._partials(grid_s, GA, device)
+        # the second query's partials of a pair whose phase 2 is one pass (``launch_pair`` with
+        # the pair kernel ``ksp``)
+        self.parts_b = jit._partials(grid_s, GA, device)
         self.out = K.agg_outputs(GA, device)
         self._init_ring(0)
         # captured pairs (``launch_pair``): index of the first query's slot -> native handle
@@ -349,18 +354,30 @@ class TwoPhaseGraph(_RingGraph):
         self.ks.launch_packed(self.grid_s, blocks[1], stream, self.shmem)
         self._final_and_d2h(slot, stream, self.grid_s)
 
-    def _enqueue_pair(self, ktp: jit.Kernel, sa: _Slot, sb: _Slot, stream: int, blocks) -> None:
+    def _enqueue_pair(self, ktp: jit.Kernel, sa: _Slot, sb: _Slot, stream: int, blocks,
+                      ksp: Optional[jit.Kernel] = None) -> None:
         """One linear chain: pair phase 1, then per query phase 2, final reduction and the copy
         into its own slot's result block (the partials and the device result block are reused
-        in stream order, as between two single queries)."""
+        in stream order, as between two single queries).  With the pair phase 2 ``ksp`` (two
+        blocks): pair phase 1, pair phase 2 into both partial sets, then final reduction and
+        copy of A, final reduction and copy of B."""
         ktp.launch_packed(self.grid_t, blocks[0], stream, 0)
+        if ksp is not None:
+            ksp.launch_packed(self.grid_s, blocks[1], stream, self.shmem)
+            self._final_and_d2h(sa, stream, self.grid_s)
+            self._final_and_d2h(sb, stream, self.grid_s, self.parts_b)
+            return
         for slot, blk in ((sa, blocks[1]), (sb, blocks[2])):
             self.ks.launch_packed(self.grid_s, blk, stream, self.shmem)
             self._final_and_d2h(slot, stream, self.grid_s)
 
-    def launch_pair(self, ktp: jit.Kernel, block_tp, block_sa, block_sb, single) -> tuple:
+    def launch_pair(self, ktp: jit.Kernel, block_tp, block_sa, block_sb, single,
+                    ksp: Optional[jit.Kernel] = None) -> tuple:
         """Queue two queries behind one pass of the pair phase-1 kernel ``ktp`` (``_cbuf``
-        blocks: the pair kernel's, and each query's phase 2).  Each query takes its own ring
+        blocks: the pair kernel's, and each query's phase 2 - or, with the pair phase-2 kernel
+        ``ksp``, its one block as ``block_sa`` and no ``block_sb``: a two-kernel chain whose
+        second kernel writes A's partials into ``parts`` and B's into ``parts_b``; A's result
+        then waits for the shared phase 2 instead of its own).  Each query takes its own ring
         slot; both slots' events are recorded behind the whole chain.  The first pair runs
         eagerly (that loads the pair kernel's module); a later one captures the chain for its
         two slots, and from then on that slot pair replays it.
@@ -373,26 +390,27 @@ class TwoPhaseGraph(_RingGraph):
         import torch
         ia = self._next
         sa, sb = self._take_slot(), self._take_slot()
-        blocks = (block_tp, block_sa, block_sb)
+        blocks = (block_tp, block_sa, block_sb) if ksp is None else (block_tp, block_sa)
         R = jit.runtime()
         h = self.pairs.get(ia)
         if h is not None:
             st = NL.raw_stream()
-            ptrs = (C.c_void_p * 3)(*[C.addressof(b) for b in blocks])
-            _rt_check(R.hs_graph_replay(h, 3, ptrs, st, None, sa.event), "hs_graph_replay")
+            ptrs = (C.c_void_p * len(blocks))(*[C.addressof(b) for b in blocks])
+            _rt_check(R.hs_graph_replay(h, len(blocks), ptrs, st, None, sa.event),
+                      "hs_graph_replay")
             self.pair_replays += 1
         else:
             cur = torch.cuda.current_stream()
             st = cur.cuda_stream
             if not self._pair_warm:
-                self._enqueue_pair(ktp, sa, sb, st, blocks)
+                self._enqueue_pair(ktp, sa, sb, st, blocks, ksp)
                 self._pair_warm = True
             else:
                 # (``ks`` twice: the native side takes kernel nodes of one function in
                 # dependency order, so blocks[1] is A's phase 2 and blocks[2] is B's)
                 h = self.pairs[ia] = self._capture_of(
-                    lambda s_: self._enqueue_pair(ktp, sa, sb, s_, blocks),
-                    (ktp, self.ks, self.ks), cur)
+                    lambda s_: self._enqueue_pair(ktp, sa, sb, s_, blocks, ksp),
+                    (ktp, self.ks, self.ks) if ksp is None else (ktp, ksp), cur)
                 _rt_check(R.hs_graph_launch(h, st), "hs_graph_launch")
                 self.pair_replays += 1
             _rt_check(R.hs_event_record(sa.event, st), "hs_event_record")
@@ -413,11 +431,12 @@ class TwoPhaseGraph(_RingGraph):
             jit.runtime().hs_graph_destroy(pairs.popitem()[1])
 
     def buffers(self) -> list:
-        return [*self.parts, self.out[0].hs_buf]
+        return [*self.parts, *self.parts_b, self.out[0].hs_buf]
 
-    def partial_ptrs(self) -> dict:
-        return {"psum": self.parts[0].data_ptr(), "pcnt": self.parts[1].data_ptr(),
-                "pmin": self.parts[2].data_ptr(), "pmax": self.parts[3].data_ptr()}
+    def partial_ptrs(self, sfx: str = "", parts=None) -> dict:
+        p = self.parts if parts is None else parts
+        return {"psum" + sfx: p[0].data_ptr(), "pcnt" + sfx: p[1].data_ptr(),
+                "pmin" + sfx: p[2].data_ptr(), "pmax" + sfx: p[3].data_ptr()}
 
     def launch(self, block_t, block_s) -> _Launch:
         """``block_t`` / ``block_s``: ``_cbuf`` argument blocks of the two phases."""

@@ -48,7 +48,15 @@ everything literal-independent done once per run.  ``exec/pairing.py`` pairs a q
 asynchronously while its predecessor still runs with the next one of the lowering; each keeps
 its own phase 2, final reduction and result copy, so its result is bit for bit the unpaired
 one.  Phase-1 dispatches per headline step 1.0 -> 0.55, step 0.592-0.595 -> 0.480-0.503 ms
-(medians 0.594 -> 0.486; ``profiles/tags2_pair.txt``).  The two-phase
+(medians 0.594 -> 0.486; ``profiles/tags2_pair.txt``).
+
+The candidate phase 2 gathers nearly the same tail-word lines for both queries of a pair (their
+candidate bands overlap by 121 of 128 days or more), so it has a pair form too (RS_PAIR,
+``cand_pair``; kernel ``hs_jit_run_bits_cand2``): per tile both row masks, one gather over the
+union of the two candidate sets, each query's own predicate test, list, walk, accumulators and
+block partials - bit for bit the single launches' (``gen_run_sparse_scan``).  A pair is then
+pair phase 1, pair phase 2, and per query the final reduction and result copy
+(``profiles/bits_cand_pair.txt``).  The two-phase
 form applies when no aggregate input comes from the right side, every right predicate reads
 only right columns, and a right-side group key (if any) has at most 255 groups."""
 from __future__ import annotations
@@ -72,7 +80,7 @@ RT2_PAIR = _CFG.rt2_pair
 RS_BITS, RS_BITS_GRID, RS_PACK = _CFG.rs_bits, _CFG.rs_bits_grid, _CFG.rs_pack
 RS_PIPE, RS_WALK, RS_LDS, RS_LUT = _CFG.rs_pipe, _CFG.rs_walk, _CFG.rs_lds, _CFG.rs_lut
 RS_PK16, RS_WAVES, RS_PACK12 = _CFG.rs_pk16, _CFG.rs_waves, _CFG.rs_pack12
-RS_PRUNE = _CFG.rs_prune
+RS_PRUNE, RS_PAIR = _CFG.rs_prune, _CFG.rs_pair
 
 
 def tag_width(p: NL.JoinParams) -> int:
@@ -248,6 +256,11 @@ def prune_plan(p: NL.JoinParams, compacts, W: int, hk=None, record: bool = False
 
 # a literal slot of ``fill_preds_aggs`` in generated source (predicate k's value / bounds / set)
 _LIT_SLOT = re.compile(r"\ba\.((?:CL|CH|L|F|T|U|S|N)\d+)\b")
+# ... and of phase 2: also the aggregate coefficients A<i>_<t> / B<i>_<t>; its partial pointers
+# and accumulator registers (the pair form's second query gets twins of all three)
+_LIT_SLOT2 = re.compile(r"\ba\.((?:CL|CH|L|F|T|U|S|N)\d+|[AB]\d+_\d+)\b")
+_PART_SLOT = re.compile(r"\ba\.(psum|pcnt|pmin|pmax)\b")
+_ACC_REG = re.compile(r"\b(acc|cnt)(\d+)\b")
 
 
 def _stage_slots(p: NL.JoinParams) -> list:
@@ -1287,10 +1300,21 @@ def fill_pack12(vs: dict, p: NL.JoinParams, compacts) -> list:
     return keep
 
 
-def sparse_shape(p: NL.JoinParams, compacts, hk=None, tk=None, cand: tuple = ()) -> tuple:
+def cand_pair(p: NL.JoinParams, compacts, cand: tuple, hk=None, tk=None) -> bool:
+    """Whether the candidate phase 2 of this join has the pair form (RS_PAIR; kernel
+    ``hs_jit_run_bits_cand2``): one pass gathers the tail words of two queries' candidates once.
+    Only the headline's form: the candidate form (``cand`` from ``prune_plan``: plain
+    aggregates in registers, no hash or top-K walk) with the nibble table (RS_LUT)."""
+    return bool(RS_PAIR and RS_LUT and cand and hk is None and tk is None and
+                not _scan_grouped(p) and pack_layout(p, compacts, cand) is not None)
+
+
+def sparse_shape(p: NL.JoinParams, compacts, hk=None, tk=None, cand: tuple = (),
+                 pair: bool = False) -> tuple:
     if cand:
-        return ("run_bits_cand", RS_WALK, RS_LUT, RS_WAVES) + scan_shape(p, compacts, 1, 64)[1:] + \
-            (pack_layout(p, compacts, cand),)
+        pair = bool(pair) and cand_pair(p, compacts, cand, hk, tk)
+        return ("run_bits_cand2" if pair else "run_bits_cand", RS_WALK, RS_LUT, RS_WAVES) + \
+            scan_shape(p, compacts, 1, 64)[1:] + (pack_layout(p, compacts, cand),)
     return ("run_bits_scan", RS_PIPE, RS_WALK, RS_LDS, RS_LUT, RS_PK16, RS_WAVES,
             _p12_slots(p, compacts)) + scan_shape(p, compacts, 1, 64)[1:] + \
         (pack_layout(p, compacts),) + ((hk.shape(),) if hk is not None else ()) + \
@@ -1298,7 +1322,7 @@ def sparse_shape(p: NL.JoinParams, compacts, hk=None, tk=None, cand: tuple = ())
 
 
 def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
-                        cand: tuple = ()) -> J.Kernel:
+                        cand: tuple = (), pair: bool = False) -> J.Kernel:
     """Phase 2 for 1-bit tags, bit-parallel: the dense per-row scan spends ~20 VALU
     instructions per row (decode, predicate, run index by popcount, tag extract, compaction
     ballot + mbcnt), which bounds it below HBM speed.  Here a wavefront takes 4096-row tiles of
@@ -1340,8 +1364,25 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     passing rows), or earlier whenever ``lst_`` holds more than CAP entries.  The walk reloads
     the tail word of a passing row (an L2 hit a few hundred cycles after the filter's load)
     rather than keeping 8 bytes per entry in LDS: 12.6 KB of LDS per workgroup instead of ~53
-    (68 VGPRs, no scratch, 7 waves per SIMD)."""
+    (68 VGPRs, no scratch, 7 waves per SIMD).
+
+    Pair form (``pair``, ``cand_pair``; kernel ``hs_jit_run_bits_cand2``): two queries tagged by
+    the pair phase 1 (bitmaps ``tags`` / ``tags_b``, the second literal set and partials with
+    ``PAIR_SFX``) in one pass over the same tiles.  Both row masks come from one LUT expansion
+    of the shared run starts.  A tile in which neither query has more than CAP candidates - every
+    tile of the headline - takes the *union path*: the candidates of (mask A | mask B) go
+    through ``clst_`` with two membership bits beside the 12-bit row offset, each tail word is
+    loaded once, either query's predicates are tested with its literals under its membership
+    bit, and the two stable appends fill two lists (A at 0, B at CAP of one ``lst_`` of 2 CAP +
+    CC entries: neither can exceed CAP).  After the tile's last pass the single form's walk
+    runs over A's list into A's accumulators, then over B's into B's: the single form would
+    not have walked earlier either, so every lane adds the same values in the same order.  Any
+    other tile takes the *dense path*: the single form's candidate loop, emitted by the same
+    code, once per query (its early walks depend on where the candidate batches fall, which a
+    union pass cannot reproduce).  Grid, tile split and flush are the single form's, so each
+    query's partials are bit for bit those of its own launch."""
     assert not cand or (hk is None and tk is None)
+    assert not pair or cand_pair(p, compacts, cand, hk, tk)
     args = J.Args()
     for n, ct in (("rstart", "const long long*"), ("rlen", "const long long*"),
                   ("tile_prefix", "const long long*")):
@@ -1350,9 +1391,25 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     args.add("p", f"GM{lk}", "const unsigned long long*")
     args.add("p", f"GR{lk}", "const int*")
     args.add("p", "tags", "const unsigned*")
+    if pair:
+        args.add("p", "tags" + PAIR_SFX, "const unsigned*")
     args.add("q", "R", "long long")
     args.add("q", "nrows", "long long")
     J._common_args(args)
+    if pair:
+        for n, ct in (("psum", "double*"), ("pmin", "double*"), ("pmax", "double*"),
+                      ("pcnt", "long long*")):
+            args.add("p", n + PAIR_SFX, ct)
+
+    def set_b(lines: List[str]) -> List[str]:
+        """``lines`` for the pair's second query: literal slots (twins added as in
+        ``gen_run_tags2``), partial pointers and accumulator registers get ``PAIR_SFX``."""
+        def twin(m):
+            kind, name, ct = args.slots[args._index[m.group(1)]]
+            return args.add(kind, name + PAIR_SFX, ct)
+        return [_ACC_REG.sub(r"\1\2" + PAIR_SFX,
+                             _PART_SLOT.sub(r"a.\1" + PAIR_SFX, _LIT_SLOT2.sub(twin, x)))
+                for x in lines]
     cols = J._col_specs(p, compacts)
     lpreds = _lpreds(p)
     aggs = [p.aggs[i] for i in range(p.naggs)]
@@ -1372,6 +1429,8 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     NI = 64  # noqa: N806
     b: List[str] = []
     b += J._acc_decls(aggs, grouped, args)
+    if pair:
+        b += set_b(J._acc_decls(aggs, grouped, args)[1:])
     assert tk is None or hk is not None
     if tk is not None:
         b += JH._topk_decls(aggs, tk)
@@ -1402,7 +1461,10 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     CC = 64 * EW  # noqa: N806 — candidate form: candidates per filter pass
     if cand:
         b.append(f"  __shared__ unsigned short clst_[{WV}][{CC}];")
-    b += [f"  __shared__ unsigned short lst_[{WV}][{CAP + CC if cand else CAP}];",
+    # (pair form: A's list at 0 and B's at CAP in the union path; the dense path uses
+    # [0, CAP + CC) for one query at a time)
+    b += [f"  __shared__ unsigned short lst_[{WV}]"
+          f"[{((2 if pair else 1) * CAP + CC) if cand else CAP}];",
           "  const int ln = (int)(threadIdx.x & 63);",
           "  const int wq = (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
           "  const i64 ntiles = a.tile_prefix[a.R];",
@@ -1426,13 +1488,20 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
           "  i64 rsC = 0, reC = 0, tbC = 0; u64 gmC = 0ull; int grC = 0;",
           "  i64 rsN = 0, reN = 0, tbN = 0; u64 gmN = 0ull; int grN = 0;",
           "  unsigned tw0A_ = 0u, tw1A_ = 0u, tw2A_ = 0u, tw0B_ = 0u, tw1B_ = 0u, tw2B_ = 0u;"]
-    g1 = J._Gen(args, cols, SPLIT, ("row0", "row0"), approx, True)
+    # per-query name infix of the tag words, row masks and counts ("" alone: the single forms)
+    QS = ("", "b") if pair else ("",)  # noqa: N806
+    if pair:
+        b.append("  unsigned tw0Ab_ = 0u, tw1Ab_ = 0u, tw2Ab_ = 0u;")
+    g1 =J._Gen(args, cols, SPLIT, ("row0", "row0"), approx, True)
     elem = {}   # array name -> C expression of element (idx) from its packed 32-bit words
     issue = []  # the current tile's (C) tag-word and predicate-column loads into buffer @S@
     xpose = []  # RS_LDS: the loaded columns' chunks moved to their rows' lanes
     slab = 0    # RS_LDS: 16-byte LDS slots per wavefront
     issue.append("    { const i64 w_ = (i64)grC >> 5; tw0@S@_ = a.tags[w_]; "
                  "tw1@S@_ = a.tags[w_ + 1]; tw2@S@_ = a.tags[w_ + 2]; }")
+    if pair:
+        issue.append("    { const i64 w_ = (i64)grC >> 5; tw0@S@b_ = a.tags_b[w_]; "
+                     "tw1@S@b_ = a.tags_b[w_ + 1]; tw2@S@b_ = a.tags_b[w_ + 2]; }")
     p12 = () if cand else _p12_slots(p, compacts)
     pipe = 0 if cand else RS_PIPE
     for sl in p12:
@@ -1494,26 +1563,30 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
              "    const int ahi = hi_ <= 0 ? 0 : (hi_ >= 64 ? 64 : (int)hi_);",
              "    const u64 am = alo >= ahi ? 0ull : ((ahi == 64 ? ~0ull : ((1ull << ahi) - 1ull)) & "
              "~((1ull << alo) - 1ull));",
-             "    const unsigned sh_ = (unsigned)(q0 & 31);",
-             "    const u64 lw_ = (u64)tw0@S@_ | ((u64)tw1@S@_ << 32);",
-             "    const u64 hw_ = (u64)tw2@S@_;",
-             "    const u64 T_ = sh_ ? ((lw_ >> sh_) | (hw_ << (64 - sh_))) : lw_;",
-             ]
+             "    const unsigned sh_ = (unsigned)(q0 & 31);"]
+    for q in QS:
+        body += [f"    const u64 lw{q}_ = (u64)tw0@S@{q}_ | ((u64)tw1@S@{q}_ << 32);",
+                 f"    const u64 hw{q}_ = (u64)tw2@S@{q}_;",
+                 f"    const u64 T{q}_ = sh_ ? ((lw{q}_ >> sh_) | (hw{q}_ << (64 - sh_))) : lw{q}_;"]
     if RS_LUT:
         # row tags by nibble: rows 4i..4i+3 take their tags from a 5-run window of T (the run
         # covering row 4i-1, then the runs starting in the nibble) through a 512-entry LDS
         # table indexed by (nibble of run starts, window) - 16 fixed steps instead of a loop
         # over the group's run starts (~15 VALU per start, ~20-28 starts for the slowest lane)
-        body += ["    u64 d_ = (u64)dlut_[((unsigned)m_ & 15u) | ((((unsigned)T_ << 1) & 31u) << 4)];",
-                 "    unsigned P_ = (unsigned)__popc((unsigned)m_ & 15u);",
+        # (pair form: the run starts and their running count are shared, one lookup per query)
+        body += [f"    u64 d{q}_ = (u64)dlut_[((unsigned)m_ & 15u) | "
+                 f"((((unsigned)T{q}_ << 1) & 31u) << 4)];" for q in QS]
+        body += ["    unsigned P_ = (unsigned)__popc((unsigned)m_ & 15u);",
                  "    #pragma unroll",
                  "    for (int i_ = 1; i_ < 16; ++i_) {",
-                 "      const unsigned mn_ = (unsigned)(m_ >> (4 * i_)) & 15u;",
-                 "      const unsigned ix_ = mn_ | (((unsigned)(T_ >> (P_ - 1u)) & 31u) << 4);",
-                 "      d_ |= (u64)dlut_[ix_] << (4 * i_);",
-                 "      P_ += (unsigned)__popc(mn_);",
-                 "    }",
-                 "    d_ &= am;"]
+                 "      const unsigned mn_ = (unsigned)(m_ >> (4 * i_)) & 15u;"]
+        for q in QS:
+            body += [f"      const unsigned ix{q}_ = mn_ | "
+                     f"(((unsigned)(T{q}_ >> (P_ - 1u)) & 31u) << 4);",
+                     f"      d{q}_ |= (u64)dlut_[ix{q}_] << (4 * i_);"]
+        body += ["      P_ += (unsigned)__popc(mn_);",
+                 "    }"]
+        body += [f"    d{q}_ &= am;" for q in QS]
     else:
         body += [
              # only the group's own runs' tags (popc(m) of them) decide whether any row is set
@@ -1633,17 +1706,87 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
         body += ["      if (@T@ + 2 < t1) {"]
         body += ["    " + x for x in geom("(@T@ + 2)", "N")]
         body += ["      }", "    }"]
-    body += [
-          # exclusive scan of the lanes' passing-row counts
-          "    const int cn_ = __popcll(d_);",
-          "    int inc_ = cn_;",
-          "    for (int o_ = 1; o_ < 64; o_ <<= 1) { const int y_ = __shfl_up(inc_, o_, 64); "
-          "if (ln >= o_) inc_ += y_; }",
-          "    const int tot_ = __shfl(inc_, 63, 64);"]
+    def scan(q: str, tot: bool = True) -> List[str]:
+        """Exclusive scan of the lanes' counts of row mask d<q>_ (cn / inc / tot <q>_)."""
+        return [f"    const int cn{q}_ = __popcll(d{q}_);",
+                f"    int inc{q}_ = cn{q}_;",
+                f"    for (int o_ = 1; o_ < 64; o_ <<= 1) {{ const int y_ = __shfl_up(inc{q}_, o_, 64); "
+                f"if (ln >= o_) inc{q}_ += y_; }}"] + \
+            ([f"    const int tot{q}_ = __shfl(inc{q}_, 63, 64);"] if tot else [])
+    if pair:
+        # both queries' candidate counts of the tile (each at most 4096) in one reduction; the
+        # scans run where a path needs them, so no lane count lives across the other path
+        body += ["    int sm_ = __popcll(d_) | (__popcll(db_) << 16);",
+                 "    for (int o_ = 32; o_ > 0; o_ >>= 1) sm_ += __shfl_xor(sm_, o_, 64);",
+                 "    const int tot_ = sm_ & 0xFFFF, totb_ = sm_ >> 16;"]
+    else:
+        body += scan("")
     layout = pack_layout(p, compacts, cand)
+    packed = {sl: (off, nb) for sl, off, nb in layout} if layout else {}
+    carry_gen = J._Gen(args, cols, SPLIT, ("tcw_", "tcw_"), frozenset(), True) \
+        if tk is not None else None
+
+    def walk(at: str = "") -> List[str]:
+        """The walk of list entries [0, wn_) of ``lst_`` (from element ``at`` on): entry
+        cb + 64 k + ln goes to lane ln, k ascending."""
+        w = [f"    for (int cb = 0; cb < wn_; cb += {64 * EW}) {{"]
+        if layout:
+            w.append("      const u64* PKt_ = a.PK + tb0;")
+        ind2 = "      "
+        for k in range(EW):
+            w += [f"{ind2}const int ce{k} = cb + {64 * k} + ln;",
+                  f"{ind2}const bool cok{k} = ce{k} < wn_;",
+                  f"{ind2}const int cof{k} = cok{k} ? (int)lst_[wq][{at}ce{k}] : 0;",
+                  f"{ind2}const i64 crow{k} = tb0 + (i64)cof{k};"]
+            if tk is not None:
+                w.append(f"{ind2}const unsigned crn{k} = cok{k} ? (unsigned)lrn_[wq][ce{k}] : "
+                         f"0xFFFFFFFFu;")
+        gs = [J._Gen(args, cols, SPLIT, (f"crow{k}", f"crow{k}"), approx, True)
+              for k in range(EW)]
+        if layout:
+            args.add("p", "PK", "const unsigned long long*")
+        for k in range(EW):
+            if layout:
+                # the tile's rows through a uniform base: 32-bit lane offsets
+                w.append(f"{ind2}const u64 pk{k}_ = PKt_[cof{k}];")
+            for sl in tail:
+                if sl in packed:
+                    off, nb = packed[sl]
+                    ct = gs[k].raw_type(sl)
+                    ut = {1: "unsigned char", 2: "unsigned short", 4: "unsigned"}[nb]
+                    J._uload_raw(gs[k], sl, f"c{k}", f"(({ct})({ut})(pk{k}_ >> {off}))", "1", w,
+                                 ind2)
+                else:
+                    J._uload(gs[k], sl, f"c{k}", w, ind2)
+        for k in range(EW):
+            g = gs[k]
+            it = f"c{k}"
+            w.append(f"{ind2}{{ bool cok = cok{k};")
+            gvar = "gic"
+            if grouped:
+                base = args.add("q", "group_base", "long long")
+                ng = args.add("q", "num_groups", "long long")
+                w.append(f"{ind2}const i64 glc = (i64){J._rename(f'x{p.group_col}', tail, it)} - "
+                         f"{base};")
+                w.append(f"{ind2}cok = cok && {J._rename(g.ok(p.group_col), tail, it)} && "
+                         f"glc >= 0 && glc < {ng};")
+                w.append(f"{ind2}const int {gvar} = cok ? (int)glc : 0;")
+            if hk is not None:
+                w += [J._rename(x, tail, it)
+                      for x in JH._hash_accumulate(g, aggs, hk, "cok", ind2, tk=tk,
+                                                   seg=f"crn{k}" if tk is not None else None,
+                                                   row=f"crow{k}", run=f"qb_ + (i64)crn{k}",
+                                                   carry_gen=carry_gen)]
+            else:
+                w += [J._rename(x, tail, it)
+                      for x in J._accumulate(g, aggs, grouped, "cok", gvar, ind2)]
+            w.append(f"{ind2}}}")
+        w.append("    }")
+        return w
+
     if cand:
         # candidates -> clst_ (CC per pass) -> tail word -> left predicates on its fields ->
-        # stable append to lst_; the walk below runs after the tile's last pass (or when lst_
+        # stable append to lst_; the walk runs after the tile's last pass (or when lst_
         # holds more than CAP entries: a pass adds at most CC)
         assert layout is not None
         sign = g1.cnf_sign(lpreds)
@@ -1651,36 +1794,83 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
         fields = {sl: off for sl, off, nb in layout if sl in cand and nb == 2}
         assert set(fields) == set(cand)
         sync = J._wave_sync(True)
-        body += ["    const u64* PKc_ = a.PK + tb0;",
-                 "    int np_ = 0, wb_ = 0;",
+
+        def to_clst(q: str, entry: str) -> List[str]:
+            """Candidates [wb_, wb_ + CC) of row mask d<q>_ (in row order) -> ``clst_``."""
+            return [f"      {{ int pos_ = inc{q}_ - cn{q}_ - wb_; u64 e_ = (pos_ < " + str(CC) +
+                    f" && pos_ + cn{q}_ > 0) ? d{q}_ : 0ull;",
+                    "        while (e_) { const int bq_ = __builtin_ctzll(e_); "
+                    f"if (pos_ >= 0 && pos_ < {CC}) clst_[wq][pos_] = (unsigned short)({entry}); "
+                    "++pos_; e_ &= e_ - 1ull; } }",
+                    f"      {sync}",
+                    f"      const int cw_ = tot{q}_ - wb_ < {CC} ? tot{q}_ - wb_ : {CC};"]
+
+        def append(k: int, ok: str, at: str, np: str) -> List[str]:
+            """Stable append of pass entry k's rows that pass the left predicates."""
+            return [f"      {{ const bool fp_ = {ok} && (int)({J._rename(sign, pslots, f'f{k}')}) >= 0;",
+                    "        const u64 bl_ = __ballot(fp_);",
+                    f"        if (fp_) lst_[wq][{at}{np} + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bl_ >> 32), "
+                    f"__builtin_amdgcn_mbcnt_lo((unsigned)bl_, 0u))] = (unsigned short)fof{k};",
+                    f"        {np} += __popcll(bl_); }}"]
+
+        def fld(k: int) -> List[str]:
+            return [f"      const int r{sl}_f{k} = (int)(short)(unsigned short)(fw{k}_ >> {off});"
+                    for sl, off in fields.items()]
+
+        def cand_loop(q: str) -> List[str]:
+            """One query's candidate loop over the tile (the single form's)."""
+            c = ["    int np_ = 0, wb_ = 0;",
                  "    for (;;) {",
-                 "    if (wb_ < tot_) {",
-                 "      { int pos_ = inc_ - cn_ - wb_; u64 e_ = (pos_ < " + str(CC) +
-                 " && pos_ + cn_ > 0) ? d_ : 0ull;",
-                 "        while (e_) { const int bq_ = __builtin_ctzll(e_); "
-                 f"if (pos_ >= 0 && pos_ < {CC}) clst_[wq][pos_] = (unsigned short)(64 * ln + bq_); "
-                 "++pos_; e_ &= e_ - 1ull; } }",
-                 f"      {sync}",
-                 f"      const int cw_ = tot_ - wb_ < {CC} ? tot_ - wb_ : {CC};"]
-        for k in range(EW):
-            body += [f"      const bool fok{k} = {64 * k} + ln < cw_;",
-                     f"      const int fof{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;"]
-        for k in range(EW):
-            body.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
-        body.append(f"      {sync}")
-        for k in range(EW):
-            for sl, off in fields.items():
-                body.append(f"      const int r{sl}_f{k} = (int)(short)(unsigned short)"
-                            f"(fw{k}_ >> {off});")
-            body += [f"      {{ const bool fp_ = fok{k} && (int)({J._rename(sign, pslots, f'f{k}')}) >= 0;",
-                     "        const u64 bl_ = __ballot(fp_);",
-                     "        if (fp_) lst_[wq][np_ + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bl_ >> 32), "
-                     f"__builtin_amdgcn_mbcnt_lo((unsigned)bl_, 0u))] = (unsigned short)fof{k};",
-                     "        np_ += __popcll(bl_); }"]
-        body += [f"      wb_ += {CC};",
-                 f"      if (wb_ < tot_ && np_ <= {CAP}) continue;",
-                 "    }",
-                 "    const int wn_ = np_;"]
+                 f"    if (wb_ < tot{q}_) {{"]
+            c += to_clst(q, "64 * ln + bq_")
+            for k in range(EW):
+                c += [f"      const bool fok{k} = {64 * k} + ln < cw_;",
+                      f"      const int fof{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;"]
+            for k in range(EW):
+                c.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
+            c.append(f"      {sync}")
+            for k in range(EW):
+                c += fld(k) + append(k, f"fok{k}", "", "np_")
+            c += [f"      wb_ += {CC};",
+                  f"      if (wb_ < tot{q}_ && np_ <= {CAP}) continue;",
+                  "    }",
+                  "    const int wn_ = np_;",
+                  f"    {sync}"]
+            c += walk()
+            c += [f"    {sync}", "    np_ = 0;", f"    if (wb_ >= tot{q}_) break;", "    }"]
+            return c
+
+        body.append("    const u64* PKc_ = a.PK + tb0;")
+        if not pair:
+            body += cand_loop("")
+        else:
+            # union path: both queries at most CAP candidates in the tile (wavefront-uniform)
+            body += [f"    if (tot_ <= {CAP} && totb_ <= {CAP}) {{   // union path",
+                     "    const u64 du_ = d_ | db_;"]
+            body += scan("u")
+            body += ["    int npa_ = 0, npb_ = 0;",
+                     f"    for (int wb_ = 0; wb_ < totu_; wb_ += {CC}) {{"]
+            # entry: row offset (12 bits), bit 12: a candidate of A, bit 13: of B
+            body += to_clst("u", "(64 * ln + bq_) | (int)((d_ >> bq_) & 1ull) << 12 | "
+                                 "(int)((db_ >> bq_) & 1ull) << 13")
+            for k in range(EW):
+                body += [f"      const bool fok{k} = {64 * k} + ln < cw_;",
+                         f"      const int fen{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;",
+                         f"      const int fof{k} = fen{k} & 4095;"]
+            for k in range(EW):
+                body.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
+            body.append(f"      {sync}")
+            for k in range(EW):
+                body += fld(k) + append(k, f"(fen{k} & 4096)", "", "npa_") + \
+                    set_b(append(k, f"(fen{k} & 8192)", f"{CAP} + ", "npb_"))
+            body += ["    }",
+                     f"    {sync}",
+                     "    { const int wn_ = npa_;"] + walk() + ["    }",
+                     "    { const int wn_ = npb_;"] + set_b(walk(f"{CAP} + ")) + ["    }",
+                     f"    {sync}",
+                     "    } else {   // dense path",
+                     "    {"] + scan("", False) + cand_loop("") + ["    }",
+                     "    {"] + scan("b", False) + set_b(cand_loop("b")) + ["    }", "    }"]
     else:
         body += [
           f"    for (int wb_ = 0; wb_ < tot_; wb_ += {CAP}) {{",
@@ -1691,64 +1881,9 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
           + ("lrn_[wq][pos_] = (unsigned short)(qr_ + __popcll(m_ & ((2ull << bq_) - 1ull))); "
              if tk is not None else "") +
           "} ++pos_; e_ &= e_ - 1ull; } }",
-          ]
-    body += [f"    {J._wave_sync(bool(cand))}",
-             f"    for (int cb = 0; cb < wn_; cb += {64 * EW}) {{"]
-    if layout:
-        body.append("      const u64* PKt_ = a.PK + tb0;")
-    ind2 = "      "
-    for k in range(EW):
-        body += [f"{ind2}const int ce{k} = cb + {64 * k} + ln;",
-                 f"{ind2}const bool cok{k} = ce{k} < wn_;",
-                 f"{ind2}const int cof{k} = cok{k} ? (int)lst_[wq][ce{k}] : 0;",
-                 f"{ind2}const i64 crow{k} = tb0 + (i64)cof{k};"]
-        if tk is not None:
-            body.append(f"{ind2}const unsigned crn{k} = cok{k} ? (unsigned)lrn_[wq][ce{k}] : "
-                        f"0xFFFFFFFFu;")
-    gs = [J._Gen(args, cols, SPLIT, (f"crow{k}", f"crow{k}"), approx, True) for k in range(EW)]
-    packed = {sl: (off, nb) for sl, off, nb in layout} if layout else {}
-    if layout:
-        args.add("p", "PK", "const unsigned long long*")
-    for k in range(EW):
-        if layout:
-            # the tile's rows through a uniform base: 32-bit lane offsets
-            body.append(f"{ind2}const u64 pk{k}_ = PKt_[cof{k}];")
-        for sl in tail:
-            if sl in packed:
-                off, nb = packed[sl]
-                ct = gs[k].raw_type(sl)
-                ut = {1: "unsigned char", 2: "unsigned short", 4: "unsigned"}[nb]
-                J._uload_raw(gs[k], sl, f"c{k}", f"(({ct})({ut})(pk{k}_ >> {off}))", "1", body,
-                             ind2)
-            else:
-                J._uload(gs[k], sl, f"c{k}", body, ind2)
-    carry_gen = J._Gen(args, cols, SPLIT, ("tcw_", "tcw_"), frozenset(), True) \
-        if tk is not None else None
-    for k in range(EW):
-        g = gs[k]
-        it = f"c{k}"
-        body.append(f"{ind2}{{ bool cok = cok{k};")
-        gvar = "gic"
-        if grouped:
-            base = args.add("q", "group_base", "long long")
-            ng = args.add("q", "num_groups", "long long")
-            body.append(f"{ind2}const i64 glc = (i64){J._rename(f'x{p.group_col}', tail, it)} - "
-                        f"{base};")
-            body.append(f"{ind2}cok = cok && {J._rename(g.ok(p.group_col), tail, it)} && "
-                        f"glc >= 0 && glc < {ng};")
-            body.append(f"{ind2}const int {gvar} = cok ? (int)glc : 0;")
-        if hk is not None:
-            body += [J._rename(x, tail, it)
-                     for x in JH._hash_accumulate(g, aggs, hk, "cok", ind2, tk=tk,
-                                                 seg=f"crn{k}" if tk is not None else None,
-                                                 row=f"crow{k}", run=f"qb_ + (i64)crn{k}",
-                                                 carry_gen=carry_gen)]
-        else:
-            body += [J._rename(x, tail, it)
-                     for x in J._accumulate(g, aggs, grouped, "cok", gvar, ind2)]
-        body.append(f"{ind2}}}")
-    body += ["    }", f"    {J._wave_sync(bool(cand))}"]
-    body += ["    np_ = 0;", "    if (wb_ >= tot_) break;", "    }"] if cand else ["    }"]
+          f"    {J._wave_sync(False)}"]
+        body += walk()
+        body += [f"    {J._wave_sync(False)}", "    }"]
 
     def tile(tv: str, cur: str, nxt: str) -> List[str]:
         return ["   {"] + [x.replace("@T@", tv).replace("@S@", cur).replace("@O@", nxt)
@@ -1767,7 +1902,11 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
         b += ["  for (i64 t = t0; t < t1; ++t) {"]
         b += tile("t", "A", "A")
         b += ["  }"]
-    if hk is None:
+    if hk is None and pair:
+        # each query's block partials, folded as in its own launch
+        b += ["  {"] + J._flush(aggs, grouped) + ["  }", "  {"] + \
+            set_b(J._flush(aggs, grouped)) + ["  }"]
+    elif hk is None:
         b += J._flush(aggs, grouped)
     if tk is not None:
         b += JH._topk_carry_final(aggs, hk, tk, "  ", carry_gen)
@@ -1781,9 +1920,14 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
             out.append(f"{ind_}const u64 tkey_ = tkey_l;")
             return out
         b += JH._topk_flush(aggs, tk, args, "wid", key_lines)
-    name = "hs_jit_run_bits_cand" if cand else "hs_jit_run_bits_scan" if hk is None else \
+    name = "hs_jit_run_bits_cand2" if pair else "hs_jit_run_bits_cand" if cand else \
+        "hs_jit_run_bits_scan" if hk is None else \
         ("hs_jit_run_bits_hash" if tk is None else "hs_jit_run_bits_topk")
-    occ = f" __attribute__((amdgpu_waves_per_eu({RS_WAVES}, {RS_WAVES})))" if RS_WAVES else ""
+    # (pair form: the second accumulator set and mask put it past the 72 VGPRs of seven waves;
+    # left alone the compiler takes 97 - four waves - and bounded to six it spills nine, so it
+    # is bounded to five: 96 VGPRs, no scratch)
+    waves = RS_WAVES or (5 if pair else 0)
+    occ = f" __attribute__((amdgpu_waves_per_eu({waves}, {waves})))" if waves else ""
     src = (J._PRELUDE + args.struct_src() +
            f'extern "C" __global__ __launch_bounds__({BLOCK}){occ} void {name}(Args a) '
            f'{{\n' + "\n".join(b) + "\n}\n")
@@ -1796,7 +1940,8 @@ class TwoPhaseLauncher:
     ``launch(p)`` fills the literal slots and queues: bitmap clear, tags, scan, partials fold."""
     __slots__ = ("kt", "ks", "grid_t", "grid_s", "GA", "shmem", "vt", "vs", "compacts", "keep",
                  "tags", "dev", "blocks", "hk", "graph", "gblocks", "tk", "tpl", "match",
-                 "launches", "ktp", "tags_b", "tplp", "pblocks", "bblocks", "held")
+                 "launches", "ktp", "tags_b", "tplp", "pblocks", "bblocks", "held", "ksp", "tpls",
+                 "sblocks")
 
     def __init__(self, kt, ks, grid_t, grid_s, GA, shmem, vt, vs, compacts, keep, tags, dev,
                  hk=None, tk=None):
@@ -1824,6 +1969,11 @@ class TwoPhaseLauncher:
         self.ktp, self.tags_b, self.tplp = None, None, None
         self.pblocks: dict = {}    # (literal vector A, B) -> pair phase-1 block
         self.bblocks: dict = {}    # literal vector -> phase-2 block reading the second bitmap
+        # the pair form of the candidate phase 2 (``cand_pair``) from the lowering, or None: a
+        # pair then runs two kernels instead of three; its packed template, and per pair of
+        # literal vectors its block, come with the first pair
+        self.ksp, self.tpls = None, None
+        self.sblocks: dict = {}    # (literal vector A, B) -> pair phase-2 block
         # a submitted query not launched yet (pairing.HeldQuery): it waits for a partner
         self.held = None
 
@@ -1868,6 +2018,8 @@ class TwoPhaseLauncher:
         # (nothing is held or paired), and the second bitmap goes
         self.ktp, self.tags_b, self.tplp = None, None, None
         self.pblocks.clear()
+        self.ksp, self.tpls = None, None
+        self.sblocks.clear()
 
     def graphable(self) -> bool:
         """Whether one query's launches can be captured: partials out (not the hash mode)."""
@@ -1924,6 +2076,7 @@ class TwoPhaseLauncher:
             if len(self.gblocks) >= 256:
                 self.gblocks.clear()
                 self.bblocks.clear()
+                self.sblocks.clear()
             self.gblocks[key] = gb
         return g, gb
 
@@ -1931,7 +2084,9 @@ class TwoPhaseLauncher:
         """Queue two queries of this lowering that share one phase-1 pass (``supports_pair``):
         the pair kernel tags A into the launcher's bitmap and B into a second one, then each
         query runs its own phase 2, final reduction and result copy, A first - one linear chain,
-        captured as one graph (``TwoPhaseGraph.launch_pair``).  Returns both queries'
+        captured as one graph (``TwoPhaseGraph.launch_pair``).  With the pair phase 2
+        (``ksp``) both queries share that pass too: pair phase 1, pair phase 2, then each
+        query's final reduction and result copy.  Returns both queries'
         ``graphs.GraphPending``; each result is bit for bit what ``launch`` gives."""
         import struct
         import torch
@@ -1961,6 +2116,29 @@ class TwoPhaseLauncher:
             if len(self.pblocks) >= 256:
                 self.pblocks.clear()
             self.pblocks[(key_a, key_b)] = pb
+        if self.ksp is not None:
+            sp = self.sblocks.get((key_a, key_b))
+            if sp is None:
+                # the single form's block with the second bitmap, the second literal set and
+                # both partial sets patched in
+                if self.tpls is None:
+                    vs0 = dict(self.vs, tags_b=self.tags_b.data_ptr())
+                    vs0.update(g.partial_ptrs())
+                    vs0.update(g.partial_ptrs(PAIR_SFX, g.parts_b))
+                    self.tpls = bytes(self.ksp.args.pack(vs0, default=0))
+                sa_: dict = {}
+                J.fill_preds_aggs(sa_, [(k_, p_a.preds[k_]) for k_ in range(p_a.npreds)],
+                                  [p_a.aggs[i] for i in range(p_a.naggs)], self.compacts)
+                sb_: dict = {}
+                J.fill_preds_aggs(sb_, [(k_, p_b.preds[k_]) for k_ in range(p_b.npreds)],
+                                  [p_b.aggs[i] for i in range(p_b.naggs)], self.compacts)
+                blk = self.ksp.args.patch(bytearray(self.tpls), sa_)
+                sp = _cbuf(self.ksp.args.patch(blk, {n + PAIR_SFX: v for n, v in sb_.items()}))
+                if len(self.sblocks) >= 256:
+                    self.sblocks.clear()
+                self.sblocks[(key_a, key_b)] = sp
+            ha, hb = g.launch_pair(self.ktp, pb, sp, None, gb_a, self.ksp)
+            return GraphPending(g, ha), GraphPending(g, hb)
         sb = self.bblocks.get(key_b)
         if sb is None:
             # B's phase 2 is the single query's block with the second bitmap for ``tags``
@@ -2111,6 +2289,9 @@ def lower(p: NL.JoinParams, rstart, rlen, rbucket, roff, compacts, runs, nrows: 
         # (its module loads, and the second bitmap is made, with the first pair)
         lz.ktp = J.kernel_for(tags2_shape(p, compacts, W, ix32, "", prune, True, True),
                               lambda: gen_run_tags2(p, compacts, W, ix32, "", prune, True, True))
+        if sparse and cand_pair(p, compacts, cand, hk, tk):
+            lz.ksp = J.kernel_for(sparse_shape(p, compacts, hk, tk, cand, True),
+                                  lambda: gen_run_sparse_scan(p, compacts, hk, tk, cand, True))
     if record and RT2_MATCH and ix32:
         # the lowering's own parameters: a later launch's may bind other column slots
         lz.match = (W, nruns, NL.JoinParams.from_buffer_copy(p))

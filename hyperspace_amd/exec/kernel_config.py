@@ -114,6 +114,10 @@ class KernelConfig:
                                  # stay tagged; phase 2 then reads no row stream: it tests the
                                  # tagged runs' rows on predicate fields of the row-packed tail
                                  # word (jit_runs.prune_plan; plain aggregates, 1-bit tags)
+    rs_pair: bool = True         # the candidate phase 2 of two queries paired in phase 1 runs as
+                                 # one pass too (jit_runs.cand_pair; hs_jit_run_bits_cand2): the
+                                 # union of their candidates' tail words is gathered once, each
+                                 # query keeps its own predicate test, list, walk and partials
     rs_lut: bool = True          # bits scan row tags by nibble through an LDS table (else a loop
                                  # over each group's run starts + prefix XOR)
     rs_lds: bool = False         # bits scan predicate columns loaded lane-coalesced, then moved

@@ -69,6 +69,9 @@ def main(out):
                 kp = jit_runs.gen_run_tags2(p, comp, W, jit_runs.RT2_I32, "", pr)
                 kp.name += "_pruned"     # (file name only)
                 ks += [kp, jit_runs.gen_run_sparse_scan(p, comp, None, None, cand)]
+                # ... and the pair form of that phase 2 (rs_pair): two bitmaps, one gather
+                if jit_runs.cand_pair(p, comp, cand):
+                    ks.append(jit_runs.gen_run_sparse_scan(p, comp, None, None, cand, True))
                 # ... and its form over 16-bit key offsets (rt2_k16)
                 from hyperspace_amd.exec import kernel_config
                 with kernel_config.use(rt2_k16=True):
