@@ -56,7 +56,17 @@ candidate bands overlap by 121 of 128 days or more), so it has a pair form too (
 union of the two candidate sets, each query's own predicate test, list, walk, accumulators and
 block partials - bit for bit the single launches' (``gen_run_sparse_scan``).  A pair is then
 pair phase 1, pair phase 2, and per query the final reduction and result copy
-(``profiles/bits_cand_pair.txt``).  The two-phase
+(``profiles/bits_cand_pair.txt``).
+
+Both candidate forms keep a passing row's tail word where the filter pass has it (RS_KEEP): it
+goes into a per-wavefront LDS ring of 63 + 64 RS_WALK entries instead of its row offset into a
+list, and the sums are taken from the ring in whole groups of 64 entries after every pass, the
+rest where the listing form walked.  The walk then loads nothing: one memory round trip per
+tile and query less, 12.7 / 22.8 KB of LDS per workgroup (single / pair), and the single form
+drops from 70 to 62 VGPRs (eight waves per SIMD).  Pair dispatch 450 -> 406 us, single
+217 -> 200 us, step 0.460 -> 0.438 ms: a tenth of the kernels' time, not the quarter one trip
+less was expected to give - the reload was an L2 hit (``profiles/bits_cand_keep.txt``).  The
+two-phase
 form applies when no aggregate input comes from the right side, every right predicate reads
 only right columns, and a right-side group key (if any) has at most 255 groups."""
 from __future__ import annotations
@@ -80,7 +90,7 @@ RT2_PAIR = _CFG.rt2_pair
 RS_BITS, RS_BITS_GRID, RS_PACK = _CFG.rs_bits, _CFG.rs_bits_grid, _CFG.rs_pack
 RS_PIPE, RS_WALK, RS_LDS, RS_LUT = _CFG.rs_pipe, _CFG.rs_walk, _CFG.rs_lds, _CFG.rs_lut
 RS_PK16, RS_WAVES, RS_PACK12 = _CFG.rs_pk16, _CFG.rs_waves, _CFG.rs_pack12
-RS_PRUNE, RS_PAIR = _CFG.rs_prune, _CFG.rs_pair
+RS_PRUNE, RS_PAIR, RS_KEEP = _CFG.rs_prune, _CFG.rs_pair, _CFG.rs_keep
 
 
 def tag_width(p: NL.JoinParams) -> int:
@@ -1313,8 +1323,8 @@ def sparse_shape(p: NL.JoinParams, compacts, hk=None, tk=None, cand: tuple = (),
                  pair: bool = False) -> tuple:
     if cand:
         pair = bool(pair) and cand_pair(p, compacts, cand, hk, tk)
-        return ("run_bits_cand2" if pair else "run_bits_cand", RS_WALK, RS_LUT, RS_WAVES) + \
-            scan_shape(p, compacts, 1, 64)[1:] + (pack_layout(p, compacts, cand),)
+        return ("run_bits_cand2" if pair else "run_bits_cand", RS_WALK, RS_LUT, RS_WAVES,
+                bool(RS_KEEP)) + scan_shape(p, compacts, 1, 64)[1:] + (pack_layout(p, compacts, cand),)
     return ("run_bits_scan", RS_PIPE, RS_WALK, RS_LDS, RS_LUT, RS_PK16, RS_WAVES,
             _p12_slots(p, compacts)) + scan_shape(p, compacts, 1, 64)[1:] + \
         (pack_layout(p, compacts),) + ((hk.shape(),) if hk is not None else ()) + \
@@ -1361,10 +1371,26 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     (ballot + prefix count) to ``lst_``, which the unchanged walk of step 3 consumes.  The walk
     runs once per tile, after its last candidate (so a tile's passing-row sequence, and with it
     every lane's sum order, is that of the streaming form while the tile has at most CAP
-    passing rows), or earlier whenever ``lst_`` holds more than CAP entries.  The walk reloads
-    the tail word of a passing row (an L2 hit a few hundred cycles after the filter's load)
-    rather than keeping 8 bytes per entry in LDS: 12.6 KB of LDS per workgroup instead of ~53
-    (68 VGPRs, no scratch, 7 waves per SIMD).
+    passing rows), or earlier whenever ``lst_`` holds more than CAP entries.  That is the
+    *listing form* (RS_KEEP off): its walk loads the tail word of a passing row again (an L2 hit
+    a few hundred cycles after the filter's load) - one more dependent round trip per tile.
+
+    With RS_KEEP (the default) the filter pass keeps the word instead: the stable append writes
+    the 64-bit word ``fw<k>_`` of a passing entry into a per-wavefront ring ``kw_`` at slot
+    (entries appended since the last reset + ballot prefix) mod KB, and nothing into ``lst_``,
+    which goes.  The walk hands entry e (counted since the reset) to lane e % 64 in ascending
+    order, so any complete group of 64 entries can be summed as soon as it exists: after every
+    pass the ``cb`` loop takes the pending whole groups from the ring (its head stays a multiple
+    of 64), and the rest where the listing form walks - after the tile's last pass, or once more
+    than CAP entries were appended since the reset (``np_`` still counts appended, not pending,
+    entries, so resets and with them the lane of every later entry fall where they fell).  Each
+    lane therefore adds the same values in the same order; a different number of masked-off
+    slots only adds +0.0 to sums that start at +0.0.  KB = 63 + CC: the most a ring can hold
+    before a consumption (a leftover below 64 plus one pass's CC appends) - 2.5 KB per wavefront
+    instead of 8 (CAP + CC) for a whole tile's words.  Every tail slot is a field of the word
+    (``pack_layout`` is required here), so the walk keeps no row offset and issues no global
+    load; it takes one entry per lane and step (LDS reads need no batch in flight), which with
+    the addresses and in-flight loads gone brings the single form from 70 to 62 VGPRs.
 
     Pair form (``pair``, ``cand_pair``; kernel ``hs_jit_run_bits_cand2``): two queries tagged by
     the pair phase 1 (bitmaps ``tags`` / ``tags_b``, the second literal set and partials with
@@ -1380,7 +1406,9 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     other tile takes the *dense path*: the single form's candidate loop, emitted by the same
     code, once per query (its early walks depend on where the candidate batches fall, which a
     union pass cannot reproduce).  Grid, tile split and flush are the single form's, so each
-    query's partials are bit for bit those of its own launch."""
+    query's partials are bit for bit those of its own launch.  With RS_KEEP the union path has
+    two rings (A's at 0, B's at KB of one ``kw_``) and sums A's whole groups, then B's, after
+    every pass; the dense path uses A's ring for one query at a time."""
     assert not cand or (hk is None and tk is None)
     assert not pair or cand_pair(p, compacts, cand, hk, tk)
     args = J.Args()
@@ -1461,11 +1489,19 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     CC = 64 * EW  # noqa: N806 — candidate form: candidates per filter pass
     if cand:
         b.append(f"  __shared__ unsigned short clst_[{WV}][{CC}];")
-    # (pair form: A's list at 0 and B's at CAP in the union path; the dense path uses
-    # [0, CAP + CC) for one query at a time)
-    b += [f"  __shared__ unsigned short lst_[{WV}]"
-          f"[{((2 if pair else 1) * CAP + CC) if cand else CAP}];",
-          "  const int ln = (int)(threadIdx.x & 63);",
+    # RS_KEEP: a passing candidate's tail word stays in a per-wavefront ring kw_ of KB entries -
+    # the leftover of a 64-entry group (at most 63) plus one filter pass's appends (at most CC)
+    keep = bool(cand) and bool(RS_KEEP)
+    KB = 63 + CC  # noqa: N806
+    if keep:
+        # (pair form: A's ring at 0 and B's at KB; the dense path uses A's for one query at a time)
+        b.append(f"  __shared__ u64 kw_[{WV}][{(2 if pair else 1) * KB}];")
+    else:
+        # (pair form: A's list at 0 and B's at CAP in the union path; the dense path uses
+        # [0, CAP + CC) for one query at a time)
+        b.append(f"  __shared__ unsigned short lst_[{WV}]"
+                 f"[{((2 if pair else 1) * CAP + CC) if cand else CAP}];")
+    b += ["  const int ln = (int)(threadIdx.x & 63);",
           "  const int wq = (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
           "  const i64 ntiles = a.tile_prefix[a.R];",
           f"  const i64 nwv = (i64)gridDim.x * {WV};",
@@ -1726,27 +1762,35 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     carry_gen = J._Gen(args, cols, SPLIT, ("tcw_", "tcw_"), frozenset(), True) \
         if tk is not None else None
 
-    def walk(at: str = "") -> List[str]:
+    def walk(at: str = "", hp: str = "hp_") -> List[str]:
         """The walk of list entries [0, wn_) of ``lst_`` (from element ``at`` on): entry
-        cb + 64 k + ln goes to lane ln, k ascending."""
-        w = [f"    for (int cb = 0; cb < wn_; cb += {64 * EW}) {{"]
-        if layout:
+        cb + 64 k + ln goes to lane ln, k ascending.  RS_KEEP: of the wn_ ring entries of
+        ``kw_`` (ring at ``at``) from slot ``hp`` on; the entries are the tail words themselves."""
+        # (RS_KEEP: LDS reads need no batch in flight - one entry per lane and step, fewer registers)
+        WE = 1 if keep else EW  # noqa: N806
+        w = [f"    for (int cb = 0; cb < wn_; cb += {64 * WE}) {{"]
+        if layout and not keep:
             w.append("      const u64* PKt_ = a.PK + tb0;")
         ind2 = "      "
-        for k in range(EW):
+        for k in range(WE):
             w += [f"{ind2}const int ce{k} = cb + {64 * k} + ln;",
-                  f"{ind2}const bool cok{k} = ce{k} < wn_;",
-                  f"{ind2}const int cof{k} = cok{k} ? (int)lst_[wq][{at}ce{k}] : 0;",
+                  f"{ind2}const bool cok{k} = ce{k} < wn_;"]
+            if keep:
+                # (hp < KB and ce < wn_ <= KB: one conditional subtraction wraps)
+                w += [f"{ind2}const int ci{k} = {hp} + ce{k} - ({hp} + ce{k} >= {KB} ? {KB} : 0);",
+                      f"{ind2}const u64 pk{k}_ = cok{k} ? kw_[wq][{at}ci{k}] : 0ull;"]
+                continue
+            w += [f"{ind2}const int cof{k} = cok{k} ? (int)lst_[wq][{at}ce{k}] : 0;",
                   f"{ind2}const i64 crow{k} = tb0 + (i64)cof{k};"]
             if tk is not None:
                 w.append(f"{ind2}const unsigned crn{k} = cok{k} ? (unsigned)lrn_[wq][ce{k}] : "
                          f"0xFFFFFFFFu;")
         gs = [J._Gen(args, cols, SPLIT, (f"crow{k}", f"crow{k}"), approx, True)
-              for k in range(EW)]
+              for k in range(WE)]
         if layout:
             args.add("p", "PK", "const unsigned long long*")
-        for k in range(EW):
-            if layout:
+        for k in range(WE):
+            if layout and not keep:
                 # the tile's rows through a uniform base: 32-bit lane offsets
                 w.append(f"{ind2}const u64 pk{k}_ = PKt_[cof{k}];")
             for sl in tail:
@@ -1758,7 +1802,7 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
                                  ind2)
                 else:
                     J._uload(gs[k], sl, f"c{k}", w, ind2)
-        for k in range(EW):
+        for k in range(WE):
             g = gs[k]
             it = f"c{k}"
             w.append(f"{ind2}{{ bool cok = cok{k};")
@@ -1793,6 +1837,8 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
         assert sign is not None
         fields = {sl: off for sl, off, nb in layout if sl in cand and nb == 2}
         assert set(fields) == set(cand)
+        # (RS_KEEP: the walk has no row, only the word - every tail slot is one of its fields)
+        assert not keep or (not grouped and all(sl in packed for sl in tail))
         sync = J._wave_sync(True)
 
         def to_clst(q: str, entry: str) -> List[str]:
@@ -1817,8 +1863,58 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
             return [f"      const int r{sl}_f{k} = (int)(short)(unsigned short)(fw{k}_ >> {off});"
                     for sl, off in fields.items()]
 
+        # RS_KEEP.  Per query four wavefront-uniform counters: np entries appended since the last
+        # reset (what ``np_ <= CAP`` tests, as in the listing form), ch of them consumed - a
+        # multiple of 64, so entry e still goes to lane e % 64 - and kp / hp, the ring slots of
+        # entries np / ch (np, ch modulo KB, kept by conditional subtraction).
+        def append_keep(k: int, ok: str, at: str, s: str) -> List[str]:
+            """``append`` with the entry's tail word written to ring slot (np + prefix) % KB."""
+            return [f"      {{ const bool fp_ = {ok} && (int)({J._rename(sign, pslots, f'f{k}')}) >= 0;",
+                    "        const u64 bl_ = __ballot(fp_);",
+                    f"        const int ix_ = kp{s}_ + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bl_ >> 32), "
+                    "__builtin_amdgcn_mbcnt_lo((unsigned)bl_, 0u));",
+                    f"        if (fp_) kw_[wq][{at}ix_ - (ix_ >= {KB} ? {KB} : 0)] = fw{k}_;",
+                    f"        const int nb_ = __popcll(bl_); np{s}_ += nb_; kp{s}_ += nb_; "
+                    f"if (kp{s}_ >= {KB}) kp{s}_ -= {KB}; }}"]
+
+        def consume(s: str, fin: str, at: str = "") -> List[str]:
+            """Sum the pending entries' whole groups of 64 - all of them where ``fin`` - from ring
+            ``at``: the walk of [ch, ch + wn_), in the listing form's order."""
+            w = walk(at, f"hp{s}_")
+            return [f"    {{ const int wn_ = ({fin} ? np{s}_ : (np{s}_ & ~63)) - ch{s}_;"] + \
+                (set_b(w) if s == "b" else w) + \
+                [f"      ch{s}_ += wn_; hp{s}_ += wn_; if (hp{s}_ >= {KB}) hp{s}_ -= {KB}; }}"]
+
+        def cand_loop_keep(q: str) -> List[str]:
+            """``cand_loop`` with the sums taken after every pass; ``fin_``: where the listing
+            form walks and resets."""
+            c = ["    int np_ = 0, wb_ = 0, kp_ = 0, ch_ = 0, hp_ = 0;",
+                 "    for (;;) {",
+                 f"    if (wb_ < tot{q}_) {{"]
+            c += to_clst(q, "64 * ln + bq_")
+            for k in range(EW):
+                c += [f"      const bool fok{k} = {64 * k} + ln < cw_;",
+                      f"      const int fof{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;"]
+            for k in range(EW):
+                c.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
+            c.append(f"      {sync}")
+            for k in range(EW):
+                c += fld(k) + append_keep(k, f"fok{k}", "", "")
+            c += [f"      wb_ += {CC};",
+                  "    }",
+                  f"    const bool fin_ = !(wb_ < tot{q}_ && np_ <= {CAP});",
+                  f"    {sync}"]
+            c += consume("", "fin_")
+            c += [f"    {sync}",
+                  "    if (fin_) { np_ = 0; kp_ = 0; ch_ = 0; hp_ = 0; "
+                  f"if (wb_ >= tot{q}_) break; }}",
+                  "    }"]
+            return c
+
         def cand_loop(q: str) -> List[str]:
             """One query's candidate loop over the tile (the single form's)."""
+            if keep:
+                return cand_loop_keep(q)
             c = ["    int np_ = 0, wb_ = 0;",
                  "    for (;;) {",
                  f"    if (wb_ < tot{q}_) {{"]
@@ -1848,8 +1944,10 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
             body += [f"    if (tot_ <= {CAP} && totb_ <= {CAP}) {{   // union path",
                      "    const u64 du_ = d_ | db_;"]
             body += scan("u")
-            body += ["    int npa_ = 0, npb_ = 0;",
-                     f"    for (int wb_ = 0; wb_ < totu_; wb_ += {CC}) {{"]
+            body += ["    int npa_ = 0, npb_ = 0;"] + \
+                (["    int kpa_ = 0, cha_ = 0, hpa_ = 0, kpb_ = 0, chb_ = 0, hpb_ = 0;"]
+                 if keep else []) + \
+                [f"    for (int wb_ = 0; wb_ < totu_; wb_ += {CC}) {{"]
             # entry: row offset (12 bits), bit 12: a candidate of A, bit 13: of B
             body += to_clst("u", "(64 * ln + bq_) | (int)((d_ >> bq_) & 1ull) << 12 | "
                                  "(int)((db_ >> bq_) & 1ull) << 13")
@@ -1861,14 +1959,23 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
                 body.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
             body.append(f"      {sync}")
             for k in range(EW):
-                body += fld(k) + append(k, f"(fen{k} & 4096)", "", "npa_") + \
-                    set_b(append(k, f"(fen{k} & 8192)", f"{CAP} + ", "npb_"))
-            body += ["    }",
-                     f"    {sync}",
-                     "    { const int wn_ = npa_;"] + walk() + ["    }",
-                     "    { const int wn_ = npb_;"] + set_b(walk(f"{CAP} + ")) + ["    }",
-                     f"    {sync}",
-                     "    } else {   // dense path",
+                body += fld(k) + (
+                    append_keep(k, f"(fen{k} & 4096)", "", "a") +
+                    set_b(append_keep(k, f"(fen{k} & 8192)", f"{KB} + ", "b")) if keep else
+                    append(k, f"(fen{k} & 4096)", "", "npa_") +
+                    set_b(append(k, f"(fen{k} & 8192)", f"{CAP} + ", "npb_")))
+            if keep:
+                # whole groups after every pass, the rest after the tile's last: A's, then B's
+                body += [f"      const bool fin_ = wb_ + {CC} >= totu_;",
+                         f"      {sync}"] + consume("a", "fin_") + \
+                    consume("b", "fin_", f"{KB} + ") + [f"      {sync}", "    }"]
+            else:
+                body += ["    }",
+                         f"    {sync}",
+                         "    { const int wn_ = npa_;"] + walk() + ["    }",
+                         "    { const int wn_ = npb_;"] + set_b(walk(f"{CAP} + ")) + ["    }",
+                         f"    {sync}"]
+            body += ["    } else {   // dense path",
                      "    {"] + scan("", False) + cand_loop("") + ["    }",
                      "    {"] + scan("b", False) + set_b(cand_loop("b")) + ["    }", "    }"]
     else:
@@ -1925,7 +2032,9 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
         ("hs_jit_run_bits_hash" if tk is None else "hs_jit_run_bits_topk")
     # (pair form: the second accumulator set and mask put it past the 72 VGPRs of seven waves;
     # left alone the compiler takes 97 - four waves - and bounded to six it spills nine, so it
-    # is bounded to five: 96 VGPRs, no scratch)
+    # is bounded to five: 96 VGPRs, no scratch.  RS_KEEP: 93 at five; bounded to six it spills 18
+    # and to seven 27 - the peak is now in the dense path, whose loop holds the other query's
+    # accumulators and mask; the union path alone fits six (73) - so five stays)
     waves = RS_WAVES or (5 if pair else 0)
     occ = f" __attribute__((amdgpu_waves_per_eu({waves}, {waves})))" if waves else ""
     src = (J._PRELUDE + args.struct_src() +

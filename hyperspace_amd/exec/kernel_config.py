@@ -118,6 +118,11 @@ class KernelConfig:
                                  # one pass too (jit_runs.cand_pair; hs_jit_run_bits_cand2): the
                                  # union of their candidates' tail words is gathered once, each
                                  # query keeps its own predicate test, list, walk and partials
+    rs_keep: bool = True         # the candidate phase 2 keeps a passing row's tail word in a small
+                                 # per-wavefront LDS ring and sums from there, whole 64-entry
+                                 # groups after each filter pass (else it lists the row's offset
+                                 # and loads the word again in a walk after the tile's last pass:
+                                 # one more memory round trip per tile and query)
     rs_lut: bool = True          # bits scan row tags by nibble through an LDS table (else a loop
                                  # over each group's run starts + prefix XOR)
     rs_lds: bool = False         # bits scan predicate columns loaded lane-coalesced, then moved
