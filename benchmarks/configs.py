@@ -5,6 +5,7 @@
     python benchmarks/configs.py --config sf10_filter       # 1 MI355X
     python benchmarks/configs.py --config hybrid --sf 100   # SF100 index + 10% appended files
     python benchmarks/configs.py --config q3_3way --sf 100  # three-way join
+    python benchmarks/configs.py --config data_skipping --sf 10   # sketch build + file pruning
     python benchmarks/configs.py --config all
 
 One JSON line per configuration on stdout.  Every configuration checks its indexed results
@@ -42,6 +43,9 @@ against the same query with Hyperspace disabled (the reference's correctness ora
   on top, and a left-anti join against a 1000-key local list; ms per query, the executor path
   and the hash-join metrics of each shape.  ``--probe-sweep`` instead times the probe kernel
   alone against a 25-key and a 1M-key table for 1 / 2 / 4 / 8 stream rows per lane.
+* ``data_skipping`` — a data-skipping index (MinMax + Bloom sketches) over 128 source files:
+  device and host sketch build, a range filter and a point lookup with and without the index,
+  and the host cost of probing the sketches (``--sf 10`` for the recorded run).
 """
 import argparse
 import datetime
@@ -991,11 +995,170 @@ def config_broadcast_join(args):
     return out
 
 
+def _med(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2]
+
+
+def _sketch_kernel_times(rel, files, per_file, runs):
+    """Median ms of each sketch kernel alone over the uploaded ``c`` and ``id`` columns: MinMax,
+    the Bloom filter of the index (global-atomics path at this size) and, for comparison, a
+    filter at the LDS limit."""
+    import torch
+    from hyperspace_amd.exec import device_build as DB
+    from hyperspace_amd.ops import kernels as K
+    device = torch.device("cuda", torch.cuda.current_device())
+    cols = DB.upload_source_columns(rel, files, ["c", "id"], device)
+    rows = [per_file] * len(files)
+    from hyperspace_amd.index import dataskipping as DS
+    _, nw, k = DS.bloom_params(per_file, 0.01)
+    lds = K.sketch_bloom_lds_words()
+    shapes = {"minmax_c": lambda: K.sketch_minmax(cols["c"], rows),
+              f"bloom_id_{nw}_words": lambda: K.sketch_bloom(cols["id"], rows, nw, k),
+              f"bloom_id_{lds}_words_lds": lambda: K.sketch_bloom(cols["id"], rows, lds, k)}
+    return {n: _median_ms(fn, runs, "gpu") for n, fn in shapes.items()}
+
+
+def config_data_skipping(args):
+    """A data-skipping index over a ``lineitem``-sized table (6M x SF rows) in 128 files: ``c``
+    is clustered by file (MinMax), ``id`` holds a disjoint random subset of the ids per file
+    (Bloom), ``v`` is the payload.  Reports the sketch build (device build seconds and GB/s of
+    decoded sketched bytes, its kernel and upload shares, the host builder over the same
+    files), a selective range filter and a point lookup with and without the index (runs
+    alternate, a new literal each run, medians; results cross-checked), and the host cost of
+    ``prune`` for one equality and for an ``IN`` list of 1000 values."""
+    import numpy as np
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+    from hyperspace_amd import (BloomFilterSketch, DataSkippingIndexConfig, Hyperspace,
+                                MinMaxSketch, col, count, get_context, sum_)
+    from hyperspace_amd.exec import device_sketch
+    from hyperspace_amd.index import dataskipping as DS
+    from hyperspace_amd.plan import expressions as E
+    nfiles, runs = 128, max(5, args.ds_runs)
+    per_file = max(1, int(6_000_000 * args.sf) // nfiles)
+    root = os.path.join(args.data_dir, f"cfg_data_skipping_sf{args.sf:g}")
+    shutil.rmtree(root, ignore_errors=True)
+    src = os.path.join(root, "t")
+    os.makedirs(src)
+    rng = np.random.default_rng(7)
+    owner = rng.permutation(nfiles)        # ids congruent to owner[f] mod nfiles live in file f
+    for f in range(nfiles):
+        ids = rng.permutation(per_file).astype(np.int64) * nfiles + owner[f]
+        pq.write_table(pa.table({
+            "c": (f * 1000 + rng.integers(0, 1000, per_file)).astype(np.int32),
+            "id": ids, "v": rng.random(per_file)}), os.path.join(src, f"part-{f:05d}.parquet"))
+    s = _session(root, args.device, args.buckets)
+    hs = Hyperspace(s)
+    df = s.read.parquet(src)
+    out = {"config": "data_skipping", "device": args.device, "sf": args.sf, "files": nfiles,
+           "rows": per_file * nfiles, "runs": runs}
+    sketched_bytes = per_file * nfiles * 12
+
+    def config(name):
+        return DataSkippingIndexConfig(name, MinMaxSketch("c"),
+                                       BloomFilterSketch("id", 0.01, per_file))
+    builds, stats = [], []
+    for i in range(runs):
+        _sync(args.device)
+        t0 = time.perf_counter()
+        hs.createIndex(df, config(f"skip{i}"))
+        builds.append(time.perf_counter() - t0)
+        stats.append(dict(device_sketch.LAST_SKETCH_STATS))
+        if i < runs - 1:
+            hs.deleteIndex(f"skip{i}")
+            hs.vacuumIndex(f"skip{i}")
+    name = f"skip{runs - 1}"
+    b = _med(builds)
+    out["build"] = {"path": stats[-1].get("path"), "columns": stats[-1].get("columns"),
+                    "create_index_s": round(b, 3), "create_index_first_s": round(builds[0], 3),
+                    "sketched_gb_per_s": round(sketched_bytes / b / 1e9, 2),
+                    "upload_s": round(_med([x["upload_s"] for x in stats]), 4),
+                    "kernels_s": round(_med([x["kernels_s"] for x in stats]), 4),
+                    "groups": stats[-1].get("groups")}
+    entry = [e for e in get_context(s).index_collection_manager.get_indexes()
+             if e.name == name][0]
+    rel = df.queryExecution.optimized_plan.relation
+    ids = {f.name: f.id for f in entry.source_file_info_set}
+    host = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        ht = DS.host_sketch_rows(rel, sorted(ids), entry.derived_dataset.sketches, ids)
+        host.append(time.perf_counter() - t0)
+    out["build"]["host_builder_s"] = round(_med(host), 3)
+    out["build"]["equals_host"] = DS.read_sketch_table(entry).sort_by("_data_file_id").equals(
+        ht.sort_by("_data_file_id"))
+
+    def q_range(i):
+        lo = (17 * i + 3) % nfiles * 1000 + 200
+        return df.filter((col("c") >= lo) & (col("c") < lo + 500)) \
+            .agg(count("*").alias("n"), sum_(col("v")).alias("sv"))
+
+    def q_point(i):
+        f = (29 * i + 5) % nfiles
+        return df.filter(col("id") == int((1000 + i) * nfiles + owner[f])) \
+            .agg(count("*").alias("n"), sum_(col("v")).alias("sv"))
+    if args.device == "gpu":
+        out["kernels_ms"] = _sketch_kernel_times(rel, sorted(ids), per_file, runs)
+    be = s.backend()
+    drop = getattr(be, "_drop_resident", lambda: None)
+
+    def timed(q, i, enabled, cold):
+        (Hyperspace.enable if enabled else Hyperspace.disable)(s)
+        if cold:
+            drop()                        # nothing resident: the scan reads its files
+        _sync(args.device)
+        t0 = time.perf_counter()
+        rows = _rows(q(i))
+        _sync(args.device)
+        return rows, (time.perf_counter() - t0) * 1e3
+    out["queries"] = {}
+    for qname, q in (("range", q_range), ("point", q_point)):
+        res = {"files_read_without_index": nfiles}
+        ok = True
+        # cold: every run starts with an empty device cache; resident: the device cache keeps
+        # what earlier runs loaded (the whole table, once the run without the index read it)
+        for mode, cold in (("cold", True), ("resident", False)):
+            t_on, t_off, kept = [], [], []
+            for i in range(runs):         # alternate: with the index, then without
+                DS.LAST_PRUNE.clear()
+                a, t = timed(q, i, True, cold)
+                t_on.append(t)
+                kept.append(DS.LAST_PRUNE.get("kept"))
+                r, t = timed(q, i, False, cold)
+                t_off.append(t)
+                ok = ok and _close(a, r) and a[0][0] > 0
+            res[mode] = {"with_index_ms": round(_med(t_on), 2),
+                         "without_index_ms": round(_med(t_off), 2)}
+            res["files_read_with_index"] = kept
+        res["path"] = getattr(be, "last_path", None)
+        res["match"] = ok
+        out["queries"][qname] = res
+    files = rel.location.all_files()
+    a = E.Attribute("id", pa.int64())
+    eq = [E.EqualTo(a, E.Literal(int(5 * nfiles + owner[3]), pa.int64()))]
+    inl = [E.In(a, [E.Literal(int(j * nfiles + owner[j % nfiles]), pa.int64())
+                    for j in range(1000)])]
+    DS.prune(entry, files, eq)            # loads the sketch table
+    probe = {}
+    for pname, conj in (("equality", eq), ("in_1000", inl)):
+        ts = []
+        for _ in range(runs):
+            t0 = time.perf_counter()
+            k = DS.prune(entry, files, conj)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        probe[pname] = {"prune_ms": round(_med(ts), 3), "kept": len(k)}
+    out["host_probe"] = probe
+    out["match"] = all(r["match"] for r in out["queries"].values()) and \
+        out["build"]["equals_host"]
+    return out
+
+
 CONFIGS = {"csv10k": config_csv10k, "sf10_filter": config_sf10_filter, "hybrid": config_hybrid,
            "q3_3way": config_q3_3way, "tpcds_3way": config_tpcds_3way,
            "streamed": config_streamed, "like": config_like,
            "count_distinct": config_count_distinct, "window": config_window,
-           "broadcast_join": config_broadcast_join}
+           "broadcast_join": config_broadcast_join, "data_skipping": config_data_skipping}
 
 
 def main():
@@ -1013,6 +1176,8 @@ def main():
                     help="like: timed runs per dictionary size and route (medians reported)")
     ap.add_argument("--probe-sweep", action="store_true",
                     help="broadcast_join: time the hash-join probe kernel alone, per rows per lane")
+    ap.add_argument("--ds-runs", type=int, default=5,
+                    help="data_skipping: runs per measurement (at least 5; medians reported)")
     ap.add_argument("--probe-rows", type=int, default=1 << 26,
                     help="broadcast_join --probe-sweep: stream rows")
     args = ap.parse_args()

@@ -8,10 +8,11 @@ import pyarrow as pa
 from ..exceptions import HyperspaceException
 from ..index import constants as C
 from ..index import signatures as S
+from ..index import dataskipping as DS
 from ..index.builder import build_from_source
 from ..index.config import IndexConfig
-from ..index.log_entry import (Content, CoveringIndex, FileIdTracker, IndexLogEntry,
-                               LogicalPlanFingerprint, Signature, Source, SparkPlan)
+from ..index.log_entry import (Content, CoveringIndex, DataSkippingIndex, FileIdTracker,
+                               IndexLogEntry, LogicalPlanFingerprint, Signature, Source, SparkPlan)
 from ..plan import logical as L
 from ..plan.types import schema_to_json
 from ..telemetry.events import CreateActionEvent
@@ -46,6 +47,13 @@ class CreateActionBase:
 
     def has_lineage(self) -> bool:
         return HyperspaceConf.index_lineage_enabled(self.session.conf)
+
+    def _sketches(self, df, config) -> List[dict]:
+        """``properties.sketches`` of a data-skipping config over ``df`` (columns resolved)."""
+        idx, _ = self.resolve_config(df, config)
+        rel = self._relation(df).relation
+        return DS.resolve_sketches(config, dict(zip(config.indexedColumns, idx)), rel.schema,
+                                   rel.partition_schema.names)
 
     # -- column resolution ------------------------------------------------------------------------
     def resolve_config(self, df, config: IndexConfig) -> Tuple[List[str], List[str]]:
@@ -108,6 +116,16 @@ class CreateActionBase:
         if isinstance(plan, L.LogicalRelation) and mgr.has_parquet_as_source_format(plan):
             props[C.HAS_PARQUET_AS_SOURCE_FORMAT_PROPERTY] = "true"
         abs_path = path if P.is_qualified(path) else P.make_absolute(path)
+        if isinstance(config, DS.DataSkippingIndexConfig):
+            # file ids are the table's key: lineage is always on for this index kind
+            props[C.LINEAGE_PROPERTY] = "true"
+            sketches = self._sketches(df, config)
+            schema = DS.sketch_schema(sketches, self._relation(df).relation.schema)
+            derived = DataSkippingIndex(sketches, schema_to_json(schema), props)
+            return IndexLogEntry(
+                config.indexName, derived, Content.from_directory(abs_path, self.file_id_tracker),
+                Source(SparkPlan(relations, None, None,
+                                 LogicalPlanFingerprint([Signature(provider.name, sig)]))), {})
         return IndexLogEntry(
             config.indexName,
             CoveringIndex(idx, inc, schema_to_json(self.index_schema(df, idx, inc, extra)),
@@ -132,6 +150,12 @@ class CreateActionBase:
               mode: str = "overwrite") -> List[str]:
         """``repartition(numBuckets, indexed) + saveWithBuckets`` (``CreateActionBase.scala:122-140``)."""
         lr = self._relation(df)
+        if isinstance(config, DS.DataSkippingIndexConfig):
+            dist = getattr(self.session, "dist", None)
+            if dist is not None and dist.rank != 0:
+                return []
+            return [DS.write_sketch_table(self.sketch_rows(df, config, files),
+                                          self.index_data_path)]
         idx, inc, extra = self.index_columns(df, config)
         if files is None:
             files = [f.path for f in lr.relation.location.all_files()]
@@ -141,6 +165,19 @@ class CreateActionBase:
         return build_from_source(self.session, lr.relation, files, idx + inc + extra, idx,
                                  self.num_buckets_for_index(), self.index_data_path,
                                  self.lineage_ids(files), mode)
+
+    def sketch_rows(self, df, config, files: Optional[List[str]] = None) -> pa.Table:
+        """The sketch table rows of ``files`` (default: every source file) of a data-skipping
+        index.  Under SPMD rank 0 builds them; the action's barrier holds the other ranks."""
+        lr = self._relation(df)
+        for f in lr.relation.location.all_files():
+            self.file_id_tracker.add_file(f)
+        if files is None:
+            files = [f.path for f in lr.relation.location.all_files()]
+        by_path = {p: v for (p, _, _), v in self.file_id_tracker.get_file_to_id_map().items()}
+        ids = {f: by_path[f] for f in files}
+        return DS.build_sketch_rows(self.session, lr.relation, files, self._sketches(df, config),
+                                    ids)
 
 
 class CreateAction(CreateActionBase, Action):

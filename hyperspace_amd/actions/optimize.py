@@ -59,6 +59,10 @@ class OptimizeAction(CreateActionBase, Action):
         return self._split
 
     def validate(self) -> None:
+        if self.previous_entry.is_data_skipping:
+            raise HyperspaceException(
+                f"optimizeIndex is not supported by index kind "
+                f"{self.previous_entry.derived_dataset.kind}.")
         if self.mode.lower() not in C.OPTIMIZE_MODES:
             raise HyperspaceException(f"Unsupported optimize mode '{self.mode}' found.")
         if not self._files()[0]:

@@ -60,6 +60,8 @@ class RefreshActionBase(CreateActionBase, Action):
     @property
     def index_config(self) -> IndexConfig:
         p = self.previous_entry
+        if p.is_data_skipping:
+            return p.config
         return IndexConfig(p.name, p.indexed_columns, p.included_columns)
 
     def validate(self) -> None:
@@ -114,6 +116,9 @@ class RefreshIncrementalAction(RefreshActionBase):
     def op(self) -> None:
         appended = self.appended_files
         deleted = self.deleted_files
+        if self.previous_entry.is_data_skipping:
+            self._refresh_sketch_table(appended, deleted)
+            return
         if appended:
             self.write(self.df, self.index_config, files=[f.name for f in appended])
         if deleted:
@@ -131,8 +136,29 @@ class RefreshIncrementalAction(RefreshActionBase):
                 "Index refresh (to handle deleted source data) is only supported on an index with "
                 "lineage.")
 
+    def _refresh_sketch_table(self, appended, deleted) -> None:
+        """Data-skipping index: the previous version's rows without the deleted files' rows,
+        plus rows built for the appended files, as the new version's one file."""
+        import pyarrow as pa
+        import pyarrow.compute as pc
+        from ..index import constants as C
+        from ..index import dataskipping as DS
+        dist = getattr(self.session, "dist", None)
+        if dist is not None and dist.rank != 0:
+            return
+        t = DS.read_sketch_table(self.previous_entry)
+        if deleted:
+            gone = pa.array([f.id for f in deleted], pa.int64())
+            t = t.filter(pc.invert(pc.is_in(t.column(C.DATA_FILE_NAME_ID), value_set=gone)))
+        if appended:
+            new = self.sketch_rows(self.df, self.index_config, [f.name for f in appended])
+            t = pa.concat_tables([t, new.cast(t.schema)])
+        DS.write_sketch_table(t, self.index_data_path)
+
     def log_entry(self):
         entry = self.get_index_log_entry(self.df, self.index_config, self.index_data_path)
+        if self.previous_entry.is_data_skipping:
+            return entry       # the new version's file holds every row
         if not self.deleted_files:
             merged = Content(self.previous_entry.content.root.merge(entry.content.root))
             return entry.copy(content=merged)
@@ -150,6 +176,10 @@ class RefreshQuickAction(RefreshActionBase):
 
     def validate(self) -> None:
         super().validate()
+        if self.previous_entry.is_data_skipping:
+            raise HyperspaceException(
+                f"Quick refresh is not supported by index kind "
+                f"{self.previous_entry.derived_dataset.kind}.")
         if not self.appended_files and not self.deleted_files:
             raise NoChangesException("Refresh quick aborted as no source data change found.")
         if self.deleted_files and not self.previous_entry.has_lineage_column:

@@ -84,7 +84,13 @@ class CpuBackend:
         return pa.Table.from_arrays(arrays, schema=_schema(p.output))
 
     def _exec_FileSourceScanExec(self, p):
-        files = [f.path for f in p.relation.location.all_files()]
+        statuses = p.relation.location.all_files()
+        if p.relation.skipping is not None:
+            # data-skipping index: drop the files its sketches rule out for the filter's
+            # literals as they are in this execution (a cached plan carries new ones each time)
+            from ..index.dataskipping import prune
+            statuses = prune(p.relation.skipping, statuses, p.data_filters)
+        files = [f.path for f in statuses]
         if p.use_bucketing:
             n = p.relation.bucket_spec.num_buckets
             groups: Dict[int, list] = {}

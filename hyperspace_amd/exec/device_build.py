@@ -619,6 +619,21 @@ def _footer_info(path: str, names: List[str]):
     return md.num_rows, maybe
 
 
+def source_row_counts(files: List[str], columns: List[str]) -> List[int]:
+    """Row count of every Parquet source file, from its footer (``_footer_info``)."""
+    from . import staging
+    return [int(r) for r, _ in staging.io_pool().map(lambda f: _footer_info(f, columns), files)]
+
+
+def upload_source_columns(rel, files: List[str], columns: List[str], device) -> dict:
+    """``columns`` of the Parquet source ``files`` of ``rel`` as device columns, rows in file
+    order: the index build's upload (``_upload_parquet``) for a single-rank consumer that
+    indexes nothing itself, such as a sketch build (exec/device_sketch.py)."""
+    _T0[0] = time.perf_counter()
+    cols, _, _ = _upload_parquet(rel, files, columns, [], None, device, None)
+    return cols
+
+
 def _upload_parquet(rel, my_files, columns, indexed, lineage_ids, device, dist, xs=None,
                     nullable_override=None):
     """Pipelined decode -> pinned -> HBM upload of this rank's Parquet files (staging.py).

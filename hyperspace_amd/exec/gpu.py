@@ -49,7 +49,8 @@ from .graphs import GraphCache
 from .hbm_budget import rank_budget
 from .staging import RESERVE_BLOCK as _RESERVE_BLOCK
 from .gpu_common import (arrow_table, _AggProgram, _needs_eval, _prefix_sorted,
-                         _warm_torch_kernels, DRel, log, QueryFuture, Unsupported)
+                         _warm_torch_kernels, DRel, log, QueryFuture, skipping_scan,
+                         Unsupported)
 from .gpu_agg import AggOps
 from .gpu_hash import HashAggOps
 from .gpu_hash_join import HashJoinOps
@@ -250,6 +251,10 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
         cand = self._prog_candidate
         self._prog_candidate = None
         if cand is None or not HyperspaceConf.prepared_submit_enabled(self.session.conf):
+            return
+        if skipping_scan(plan):
+            # a data-skipping scan loads the files its sketches keep for this execution's
+            # literals: a program replayed over the table of other literals would be wrong
             return
         m = self._match_agg(plan)
         if m is None or m[0] is not cand[0]:
@@ -707,6 +712,9 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
             "spark.hyperspace.mi.bucketPlacement", "balanced")) if d is not None else None
         tag = (tag, getattr(self, "_bucket_chunk", None),
                self.session.conf.get("spark.hyperspace.mi.hybridScanMerge.enabled", "true"))
+        if p.relation.skipping is not None:
+            # the kept files depend on this execution's literals: never a memoized table
+            return self._scan(p)
         memo = self.__dict__.setdefault("_scans", {})
         m = memo.get(id(p))
         if m is not None and m[0] is p and m[2] == tag and m[1].table is not None and \
@@ -727,6 +735,12 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
         rel = p.relation
         if files is None:
             files = rel.location.all_files()
+            if rel.skipping is not None:
+                from ..index.dataskipping import prune
+                kept = prune(rel.skipping, files, p.data_filters)
+                # every file ruled out: scan the smallest one (the filter above drops its rows)
+                # so the operators downstream still see a loaded table
+                files = kept or sorted(files, key=lambda f: (f.length, f.path))[:1]
         d = self._dist()
         rank, world = (d.rank, d.world) if d is not None else (0, 1)
         names = [a.name for a in p.output]

@@ -19,7 +19,7 @@ from .graphs import _cbuf, GraphPending as _GraphPending, range_bounds, ScanAggG
 from .pairing import HeldQuery
 from .gpu_common import (arrow_table, _compact_buffers, _eval_scalar, _GraphPrep, _group_limit,
                          _JoinPrep, _NeedHash, _ScanPrep, _Stale, _use_on, bucket_chunks, DRel,
-                         GROUP_LDS_SCAN, log, MAX_GROUPS_SCAN, Unsupported)
+                         GROUP_LDS_SCAN, log, MAX_GROUPS_SCAN, skipping_scan, Unsupported)
 
 
 class AggOps:
@@ -279,7 +279,7 @@ class AggOps:
         dependent) whose lowering completed."""
         st = getattr(self, "_scan_gs", None)
         if st is None or r.parts or r.extra or r.split or \
-                getattr(r.table, "_hs_cache_key", None) is None:
+                getattr(r.table, "_hs_cache_key", None) is None or skipping_scan(final):
             return
         col_info, descs, gs, p = st
         preps = self.__dict__.setdefault("_agg_preps", {})
@@ -294,7 +294,7 @@ class AggOps:
         bucket ranges, resident tables) for its next submission."""
         rec = getattr(self, "_join_rec", None)
         self._join_rec = None
-        if rec is None or res is None or rec[6] is None:
+        if rec is None or res is None or rec[6] is None or skipping_scan(final):
             return
         left, right, lk, rk, col_info, descs, launcher, specs, lconds = rec
         for t in (left.table, right.table):

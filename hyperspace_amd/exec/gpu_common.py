@@ -263,6 +263,13 @@ def _eval_scalar(e, agg_val, attr_val):
     raise Unsupported(f"result expression {type(e).__name__}")
 
 
+def skipping_scan(plan) -> bool:
+    """Whether a scan under ``plan`` carries a data-skipping index: the files it loads depend
+    on each execution's literals, so nothing lowered over its table is kept for the next."""
+    return bool(plan.collect(lambda x: isinstance(x, X.FileSourceScanExec) and
+                             x.relation.skipping is not None))
+
+
 _SEMI_LITS: dict = {}
 
 

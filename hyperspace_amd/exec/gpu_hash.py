@@ -16,7 +16,8 @@ from ..utils.tracing import stage
 from . import compile as CP, jit
 from .arrow_eval import key
 from .gpu_common import (arrow_table, _HashPrep, _eval_vec, _fd_columns, _finalize_array,
-                         _gather_tables, DRel, H_TOPK_K, TOPK_MIN_GROUPS, Unsupported)
+                         _gather_tables, DRel, H_TOPK_K, skipping_scan, TOPK_MIN_GROUPS,
+                         Unsupported)
 
 
 class HashAggOps:
@@ -611,8 +612,9 @@ class HashAggOps:
 
     def _hash_prep_put(self, final, order, limit, node, launches, setup):
         """Keep a hash-mode join aggregate's setup for its next submission: one join launch
-        over resident tables (no bucket-union parts, no computed columns)."""
-        if len(launches) != 1 or launches[0][0] != "join":
+        over resident tables (no bucket-union parts, no computed columns).  Never over a
+        data-skipping scan: its tables hold the files kept for this submission's literals."""
+        if len(launches) != 1 or launches[0][0] != "join" or skipping_scan(final):
             return None
         _, a, b = launches[0]
         if a.parts or b.parts or a.extra or b.extra or a.split or b.split or \

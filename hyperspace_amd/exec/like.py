@@ -183,10 +183,11 @@ _BITMAPS: "OrderedDict[tuple, tuple]" = OrderedDict()
 _BITMAPS_CAP = 64
 
 
-def device_dictionary(dictionary: pa.Array, device) -> DeviceDictionary:
+def device_dictionary(dictionary: pa.Array, device, cache: bool = True) -> DeviceDictionary:
     """``dictionary`` on ``device``: uploaded once per dictionary object
     (``ops.kernels.dictionary_bytes``, shared with the device hash of dictionary columns) and
-    counted against the table caches' budgets while it lives."""
+    counted against the table caches' budgets while it lives.  ``cache`` false: for a
+    dictionary used once (a sketch build's file group); it is not kept and not counted."""
     from ..ops import kernels as K
     from .device_cache import track_derived
     key = (id(dictionary), str(device))
@@ -194,6 +195,10 @@ def device_dictionary(dictionary: pa.Array, device) -> DeviceDictionary:
     if hit is not None and hit.dictionary is dictionary:
         _DEV_DICTS.move_to_end(key)
         return hit
+    if not cache:
+        offs, chars = K.dictionary_bytes(dictionary, device, cache=False)
+        return DeviceDictionary(dictionary, offs, chars, len(dictionary),
+                                dictionary_max_len(dictionary))
     offs, chars = K.dictionary_bytes(dictionary, device)
     track_derived(offs)
     track_derived(chars)

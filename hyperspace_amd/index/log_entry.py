@@ -235,6 +235,53 @@ class CoveringIndex:
                              o.get("kind", "CoveringIndex"), o.get("kindAbbr", "CI"))
 
 
+@dataclass
+class DataSkippingIndex:
+    """Per-source-file sketches (``index/dataskipping.py``).  ``sketches``: one dict per sketch,
+    ``{type, column, fpp?, expectedDistinctCountPerFile?, numBits?, numHashFunctions?}``;
+    ``schema_string``: the sketch table's schema."""
+    sketches: List[dict]
+    schema_string: str
+    properties: Dict[str, str] = field(default_factory=dict)
+    kind: str = "DataSkippingIndex"
+    kind_abbr: str = "DS"
+
+    @property
+    def indexed(self) -> List[str]:
+        out: List[str] = []
+        for s in self.sketches:
+            if s["column"] not in out:
+                out.append(s["column"])
+        return out
+
+    @property
+    def included(self) -> List[str]:
+        return []
+
+    @property
+    def num_buckets(self) -> int:
+        return 0
+
+    def to_json_obj(self):
+        return {"properties": {"sketches": [dict(s) for s in self.sketches],
+                               "schemaString": self.schema_string,
+                               "properties": dict(self.properties)},
+                "kind": self.kind, "kindAbbr": self.kind_abbr}
+
+    @staticmethod
+    def from_json_obj(o) -> "DataSkippingIndex":
+        p = o["properties"]
+        return DataSkippingIndex([dict(s) for s in p["sketches"]], p["schemaString"],
+                                 dict(p.get("properties") or {}),
+                                 o.get("kind", "DataSkippingIndex"), o.get("kindAbbr", "DS"))
+
+
+def derived_dataset_from_json_obj(o):
+    if o.get("kind", "CoveringIndex") == "DataSkippingIndex":
+        return DataSkippingIndex.from_json_obj(o)
+    return CoveringIndex.from_json_obj(o)
+
+
 @dataclass(frozen=True)
 class Signature:
     provider: str
@@ -387,7 +434,7 @@ class IndexLogEntry(LogEntry):
 
     @staticmethod
     def from_json_obj(o) -> "IndexLogEntry":
-        e = IndexLogEntry(o["name"], CoveringIndex.from_json_obj(o["derivedDataset"]),
+        e = IndexLogEntry(o["name"], derived_dataset_from_json_obj(o["derivedDataset"]),
                           Content.from_json_obj(o["content"]),
                           Source(SparkPlan.from_json_obj(o["source"]["plan"])),
                           dict(o.get("properties") or {}))
@@ -490,8 +537,19 @@ class IndexLogEntry(LogEntry):
 
     @property
     def config(self):
+        if self.is_data_skipping:
+            from .dataskipping import config_of
+            return config_of(self.name, self.derived_dataset.sketches)
         from .config import IndexConfig
         return IndexConfig(self.name, self.indexed_columns, self.included_columns)
+
+    @property
+    def is_covering(self) -> bool:
+        return self.derived_dataset.kind == "CoveringIndex"
+
+    @property
+    def is_data_skipping(self) -> bool:
+        return self.derived_dataset.kind == "DataSkippingIndex"
 
     @property
     def signature(self) -> Signature:

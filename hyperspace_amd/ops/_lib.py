@@ -266,6 +266,11 @@ def lib():
     _sig(L.hs_hj_build, I, P, I64, P, I64, P, P, P, I64, P)
     _sig(L.hs_hj_probe, I, P, I64, P, I64, P, P, P, P, I64, I64, I, I, P, P, P, P, P)
     _sig(L.hs_hj_emit, I, P, I64, P, P, I64, P, P, P, I64, I64, I, P, P, P)
+    _sig(L.hs_sketch_slab_rows, I)
+    _sig(L.hs_sketch_bloom_lds_words, I)
+    _sig(L.hs_sketch_minmax, I, P, P, I64, P, I64, P, P, P, P, P, P, P)
+    _sig(L.hs_sketch_bloom, I, P, P, P, I64, P, I64, I, I, P, P, P)
+    _sig(L.hs_sketch_hash_entries, I, P, P, I64, P, P)
     _lib = L
     return L
 

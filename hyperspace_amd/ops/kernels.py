@@ -43,9 +43,10 @@ def hash_xform(atype) -> int:
 _DICT_BYTES: dict = {}
 
 
-def dictionary_bytes(dictionary, device):
+def dictionary_bytes(dictionary, device, cache: bool = True):
     """(int64 offsets [n+1], uint8 chars) of a string dictionary on the device, uploaded once
-    per dictionary object (the entry keeps a reference, so its id is not reused)."""
+    per dictionary object (the entry keeps a reference, so its id is not reused).  ``cache``
+    false: a dictionary used once (a build's file group) is uploaded without being kept."""
     import numpy as np
     import pyarrow as pa
     torch = _torch()
@@ -65,6 +66,8 @@ def dictionary_bytes(dictionary, device):
     o = torch.from_numpy((offs - base).copy()).to(device)
     ch = torch.from_numpy(np.ascontiguousarray(chars) if len(chars) else np.zeros(1, np.uint8)) \
         .to(device)
+    if not cache:
+        return o, ch
     if len(_DICT_BYTES) > 256:
         _DICT_BYTES.clear()
     _DICT_BYTES[key] = (dictionary, o, ch)
@@ -1114,3 +1117,125 @@ def join_pairs(params: NL.JoinParams, rstart, rlen, rbucket, roff, max_tiles: in
                             grid, NL.ptr(offs), NL.ptr(ol), NL.ptr(orr), NL.stream_ptr()),
              "hs_join_emit")
     return ol[:total], orr[:total]
+
+
+# ------------------------------------------------------------------------------------------------
+# data-skipping sketches (csrc/kernels/sketch.hip)
+# ------------------------------------------------------------------------------------------------
+def sketch_slab_rows() -> int:
+    return int(NL.lib().hs_sketch_slab_rows())
+
+
+def sketch_bloom_lds_words() -> int:
+    """Largest filter (64-bit words) ``sketch_bloom`` builds in LDS; above it, global atomics."""
+    return int(NL.lib().hs_sketch_bloom_lds_words())
+
+
+def sketch_slabs(file_rows: Sequence[int], slab_rows: int):
+    """The (file, slab) work list of files holding ``file_rows`` rows back to back: an
+    ``(nslabs, 3)`` int64 array of {file, first row, end row} and the ``nfiles + 1`` offsets of
+    each file's slabs in it.  A file without rows has no slab."""
+    rows = np.asarray(list(file_rows), dtype=np.int64)
+    if (rows < 0).any():
+        raise ValueError("negative file row count")
+    starts = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    per_file = -(-rows // slab_rows)
+    off = np.concatenate([[0], np.cumsum(per_file)]).astype(np.int64)
+    n = int(off[-1])
+    file_of = np.repeat(np.arange(len(rows), dtype=np.int64), per_file)
+    within = np.arange(n, dtype=np.int64) - off[:-1][file_of]
+    first = starts[:-1][file_of] + within * slab_rows
+    end = np.minimum(first + slab_rows, starts[1:][file_of])
+    return np.stack([file_of, first, end], axis=1).reshape(-1, 3), off
+
+
+def _sketch_work(col, file_rows):
+    torch = _torch()
+    slabs, off = sketch_slabs(file_rows, sketch_slab_rows())
+    total = int(np.sum(np.asarray(list(file_rows), dtype=np.int64)))
+    if total != len(col) or (col.valid is not None and col.valid.numel() != total):
+        raise ValueError(f"sketch: files hold {total} rows, the column {len(col)}")
+    dev = col.data.device
+    both = torch.from_numpy(np.concatenate([slabs.reshape(-1), off])).to(dev)
+    return both[:slabs.size], both[slabs.size:], slabs.shape[0], len(off) - 1
+
+
+def _from_image(img: np.ndarray, dtype: np.dtype) -> np.ndarray:
+    """Values of the order-preserving unsigned images ``sketch_minmax`` reduces on."""
+    dtype = np.dtype(dtype)
+    img = img.astype(np.uint64)
+    if dtype.kind == "i":
+        bits = dtype.itemsize * 8
+        u = (img ^ np.uint64(1 << (bits - 1))).astype(f"u{dtype.itemsize}")
+        return u.view(dtype)
+    top = np.uint64(1 << (dtype.itemsize * 8 - 1))
+    mask = np.uint64((1 << (dtype.itemsize * 8)) - 1)
+    b = np.where(img & top, img ^ top, ~img & mask)
+    return b.astype(f"u{dtype.itemsize}").view(dtype)
+
+
+def sketch_minmax(col, file_rows: Sequence[int]):
+    """(min, max, non-null count) per file of device column ``col``, whose rows are those of
+    files with ``file_rows`` rows back to back.  min / max are numpy arrays in the column's
+    storage type, in Spark's order (floats: NaN largest, -0.0 stored as 0.0), meaningful where
+    the count is not 0.  One host readback of 3 words per file."""
+    torch = _torch()
+    if col.hs_type not in (NL.I8, NL.I16, NL.I32, NL.I64, NL.F32, NL.F64):
+        raise ValueError(f"sketch_minmax: unsupported storage type {col.data.dtype}")
+    slabs, off, ns, nf = _sketch_work(col, file_rows)
+    dev = col.data.device
+    part = torch.empty(3 * max(ns, 1), dtype=torch.int64, device=dev)
+    out = torch.empty(3 * max(nf, 1), dtype=torch.int64, device=dev)
+    p, o = max(ns, 1), max(nf, 1)
+    desc = col.desc()
+    NL.check(NL.lib().hs_sketch_minmax(
+        C.byref(desc), NL.ptr(slabs), ns, NL.ptr(off), nf, NL.ptr(part[:p]), NL.ptr(part[p:2 * p]),
+        NL.ptr(part[2 * p:]), NL.ptr(out[:o]), NL.ptr(out[o:2 * o]), NL.ptr(out[2 * o:]),
+        NL.stream_ptr()), "hs_sketch_minmax")
+    h = out.cpu().numpy()
+    np_dtype = np.dtype(str(col.data.dtype).replace("torch.", ""))
+    cnt = h[2 * o:2 * o + nf].copy()
+    mn = _from_image(h[:nf].view(np.uint64), np_dtype)
+    mx = _from_image(h[o:o + nf].view(np.uint64), np_dtype)
+    return mn, mx, cnt
+
+
+def sketch_hash_entries(dev_dict):
+    """``(n, 2)`` int32 device tensor of Spark Murmur3 ``hashUnsafeBytes(entry, 0)`` and
+    ``hashUnsafeBytes(entry, h1)`` per entry of ``dev_dict`` (``exec.like.DeviceDictionary``)."""
+    torch = _torch()
+    n = int(dev_dict.n)
+    out = torch.empty((n, 2), dtype=torch.int32, device=dev_dict.offsets.device)
+    NL.check(NL.lib().hs_sketch_hash_entries(NL.ptr(dev_dict.chars), NL.ptr(dev_dict.offsets), n,
+                                             NL.ptr(out), NL.stream_ptr()),
+             "hs_sketch_hash_entries")
+    return out
+
+
+def sketch_bloom(col, file_rows: Sequence[int], num_words: int, k: int, entry_hashes=None):
+    """``(nfiles, num_words)`` int64 device words of the per-file Bloom filters (Spark
+    ``BloomFilterImpl`` bit positions, ``k`` hash functions) of the non-null values of ``col``:
+    integers hashed as int64, or int32 dictionary codes hashed through ``entry_hashes``
+    (``sketch_hash_entries`` of the column's dictionary)."""
+    torch = _torch()
+    num_words, k = int(num_words), int(k)
+    if not 1 <= num_words <= (1 << 20) or k < 1:
+        raise ValueError("sketch_bloom: bad filter size")
+    if entry_hashes is not None:
+        if col.hs_type != NL.I32:
+            raise ValueError("sketch_bloom: dictionary codes must be int32")
+        if entry_hashes.numel() == 0 and len(col) and col.valid is None:
+            raise ValueError("sketch_bloom: codes without dictionary entries")
+    elif col.hs_type not in (NL.I8, NL.I16, NL.I32, NL.I64):
+        raise ValueError(f"sketch_bloom: unsupported storage type {col.data.dtype}")
+    slabs, off, ns, nf = _sketch_work(col, file_rows)
+    dev = col.data.device
+    out = torch.empty((nf, num_words), dtype=torch.int64, device=dev)
+    partials = None
+    if num_words <= sketch_bloom_lds_words():
+        partials = torch.empty(max(ns, 1) * num_words, dtype=torch.int64, device=dev)
+    desc = col.desc()
+    NL.check(NL.lib().hs_sketch_bloom(
+        C.byref(desc), NL.ptr(entry_hashes), NL.ptr(slabs), ns, NL.ptr(off), nf, num_words, k,
+        NL.ptr(partials), NL.ptr(out), NL.stream_ptr()), "hs_sketch_bloom")
+    return out

@@ -80,10 +80,21 @@ class FileIndex:
         return f"{self.kind}[{', '.join(self.root_paths)}]"
 
 
+class DataSkippingFileIndex(FileIndex):
+    """The source listing of a relation that a data-skipping index is attached to
+    (``HadoopFsRelation.skipping``).  ``all_files()`` is still the full listing: the executors
+    prune it per execution, with the literal values of that execution."""
+
+    kind = "DataSkippingFileIndex"
+
+    def __init__(self, base: FileIndex):
+        super().__init__(base.root_paths, base.all_files(), base.partition_spec)
+
+
 class HadoopFsRelation:
     def __init__(self, location: FileIndex, partition_schema: pa.Schema, data_schema: pa.Schema,
                  bucket_spec: Optional[BucketSpec], file_format: str, options: dict,
-                 index=None):
+                 index=None, skipping=None):
         self.location = location
         self.partition_schema = partition_schema if partition_schema is not None else pa.schema([])
         self.data_schema = data_schema
@@ -91,6 +102,9 @@ class HadoopFsRelation:
         self.file_format = file_format
         self.options = dict(options or {})
         self.index = index  # IndexLogEntry when this is an IndexHadoopFsRelation
+        # IndexLogEntry of a data-skipping index: still the source relation (is_index() stays
+        # false); its scan drops files by the index's sketches when it executes
+        self.skipping = skipping
 
     @property
     def schema(self) -> pa.Schema:
@@ -106,7 +120,8 @@ class HadoopFsRelation:
                                 kw.get("bucket_spec", self.bucket_spec),
                                 kw.get("file_format", self.file_format),
                                 kw.get("options", self.options),
-                                kw.get("index", self.index))
+                                kw.get("index", self.index),
+                                kw.get("skipping", self.skipping))
 
     def is_index(self) -> bool:
         return self.index is not None

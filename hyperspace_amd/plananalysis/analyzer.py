@@ -131,14 +131,19 @@ def explain_string(df, session, indexes_df, verbose: bool) -> str:
 
 def _write_used_indexes(plan, indexes_df, out):
     paths = set()
+    skipping = set()
     for p in plan.iter_pre():
         if isinstance(p, X.FileSourceScanExec):
             for r in p.relation.location.root_paths:
                 paths.add(P.get_parent(r))
                 paths.add(r)
+            if p.relation.skipping is not None:
+                # a data-skipping index leaves the scan on the source's paths
+                skipping.add(p.relation.skipping.name)
     t: pa.Table = indexes_df.to_arrow()
     for name, loc in zip(t.column("name").to_pylist(), t.column("indexLocation").to_pylist()):
-        if loc in paths or any(x.startswith(loc.rstrip("/") + "/") for x in paths):
+        if name in skipping or loc in paths or \
+                any(x.startswith(loc.rstrip("/") + "/") for x in paths):
             out.write_line(f"{name}:{loc}")
 
 

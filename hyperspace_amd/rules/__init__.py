@@ -1,15 +1,17 @@
 """Hyperspace optimizer rules and their registration (reference ``package.scala:25-79``).
 
-``enable`` installs ``JoinIndexRule`` then ``FilterIndexRule`` (join first: order matters) plus
+``enable`` installs ``JoinIndexRule`` then ``FilterIndexRule`` (join first: order matters), then
+``ApplyDataSkipping`` for the source relations the covering-index rules left alone, plus
 ``BucketUnionStrategy``; it first removes existing entries so it is idempotent.
 """
 from __future__ import annotations
 
+from .data_skipping_rule import ApplyDataSkipping
 from .filter_rule import FilterIndexRule
 from .join_rule import JoinIndexRule
 from .bucket_union_strategy import BucketUnionStrategy
 
-HYPERSPACE_RULES = (JoinIndexRule, FilterIndexRule)
+HYPERSPACE_RULES = (JoinIndexRule, FilterIndexRule, ApplyDataSkipping)
 
 
 def enable(session) -> None:

@@ -50,7 +50,8 @@ def find_covering_indexes(session, filt, out_cols, filt_cols) -> list:
         return []
     all_idx = get_context(session).index_collection_manager.get_indexes([states.ACTIVE])
     cands = [i for i in all_idx
-             if index_covers_plan(session, out_cols, filt_cols, i.indexed_columns, i.included_columns)]
+             if i.is_covering and index_covers_plan(session, out_cols, filt_cols,
+                                                    i.indexed_columns, i.included_columns)]
     return RU.get_candidate_indexes(session, cands, rel)
 
 

@@ -123,7 +123,9 @@ def _is_compatible(li, ri, mapping) -> bool:
 
 def get_best_index_pair(session, left, right, cond):
     from ..hyperspace import get_context
-    all_idx = get_context(session).index_collection_manager.get_indexes([states.ACTIVE])
+    all_idx = [i for i in
+               get_context(session).index_collection_manager.get_indexes([states.ACTIVE])
+               if i.is_covering]
     lbase = [a.name for a in _relation_outputs(left)]
     rbase = [a.name for a in _relation_outputs(right)]
     mapping = _lr_column_mapping(session, lbase, rbase, cond)
