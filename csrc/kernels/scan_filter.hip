@@ -123,6 +123,28 @@ __global__ __launch_bounds__(64 * RANGE_WAVES) void hs_range_search_dev_kernel(
             (uint64_t)bp[4], (int)bp[5], rstart, rlen, rbucket);
 }
 
+// The same search with everything in ONE by-value struct, the bounds included (has_lo, lo,
+// lo_incl, has_hi, hi, hi_incl as int64): a captured pipeline's replay rewrites the struct like a
+// generated kernel's argument block, so the bounds need no H2D copy node.
+struct RangeValArgs {
+  ColDesc key;
+  const int64_t* bucket_off;
+  const int32_t* buckets;
+  int64_t* rstart;
+  int64_t* rlen;
+  int32_t* rbucket;
+  int64_t bp[6];
+  int32_t nb;
+  int32_t pad;
+};
+
+__global__ __launch_bounds__(64 * RANGE_WAVES) void hs_range_search_val_kernel(RangeValArgs a) {
+  const int i = blockIdx.x * RANGE_WAVES + (threadIdx.x >> 6);
+  if (i >= a.nb) return;
+  range_one(a.key, a.bucket_off, a.buckets, i, (int)a.bp[0], (uint64_t)a.bp[1], (int)a.bp[2],
+            (int)a.bp[3], (uint64_t)a.bp[4], (int)a.bp[5], a.rstart, a.rlen, a.rbucket);
+}
+
 // ranges -> tile prefix (ONE wavefront, R arbitrary): tile_prefix[R] = total tiles.
 // rstart != nullptr: each range is widened down to a multiple of `align` rows first (the tiling of
 // the vectorized generated kernels, which load `align` consecutive rows per thread).
@@ -220,15 +242,16 @@ __global__ __launch_bounds__(SF_BLOCK) void hs_scan_agg_kernel(
   acc_flush<GROUPED, SF_BLOCK>(acc, p.aggs, A, GA, gl, psum, pcnt, pmin, pmax);
 }
 
-// Deterministic final reduction: one workgroup per output slot, fixed-order tree.
-__global__ __launch_bounds__(FIN_BLOCK) void hs_agg_final_kernel(
+// Deterministic final reduction of output slot ``i`` by one workgroup of FIN_BLOCK threads, in a
+// fixed order: lane t sums partials t, t + FIN_BLOCK, ..., then the wave butterfly, then the
+// waves in order.  The totals are valid in thread 0 (returns true there).  Shared by
+// hs_agg_final_kernel and hs_agg_fold_kernel, whose results must agree bit for bit.
+__device__ __forceinline__ bool agg_final_slot(
     const double* __restrict__ psum, const int64_t* __restrict__ pcnt,
-    const double* __restrict__ pmin, const double* __restrict__ pmax, int nblk, int GA,
-    double* __restrict__ osum, int64_t* __restrict__ ocnt, double* __restrict__ omin,
-    double* __restrict__ omax) {
+    const double* __restrict__ pmin, const double* __restrict__ pmax, int nblk, int GA, int i,
+    double& ts, int64_t& tc, double& tmn, double& tmx) {
   __shared__ double rs[FIN_BLOCK / 64], rmn[FIN_BLOCK / 64], rmx[FIN_BLOCK / 64];
   __shared__ int64_t rc[FIN_BLOCK / 64];
-  const int i = blockIdx.x;
   double s = 0.0, mn = __builtin_inf(), mx = -__builtin_inf();
   int64_t c = 0;
 #pragma unroll 4
@@ -251,19 +274,77 @@ __global__ __launch_bounds__(FIN_BLOCK) void hs_agg_final_kernel(
     rmx[w] = mx;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double ts = 0.0, tmn = __builtin_inf(), tmx = -__builtin_inf();
-    int64_t tc = 0;
-    for (int k = 0; k < FIN_BLOCK / 64; ++k) {
-      ts += rs[k];
-      tc += rc[k];
-      tmn = fmin(tmn, rmn[k]);
-      tmx = fmax(tmx, rmx[k]);
-    }
+  if (threadIdx.x != 0) return false;
+  ts = 0.0, tmn = __builtin_inf(), tmx = -__builtin_inf();
+  tc = 0;
+  for (int k = 0; k < FIN_BLOCK / 64; ++k) {
+    ts += rs[k];
+    tc += rc[k];
+    tmn = fmin(tmn, rmn[k]);
+    tmx = fmax(tmx, rmx[k]);
+  }
+  return true;
+}
+
+// Deterministic final reduction: one workgroup per output slot, fixed-order tree.
+__global__ __launch_bounds__(FIN_BLOCK) void hs_agg_final_kernel(
+    const double* __restrict__ psum, const int64_t* __restrict__ pcnt,
+    const double* __restrict__ pmin, const double* __restrict__ pmax, int nblk, int GA,
+    double* __restrict__ osum, int64_t* __restrict__ ocnt, double* __restrict__ omin,
+    double* __restrict__ omax) {
+  const int i = blockIdx.x;
+  double ts, tmn, tmx;
+  int64_t tc;
+  if (agg_final_slot(psum, pcnt, pmin, pmax, nblk, GA, i, ts, tc, tmn, tmx)) {
     osum[i] = ts;
     ocnt[i] = tc;
     omin[i] = tmn;
     omax[i] = tmx;
+  }
+}
+
+// The final reduction of one or two partial sets that also delivers the result: workgroup
+// (set, slot) folds its slot as hs_agg_final_kernel does and writes it into the set's device
+// result block (where given) and into its host result block (pinned, mapped), both in the layout
+// sum | count | min | max of 8 * GA bytes each.  A captured pipeline ends in this one kernel: no
+// copy node, and the host block's address travels in the by-value argument struct, which a
+// replay rewrites like a generated kernel's block.
+struct AggFoldSet {
+  const double* psum;
+  const int64_t* pcnt;
+  const double* pmin;
+  const double* pmax;
+  unsigned char* dout;   // device result block, or nullptr
+  unsigned char* hout;   // host result block
+  int32_t nblk;
+  int32_t pad;
+};
+
+struct AggFoldArgs {
+  int32_t GA;
+  int32_t nsets;   // 1 or 2
+  AggFoldSet set[2];
+};
+
+__device__ __forceinline__ void agg_fold_store(unsigned char* __restrict__ out, int GA, int i,
+                                               double ts, int64_t tc, double tmn, double tmx) {
+  const size_t n = (size_t)8 * GA;
+  ((double*)out)[i] = ts;
+  ((int64_t*)(out + n))[i] = tc;
+  ((double*)(out + 2 * n))[i] = tmn;
+  ((double*)(out + 3 * n))[i] = tmx;
+}
+
+__global__ __launch_bounds__(FIN_BLOCK) void hs_agg_fold_kernel(AggFoldArgs a) {
+  const int k = blockIdx.x / a.GA, i = blockIdx.x - k * a.GA;
+  if (k >= a.nsets) return;   // (block-uniform)
+  const AggFoldSet st = k == 0 ? a.set[0] : a.set[1];   // (no dynamic index into the kernarg)
+  double ts, tmn, tmx;
+  int64_t tc;
+  if (agg_final_slot(st.psum, st.pcnt, st.pmin, st.pmax, st.nblk, a.GA, i, ts, tc, tmn, tmx)) {
+    if (st.dout != nullptr) agg_fold_store(st.dout, a.GA, i, ts, tc, tmn, tmx);
+    agg_fold_store(st.hout, a.GA, i, ts, tc, tmn, tmx);
+    __threadfence_system();
   }
 }
 
@@ -433,6 +514,33 @@ int hs_agg_final(const double* psum, const int64_t* pcnt, const double* pmin, co
   if (GA <= 0) return 0;
   hipLaunchKernelGGL(hs_agg_final_kernel, dim3(GA), dim3(FIN_BLOCK), 0, (hipStream_t)stream, psum,
                      pcnt, pmin, pmax, nblk, GA, osum, ocnt, omin, omax);
+  return (int)hipGetLastError();
+}
+
+int hs_agg_fold_args_size() { return (int)sizeof(AggFoldArgs); }
+
+// The function a captured kernel node of hs_agg_fold carries (hipKernelNodeParams::func): for a
+// kernel launched through the runtime API that is the host stub's address.
+void* hs_agg_fold_func() { return (void*)hs_agg_fold_kernel; }
+
+int hs_agg_fold(const AggFoldArgs* a, void* stream) {
+  if (a->GA <= 0) return 0;
+  if (a->nsets < 1 || a->nsets > 2) return -1;
+  for (int k = 0; k < a->nsets; ++k)
+    if (a->set[k].hout == nullptr || a->set[k].nblk < 0) return -1;
+  hipLaunchKernelGGL(hs_agg_fold_kernel, dim3(a->nsets * a->GA), dim3(FIN_BLOCK), 0,
+                     (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+}
+
+int hs_range_search_val_args_size() { return (int)sizeof(RangeValArgs); }
+
+void* hs_range_search_val_func() { return (void*)hs_range_search_val_kernel; }
+
+int hs_range_search_val(const RangeValArgs* a, void* stream) {
+  if (a->nb <= 0) return 0;
+  hipLaunchKernelGGL(hs_range_search_val_kernel, dim3((a->nb + RANGE_WAVES - 1) / RANGE_WAVES),
+                     dim3(64 * RANGE_WAVES), 0, (hipStream_t)stream, *a);
   return (int)hipGetLastError();
 }
 

@@ -1,8 +1,10 @@
 // Captured HIP graphs of query pipelines with per-replay kernel arguments.
 //
 // A fused query pipeline (exec/graphs.py: range search + tile map + generated scan kernel +
-// final fold + result copy; or the two-phase merge join's tags + bits scan + fold + copy) is
-// captured once from a stream and replayed per query.  The generated kernels take their literals
+// result fold; or the two-phase merge join's tags + candidate scan + result fold) is captured
+// once from a stream and replayed per query.  Every node is a kernel: the fold writes the result
+// into the replay's pinned host block, whose address travels in its argument struct, and the
+// range bounds travel in the search kernel's.  The generated kernels take their literals
 // in a by-value argument struct (kernarg segment): reading that struct from device memory instead
 // would turn every column load of the kernel into a flat load (the compiler cannot prove a pointer
 // read from memory is global), which measured ~2x slower on gfx950.  So instead of a parameter
@@ -19,7 +21,11 @@
 //       work, rewrite the first nblocks kernel nodes' argument blocks, launch, and record the
 //       slot's ``done`` event (the Python side's per-call overhead was several torch stream /
 //       event calls per query)
+//   hs_graph_clone(handle) -> handle       (another executable graph of the same capture)
+//   hs_graph_node_counts(handle, &kernels, &memcpys, &others)
 //   hs_graph_destroy(handle)
+//   funcs[i] is a generated kernel's hipFunction_t or a library kernel's function address
+//   (hs_agg_fold_func / hs_range_search_val_func of libhs_kernels: ONE by-value struct each).
 //   hs_event_create() / hs_event_record(ev, stream) / hs_event_query(ev) / hs_event_sync(ev) /
 //   hs_event_destroy(ev)       (timing-disabled events of the replay slots)
 #include <hip/hip_runtime.h>
@@ -27,6 +33,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -35,7 +42,9 @@ namespace {
 thread_local std::string g_err;
 
 struct HsGraph {
-  hipGraph_t graph = nullptr;
+  // the captured graph: shared by the handle of the capture and its clones (hs_graph_clone),
+  // destroyed with the last of them
+  std::shared_ptr<ihipGraph> graph;
   hipGraphExec_t exec = nullptr;
   hipEvent_t join = nullptr;               // hs_graph_replay's ``after`` ordering event
   std::vector<hipGraphNode_t> nodes;       // the kernel node of funcs[i]
@@ -116,21 +125,19 @@ void* hs_graph_capture_end(void* stream, void** funcs, int nfuncs) {
     return nullptr;
   }
   auto* g = new HsGraph();
-  g->graph = graph;
+  g->graph = std::shared_ptr<ihipGraph>(graph, [](hipGraph_t x) { hipGraphDestroy(x); });
   size_t n = 0;
   e = hipGraphGetNodes(graph, nullptr, &n);
   std::vector<hipGraphNode_t> all(n);
   if (e == hipSuccess && n) e = hipGraphGetNodes(graph, all.data(), &n);
   if (e != hipSuccess) {
     fail("hipGraphGetNodes", e);
-    hipGraphDestroy(graph);
     delete g;
     return nullptr;
   }
   all.resize(n);
   if (!sort_by_depth(all)) {
     g_err = "hs_graph_capture_end: could not order the captured nodes by dependency";
-    hipGraphDestroy(graph);
     delete g;
     return nullptr;
   }
@@ -152,7 +159,6 @@ void* hs_graph_capture_end(void* stream, void** funcs, int nfuncs) {
     }
     if (!found) {
       g_err = "hs_graph_capture_end: kernel node of function " + std::to_string(i) + " not found";
-      hipGraphDestroy(graph);
       delete g;
       return nullptr;
     }
@@ -160,11 +166,55 @@ void* hs_graph_capture_end(void* stream, void** funcs, int nfuncs) {
   e = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
   if (e != hipSuccess) {
     fail("hipGraphInstantiate", e);
-    hipGraphDestroy(graph);
     delete g;
     return nullptr;
   }
   return g;
+}
+
+// Another executable graph of ``handle``'s captured graph: same node table, no second capture.
+// The clone replays independently of the original (its own argument blocks per replay), so one
+// capture serves every in-flight instance of a pipeline.  Returns nullptr on failure.
+void* hs_graph_clone(void* handle) {
+  auto* src = (HsGraph*)handle;
+  if (src == nullptr || !src->graph) {
+    g_err = "hs_graph_clone: no captured graph";
+    return nullptr;
+  }
+  auto* g = new HsGraph();
+  g->graph = src->graph;
+  g->nodes = src->nodes;
+  g->params = src->params;
+  const hipError_t e = hipGraphInstantiate(&g->exec, g->graph.get(), nullptr, nullptr, 0);
+  if (e != hipSuccess) {
+    fail("hipGraphInstantiate", e);
+    delete g;
+    return nullptr;
+  }
+  return g;
+}
+
+// Node counts of the captured graph by kind (tests: a pipeline is kernel nodes only).
+int hs_graph_node_counts(void* handle, int* kernels, int* memcpys, int* others) {
+  auto* g = (HsGraph*)handle;
+  size_t n = 0;
+  hipError_t e = hipGraphGetNodes(g->graph.get(), nullptr, &n);
+  std::vector<hipGraphNode_t> all(n);
+  if (e == hipSuccess && n) e = hipGraphGetNodes(g->graph.get(), all.data(), &n);
+  if (e != hipSuccess) return fail("hipGraphGetNodes", e);
+  int nk = 0, nm = 0, no = 0;
+  for (size_t k = 0; k < n; ++k) {
+    hipGraphNodeType t;
+    e = hipGraphNodeGetType(all[k], &t);
+    if (e != hipSuccess) return fail("hipGraphNodeGetType", e);
+    if (t == hipGraphNodeTypeKernel) ++nk;
+    else if (t == hipGraphNodeTypeMemcpy) ++nm;
+    else ++no;
+  }
+  *kernels = nk;
+  *memcpys = nm;
+  *others = no;
+  return 0;
 }
 
 // Kernel node i of the executable graph takes the argument block ``args`` (the generated kernels
@@ -263,8 +313,7 @@ void hs_graph_destroy(void* handle) {
   if (g == nullptr) return;
   if (g->join) hipEventDestroy(g->join);
   if (g->exec) hipGraphExecDestroy(g->exec);
-  if (g->graph) hipGraphDestroy(g->graph);
-  delete g;
+  delete g;   // (the captured graph goes with its last handle)
 }
 
 }  // extern "C"

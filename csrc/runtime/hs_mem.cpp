@@ -1,9 +1,9 @@
 // Host memory + copy primitives for the graph-captured query pipelines (exec/graphs.py).
 //
-// Pinned parameter / result blocks are allocated here with hipHostMalloc (not through torch's
-// caching host allocator, whose per-copy event bookkeeping is not capture-safe), and the H2D
-// parameter copy and D2H result copy are issued with hipMemcpyAsync so that stream capture
-// records them as memcpy nodes reading / writing those fixed pinned addresses on every replay.
+// Pinned result blocks are allocated here with hipHostMalloc (not through torch's caching host
+// allocator): mapped, coherent host memory that the pipelines' fold kernel writes directly, so a
+// captured pipeline has no copy node.  hs_memcpy_async is what eager callers and the diagnostics
+// copy with (under stream capture it records a memcpy node).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>

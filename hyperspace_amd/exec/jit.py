@@ -111,6 +111,11 @@ def runtime():
                 L.hs_graph_set_args.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
                 L.hs_graph_launch.restype = C.c_int
                 L.hs_graph_launch.argtypes = [C.c_void_p, C.c_void_p]
+                L.hs_graph_clone.restype = C.c_void_p
+                L.hs_graph_clone.argtypes = [C.c_void_p]
+                L.hs_graph_node_counts.restype = C.c_int
+                L.hs_graph_node_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]
                 L.hs_graph_destroy.restype = None
                 L.hs_graph_destroy.argtypes = [C.c_void_p]
                 L.hs_graph_replay.restype = C.c_int

@@ -125,6 +125,24 @@ class WinKeys(C.Structure):
                 ("npart", C.c_int32), ("norder", C.c_int32)]
 
 
+class AggFoldSet(C.Structure):
+    _fields_ = [("psum", C.c_void_p), ("pcnt", C.c_void_p), ("pmin", C.c_void_p),
+                ("pmax", C.c_void_p), ("dout", C.c_void_p), ("hout", C.c_void_p),
+                ("nblk", C.c_int32), ("pad", C.c_int32)]
+
+
+class AggFoldArgs(C.Structure):
+    """``hs_agg_fold_kernel``'s by-value argument struct (csrc/kernels/scan_filter.hip)."""
+    _fields_ = [("GA", C.c_int32), ("nsets", C.c_int32), ("set", AggFoldSet * 2)]
+
+
+class RangeValArgs(C.Structure):
+    """``hs_range_search_val_kernel``'s by-value argument struct."""
+    _fields_ = [("key", ColDesc), ("bucket_off", C.c_void_p), ("buckets", C.c_void_p),
+                ("rstart", C.c_void_p), ("rlen", C.c_void_p), ("rbucket", C.c_void_p),
+                ("bp", C.c_int64 * 6), ("nb", C.c_int32), ("pad", C.c_int32)]
+
+
 _lib = None
 
 
@@ -160,7 +178,8 @@ def lib():
                      ("hs_join_params_size", JoinParams), ("hs_sort_key_spec_size", SortKeySpec),
                      ("hs_gather_params_size", GatherParams), ("hs_xch_params_size", XchParams),
                      ("hs_xch_copy_size", XchCopy), ("hs_merge_keys_size", MergeKeys),
-                     ("hs_win_keys_size", WinKeys)):
+                     ("hs_win_keys_size", WinKeys), ("hs_agg_fold_args_size", AggFoldArgs),
+                     ("hs_range_search_val_args_size", RangeValArgs)):
         f = getattr(L, name)
         f.restype = C.c_int
         if f() != C.sizeof(st):
@@ -190,6 +209,10 @@ def lib():
     _sig(L.hs_scan_bitmap, I, P, P, P, I, P, I, I, I64, I64, P, P)
     _sig(L.hs_join_agg, I, P, P, P, P, P, I, P, I64, P, I, P, P, P, P, P, P, P, P, P)
     _sig(L.hs_agg_final, I, P, P, P, P, I, I, P, P, P, P, P)
+    _sig(L.hs_agg_fold, I, P, P)
+    _sig(L.hs_agg_fold_func, P)
+    _sig(L.hs_range_search_val, I, P, P)
+    _sig(L.hs_range_search_val_func, P)
     _sig(L.hs_join_count, I, P, P, P, P, P, I, P, I64, P, I, P, P)
     _sig(L.hs_join_emit, I, P, I, P, P, I, P, P, P, P)
     _sig(L.hs_join_spans, I, P, P, P, P, P, I, P, I64, P, I, P)
