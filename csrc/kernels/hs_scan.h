@@ -128,12 +128,15 @@ __device__ __forceinline__ bool hs_agg_value(const AggSpec& a, const ColDesc* co
   return true;
 }
 
+// MIN / MAX skip NaN inputs like fmin / fmax on the global path: the slot changes only when v
+// compares below (above) it, which a NaN never does - a wave whose 64 lanes all hold NaN for
+// one group hands its NaN reduction to these helpers.
 __device__ __forceinline__ void hs_lds_atomic_min(double* addr, double v) {
   unsigned long long* a = (unsigned long long*)addr;
   unsigned long long old = *a, assumed;
   do {
     assumed = old;
-    if (__longlong_as_double((long long)assumed) <= v) break;
+    if (!(v < __longlong_as_double((long long)assumed))) break;   // (a NaN operand is skipped)
     old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
   } while (assumed != old);
 }
@@ -143,7 +146,7 @@ __device__ __forceinline__ void hs_lds_atomic_max(double* addr, double v) {
   unsigned long long old = *a, assumed;
   do {
     assumed = old;
-    if (__longlong_as_double((long long)assumed) >= v) break;
+    if (!(v > __longlong_as_double((long long)assumed))) break;   // (a NaN operand is skipped)
     old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
   } while (assumed != old);
 }

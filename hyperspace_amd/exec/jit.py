@@ -762,10 +762,13 @@ def _accumulate(gen: _Gen, aggs, grouped: bool, pass_var: str, gvar: str, ind: s
             out.append(f"{ind}    const double r = wsum(mine ? v : 0.0);")
         out.append(f"{ind}    if ((int)(threadIdx.x & 63) == ld) {{")
         out.append(f"{ind}      const int s = g0 * NA + {i};")
+        # r is NaN when all 64 lanes hold NaN for this group; lds_min / lds_max would store it
+        # over the slot (no ordered compare holds), so it is folded into the identity first:
+        # NaN inputs are skipped, as fmin / fmax skip them on the global path
         if a.kind == NL.AK_MIN:
-            out.append(f"{ind}      lds_min(&gmn[s], r);")
+            out.append(f"{ind}      lds_min(&gmn[s], fmin(r, __builtin_inf()));")
         elif a.kind == NL.AK_MAX:
-            out.append(f"{ind}      lds_max(&gmx[s], r);")
+            out.append(f"{ind}      lds_max(&gmx[s], fmax(r, -__builtin_inf()));")
         elif a.kind == NL.AK_SUM:
             out.append(f"{ind}      atomicAdd(&gsum[s], r);")
         out.append(f"{ind}      atomicAdd(&gcnt[s], (unsigned long long)__popcll(cm));")
@@ -1012,6 +1015,13 @@ def int_bounds(op: int, lit: float, scale: float) -> Tuple[int, int]:
             return (_BIG, -_BIG) if below else (-_BIG, _BIG)
         return (_BIG, -_BIG)
 
+    # a compact decimal column holds |q| < 2^52 (compact.hip / encoding.py): a literal whose
+    # scaled image lies beyond that (or overflows to inf) is above / below every value, so the
+    # answer depends on its sign and the op alone, as for +-inf.  This also bounds the search
+    # below: inside the range neighbouring integers are distinct doubles
+    if not abs(lit * scale) < float(1 << 53):
+        return int_bounds(op, math.copysign(math.inf, lit), scale)
+
     def first(pred) -> int:                          # smallest integer t with pred(t / scale)
         t = math.floor(lit * scale) - 4
         while not pred(t / scale):
@@ -1133,7 +1143,10 @@ def gen_join_agg(p: NL.JoinParams, compacts=None) -> Kernel:
         ([p.group_col] if grouped else [])
     left_all = list(dict.fromkeys([lk] + [s for s in need if s < split]))
     right_all = list(dict.fromkeys([s for s in need if s >= split]))
-    lpred_slots = list(dict.fromkeys([lk] + [s for s in _pred_slots(lpreds) if s < split]))
+    # left columns a per-match predicate reads (l.a < r.b) load with the left predicates':
+    # the residual CNF is evaluated before the late (aggregate-input) left loads
+    lpred_slots = list(dict.fromkeys([lk] + [s for s in _pred_slots(lpreds) + _pred_slots(rpreds)
+                                             if s < split]))
     if JOIN_EAGER:
         left_first, left_late = left_all, []
     else:

@@ -623,13 +623,28 @@ def test_int_bounds_match_decoded_double_compares():
         qs = list(range(-3000, 3000))
         lits = [q / scale for q in rng.sample(qs, 40)] + [rng.uniform(-30, 30) for _ in range(40)]
         lits += [0.05, 0.07, -0.0, float("inf"), float("-inf"), float("nan")]
-        for lit in lits:
+        # literals far outside the column's range (|q| < 2^52): the bounds must come back at
+        # once whatever the magnitude, and still agree with the double compare for the extreme
+        # q a compact column can hold
+        big = [s * m for m in (1e16, 1e22, 1e300, 1.7976931348623157e308) for s in (1, -1)]
+        big.append(5e-324)
+        edge = [s * ((1 << 52) - d) for d in (1, 2, 3) for s in (1, -1)]
+        for lit in lits + big:
             for op, f in ops.items():
                 lo, hi = int_bounds(op, lit, scale)
-                for q in qs[::7]:
+                for q in qs[::7] + edge:
                     inside = lo <= q <= hi
                     got = (not inside) if op == NL.OP_NE else inside
                     assert got == f(q / scale, lit), (scale, lit, op, q)
+        # literals next to the extreme q themselves
+        for q0 in edge:
+            for lit in (q0 / scale, (q0 + 0.5) / scale):
+                for op, f in ops.items():
+                    lo, hi = int_bounds(op, lit, scale)
+                    for q in (q0 - 1, q0, q0 + 1):
+                        inside = lo <= q <= hi
+                        got = (not inside) if op == NL.OP_NE else inside
+                        assert got == f(q / scale, lit), (scale, lit, op, q)
 
 
 def test_timestamp_literals_exact_in_column_unit():
