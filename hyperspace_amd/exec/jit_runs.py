@@ -71,6 +71,7 @@ form applies when no aggregate input comes from the right side, every right pred
 only right columns, and a right-side group key (if any) has at most 255 groups."""
 from __future__ import annotations
 
+import collections
 import re
 from typing import List, Optional
 
@@ -1073,17 +1074,7 @@ def _scan_grouped(p: NL.JoinParams) -> bool:
 
 def gen_run_scan(p: NL.JoinParams, compacts, W: int, NI: int) -> J.Kernel:
     """Phase 2 (module docstring): the left rows' scan with the run-tag test."""
-    args = J.Args()
-    for n, ct in (("rstart", "const long long*"), ("rlen", "const long long*"),
-                  ("tile_prefix", "const long long*")):
-        args.add("p", n, ct)
-    lk = p.lkey
-    args.add("p", f"GM{lk}", "const unsigned long long*")
-    args.add("p", f"GR{lk}", "const int*")
-    args.add("p", "tags", "const unsigned*")
-    args.add("q", "R", "long long")
-    args.add("q", "nrows", "long long")
-    J._common_args(args)
+    args, lk = _scan_args(p), p.lkey
     cols = J._col_specs(p, compacts)
     lpreds = _lpreds(p)
     aggs = [p.aggs[i] for i in range(p.naggs)]
@@ -1331,86 +1322,17 @@ def sparse_shape(p: NL.JoinParams, compacts, hk=None, tk=None, cand: tuple = (),
         ((tk.shape(),) if tk is not None else ())
 
 
-def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
-                        cand: tuple = (), pair: bool = False) -> J.Kernel:
-    """Phase 2 for 1-bit tags, bit-parallel: the dense per-row scan spends ~20 VALU
-    instructions per row (decode, predicate, run index by popcount, tag extract, compaction
-    ballot + mbcnt), which bounds it below HBM speed.  Here a wavefront takes 4096-row tiles of
-    the left ranges, lane l the 64-row group l of its tile, and works on 64-bit row masks:
+# the bit-parallel phase 2: rows per wavefront tile (64 groups, one per lane) and list entries per
+# wavefront and round (a denser tile takes rounds)
+BITS_TILE, BITS_CAP = 4096, 1024
+# the stable append's slot offset of a lane: the passing lanes below it in the ballot bl_
+_BALLOT_PREFIX = ("(int)__builtin_amdgcn_mbcnt_hi((unsigned)(bl_ >> 32), "
+                  "__builtin_amdgcn_mbcnt_lo((unsigned)bl_, 0u))")
 
-    1. tag mask: the tag bits of the group's runs (gruns / 3 tag words) deposited at the run
-       starts (gmask) and spread over each run's rows by a prefix XOR (as hs_run_rowmask),
-       limited to the tile's range rows - ~1.5 instructions per row;
-    2. predicate mask: the lane's 64 rows of every left predicate column (vector loads, in
-       flight with the tag words), one compare + shift-or per row;
-    3. the rows of (tag mask & predicate mask) - the join's passing rows, a few percent - go to
-       a per-wavefront LDS list (offsets from a shuffle scan of the lanes' popcounts), which the
-       wavefront walks 4 entries per lane per pass: aggregate inputs loaded at those rows only
-       and accumulated.
 
-    The next tile's run-form words are prefetched during the current tile.
-
-    With ``hk`` (an exec.hash_agg.KeyPlan over left columns) the walk groups by the hash key
-    instead: each pass's 64 list entries are consecutive passing rows, so a segmented shuffle
-    reduce folds a group's rows (one run = one left join key) before one table probe
-    (``jit_hash._hash_accumulate``); kernel ``hs_jit_run_bits_hash``, no partials.
-
-    With ``tk`` as well (an exec.hash_agg.TopKPlan: ORDER BY <aggregate> LIMIT k over those
-    groups), the windows are walked in row order with the last segment of each carried into
-    the next (``jit_hash._topk_accumulate``): a key is final when the walk leaves it and competes
-    for the wavefront's top-K registers instead of probing the table; only keys that may
-    continue into the neighbouring wavefronts' tiles (at most two per wavefront) go to the
-    table (kernel ``hs_jit_run_bits_topk``; every wavefront writes its list at the end).
-
-    Candidate form (``cand``: the predicate slots of ``prune_plan``; kernel
-    ``hs_jit_run_bits_cand``): phase 1 tagged only runs that may hold a passing row, so step 2's
-    row stream goes.  The rows of (tag mask & range mask) are the tile's *candidates*; they go
-    to a small per-wavefront LDS list ``clst_``, 64 * RS_WALK at a time, the wavefront loads
-    each candidate's row-packed tail word (which holds the predicate columns' codes as extra
-    fields), tests the left predicates on those fields and appends the passing entries stably
-    (ballot + prefix count) to ``lst_``, which the unchanged walk of step 3 consumes.  The walk
-    runs once per tile, after its last candidate (so a tile's passing-row sequence, and with it
-    every lane's sum order, is that of the streaming form while the tile has at most CAP
-    passing rows), or earlier whenever ``lst_`` holds more than CAP entries.  That is the
-    *listing form* (RS_KEEP off): its walk loads the tail word of a passing row again (an L2 hit
-    a few hundred cycles after the filter's load) - one more dependent round trip per tile.
-
-    With RS_KEEP (the default) the filter pass keeps the word instead: the stable append writes
-    the 64-bit word ``fw<k>_`` of a passing entry into a per-wavefront ring ``kw_`` at slot
-    (entries appended since the last reset + ballot prefix) mod KB, and nothing into ``lst_``,
-    which goes.  The walk hands entry e (counted since the reset) to lane e % 64 in ascending
-    order, so any complete group of 64 entries can be summed as soon as it exists: after every
-    pass the ``cb`` loop takes the pending whole groups from the ring (its head stays a multiple
-    of 64), and the rest where the listing form walks - after the tile's last pass, or once more
-    than CAP entries were appended since the reset (``np_`` still counts appended, not pending,
-    entries, so resets and with them the lane of every later entry fall where they fell).  Each
-    lane therefore adds the same values in the same order; a different number of masked-off
-    slots only adds +0.0 to sums that start at +0.0.  KB = 63 + CC: the most a ring can hold
-    before a consumption (a leftover below 64 plus one pass's CC appends) - 2.5 KB per wavefront
-    instead of 8 (CAP + CC) for a whole tile's words.  Every tail slot is a field of the word
-    (``pack_layout`` is required here), so the walk keeps no row offset and issues no global
-    load; it takes one entry per lane and step (LDS reads need no batch in flight), which with
-    the addresses and in-flight loads gone brings the single form from 70 to 62 VGPRs.
-
-    Pair form (``pair``, ``cand_pair``; kernel ``hs_jit_run_bits_cand2``): two queries tagged by
-    the pair phase 1 (bitmaps ``tags`` / ``tags_b``, the second literal set and partials with
-    ``PAIR_SFX``) in one pass over the same tiles.  Both row masks come from one LUT expansion
-    of the shared run starts.  A tile in which neither query has more than CAP candidates - every
-    tile of the headline - takes the *union path*: the candidates of (mask A | mask B) go
-    through ``clst_`` with two membership bits beside the 12-bit row offset, each tail word is
-    loaded once, either query's predicates are tested with its literals under its membership
-    bit, and the two stable appends fill two lists (A at 0, B at CAP of one ``lst_`` of 2 CAP +
-    CC entries: neither can exceed CAP).  After the tile's last pass the single form's walk
-    runs over A's list into A's accumulators, then over B's into B's: the single form would
-    not have walked earlier either, so every lane adds the same values in the same order.  Any
-    other tile takes the *dense path*: the single form's candidate loop, emitted by the same
-    code, once per query (its early walks depend on where the candidate batches fall, which a
-    union pass cannot reproduce).  Grid, tile split and flush are the single form's, so each
-    query's partials are bit for bit those of its own launch.  With RS_KEEP the union path has
-    two rings (A's at 0, B's at KB of one ``kw_``) and sums A's whole groups, then B's, after
-    every pass; the dense path uses A's ring for one query at a time."""
-    assert not cand or (hk is None and tk is None)
-    assert not pair or cand_pair(p, compacts, cand, hk, tk)
+def _scan_args(p: NL.JoinParams, pair: bool = False) -> J.Args:
+    """The argument header of both phase-2 generators (the struct layout starts with it);
+    ``pair``: with the second query's bitmap and partials (PAIR_SFX)."""
     args = J.Args()
     for n, ct in (("rstart", "const long long*"), ("rlen", "const long long*"),
                   ("tile_prefix", "const long long*")):
@@ -1428,190 +1350,299 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
         for n, ct in (("psum", "double*"), ("pmin", "double*"), ("pmax", "double*"),
                       ("pcnt", "long long*")):
             args.add("p", n + PAIR_SFX, ct)
+    return args
 
-    def set_b(lines: List[str]) -> List[str]:
+
+# Which bit-parallel phase-2 kernel is generated, resolved once (``_bits_form``): its name; the
+# candidate forms' predicate slots ``cand``, whether they keep the passing words (RS_KEEP) and
+# serve a pair; a hash / top-K walk; a left-side group table; the predicate slots streamed as
+# 12-bit copies; the pipeline depth; ``pack_layout`` of the tail word or None; and the constants:
+# T rows per tile, CAP, EW list entries per lane per walk pass (loads in flight together), CC
+# candidates per filter pass, KB ring entries and WV wavefronts per workgroup.
+# RS_KEEP: a passing candidate's tail word stays in a per-wavefront ring kw_ of KB entries -
+# the leftover of a 64-entry group (at most 63) plus one filter pass's appends (at most CC)
+_BitsForm = collections.namedtuple(
+    "_BitsForm", "name cand keep pair hash topk grouped p12 pipe layout T CAP EW CC KB WV")
+
+
+def _bits_tail(p: NL.JoinParams, hk, tk) -> list:
+    """The slots the walk reads per passing row."""
+    # top-K mode segments the walk by key run (lrn_) and loads the key columns only where a
+    # group is emitted (jit_hash._hash_accumulate ``seg``): they are not part of the per-row tail
+    aggs = [p.aggs[i] for i in range(p.naggs)]
+    return list(dict.fromkeys(J._agg_slots(aggs) + ([p.group_col] if _scan_grouped(p) else []) +
+                              (list(hk.slots) if hk is not None and tk is None else [])))
+
+
+def _bits_form(p: NL.JoinParams, compacts, hk, tk, cand: tuple, pair: bool) -> _BitsForm:
+    """The form of ``gen_run_sparse_scan``'s arguments under the bound tunables, and every check
+    that the combination exists."""
+    grouped = _scan_grouped(p)
+    layout = pack_layout(p, compacts, cand)
+    keep = bool(cand) and bool(RS_KEEP)
+    p12 = () if cand else _p12_slots(p, compacts)
+    assert not cand or (hk is None and tk is None)
+    assert not pair or cand_pair(p, compacts, cand, hk, tk)
+    assert not (grouped and (p.group_col >= SPLIT or hk is not None))
+    assert tk is None or hk is not None
+    # (the predicates' packed forms, on scratch arguments: the emitters add the literal slots)
+    dry = J._Gen(J.Args(), J._col_specs(p, compacts), SPLIT, ("row0", "row0"), frozenset(), True)
+    assert not p12 or dry.cnf_sign2(_lpreds(p), "pw{}_", offset="a.P12O_{}") is not None
+    if cand:
+        assert layout is not None and dry.cnf_sign(_lpreds(p)) is not None
+        assert {sl for sl, off, nb in layout if sl in cand and nb == 2} == set(cand)
+        # (RS_KEEP: the walk has no row, only the word - every tail slot is one of its fields)
+        assert not keep or (not grouped and
+                            {sl for sl, _, _ in layout} >= set(_bits_tail(p, hk, tk)))
+    name = "hs_jit_run_bits_cand2" if pair else "hs_jit_run_bits_cand" if cand else \
+        "hs_jit_run_bits_scan" if hk is None else \
+        ("hs_jit_run_bits_hash" if tk is None else "hs_jit_run_bits_topk")
+    cc = 64 * max(1, RS_WALK)
+    return _BitsForm(name, tuple(cand), keep, bool(pair), hk is not None, tk is not None, grouped,
+                     p12, 0 if cand else RS_PIPE, layout, BITS_TILE, BITS_CAP, max(1, RS_WALK),
+                     cc, 63 + cc, J.BLOCK // 64)
+
+
+class _BitsScan:
+    """The builder behind ``gen_run_sparse_scan``: one method per stage of the kernel, each
+    returning its source lines, over the form ``f``, the argument struct and the column /
+    predicate / aggregate descriptions.  Stages add slots to ``args`` as they emit (each says
+    so), and the slot order is the ``Args`` struct layout - part of the source text - so the
+    order of the driver's calls is fixed: header, ``acc_decls``, ``loads``, ``pred_mask`` or
+    ``candidates``, the first ``walk``, ``set_b`` twins where first referenced, ``epilogue``."""
+
+    def __init__(self, p: NL.JoinParams, compacts, hk, tk, cand: tuple, pair: bool):
+        self.f = f = _bits_form(p, compacts, hk, tk, cand, pair)
+        self.p, self.hk, self.tk, self.lk = p, hk, tk, p.lkey
+        self.args = args = _scan_args(p, f.pair)
+        self.cols = cols = J._col_specs(p, compacts)
+        self.lpreds, self.aggs = _lpreds(p), [p.aggs[i] for i in range(p.naggs)]
+        self.pslots, self.tail = J._pred_slots(self.lpreds), _bits_tail(p, hk, tk)
+        self.approx = J._sum_only_slots(self.lpreds, self.aggs,
+                                        p.group_col if f.grouped else -1, cols) - \
+            set(hk.slots if hk is not None else [])
+        self.g1 = J._Gen(args, cols, SPLIT, ("row0", "row0"), self.approx, True)
+        self.carry_gen = J._Gen(args, cols, SPLIT, ("tcw_", "tcw_"), frozenset(), True) \
+            if tk is not None else None
+        self.packed = {sl: (off, nb) for sl, off, nb in f.layout} if f.layout else {}
+        # per-query name infix of the tag words, row masks and counts ("" alone: the single forms)
+        self.QS = ("", "b") if f.pair else ("",)
+        self.elem = {}   # array name -> C expression of element (idx) from its packed 32-bit words
+        self.issue = []  # the current tile's (C) tag-word and predicate-column loads into buffer @S@
+        self.xpose = []  # RS_LDS: the loaded columns' chunks moved to their rows' lanes
+        self.slab = 0    # RS_LDS: 16-byte LDS slots per wavefront
+
+    @staticmethod
+    def subst(lines: List[str], ind: str = "", **marks) -> List[str]:
+        """``lines`` indented by ``ind`` with the emitters' placeholders replaced, in the order
+        given: @S@, the register buffer (A / B) of the tile worked on; @O@, the other buffer,
+        which the next tile's loads fill; @T@, the tile index expression; @LIVE@, a prefix of a
+        buffer load's byte count ("!nx_ ? 0ll : " empties it past the wavefront's last tile)."""
+        out = []
+        for x in lines:
+            for k, v in marks.items():
+                x = x.replace(f"@{k}@", v)
+            out.append(ind + x)
+        return out
+
+    def set_b(self, lines: List[str]) -> List[str]:
         """``lines`` for the pair's second query: literal slots (twins added as in
-        ``gen_run_tags2``), partial pointers and accumulator registers get ``PAIR_SFX``."""
+        ``gen_run_tags2``), partial pointers and accumulator registers get ``PAIR_SFX``.  The
+        regex twin of the first query's code; as a side effect it adds a ``_b`` slot for every
+        literal slot it meets first, so the order of its calls fixes the struct layout too."""
         def twin(m):
-            kind, name, ct = args.slots[args._index[m.group(1)]]
-            return args.add(kind, name + PAIR_SFX, ct)
+            kind, name, ct = self.args.slots[self.args._index[m.group(1)]]
+            return self.args.add(kind, name + PAIR_SFX, ct)
         return [_ACC_REG.sub(r"\1\2" + PAIR_SFX,
                              _PART_SLOT.sub(r"a.\1" + PAIR_SFX, _LIT_SLOT2.sub(twin, x)))
                 for x in lines]
-    cols = J._col_specs(p, compacts)
-    lpreds = _lpreds(p)
-    aggs = [p.aggs[i] for i in range(p.naggs)]
-    grouped = _scan_grouped(p)
-    assert not (grouped and p.group_col >= SPLIT)
-    pslots = J._pred_slots(lpreds)
-    assert not (grouped and hk is not None)
-    # top-K mode segments the walk by key run (lrn_) and loads the key columns only where a
-    # group is emitted (jit_hash._hash_accumulate ``seg``): they are not part of the per-row tail
-    tail = list(dict.fromkeys(J._agg_slots(aggs) + ([p.group_col] if grouped else []) +
-                              (list(hk.slots) if hk is not None and tk is None else [])))
-    approx = J._sum_only_slots(lpreds, aggs, p.group_col if grouped else -1, cols) - \
-        set(hk.slots if hk is not None else [])
-    BLOCK = J.BLOCK  # noqa: N806
-    WV = BLOCK // 64  # noqa: N806
-    T = 4096  # noqa: N806 — rows per wavefront tile: 64 groups, one per lane
-    NI = 64  # noqa: N806
-    b: List[str] = []
-    b += J._acc_decls(aggs, grouped, args)
-    if pair:
-        b += set_b(J._acc_decls(aggs, grouped, args)[1:])
-    assert tk is None or hk is not None
-    if tk is not None:
-        b += JH._topk_decls(aggs, tk)
-    CAP = 1024  # noqa: N806 — list entries per wavefront and round (a denser tile takes rounds)
-    EW = max(1, RS_WALK)  # noqa: N806 — list entries per lane per walk pass, loads in flight together
 
-    def geom(tv: str, sfx: str) -> List[str]:
+    def at(self, s: str) -> str:
+        """Offset of query ``s``'s list in ``lst_`` / ring in ``kw_`` (B's in the union path)."""
+        return f"{self.f.KB if self.f.keep else self.f.CAP} + " if s == "b" else ""
+
+    def acc_decls(self) -> List[str]:
+        """Accumulators and top-K registers.  Adds num_groups / group_base for a group table."""
+        b = J._acc_decls(self.aggs, self.f.grouped, self.args)
+        if self.f.pair:
+            b += self.set_b(J._acc_decls(self.aggs, self.f.grouped, self.args)[1:])
+        if self.tk is not None:
+            b += JH._topk_decls(self.aggs, self.tk)
+        return b
+
+    def loads(self) -> List[str]:
+        """Enumerates the tile's loads - tag words and the predicate columns' row stream (none
+        in the candidate forms) - into ``issue`` / ``xpose`` / ``slab`` / ``elem``; returns their
+        register buffers' declarations.  Adds the P12_ / P12O_ slots or the column pointers."""
+        f, args, b = self.f, self.args, []
+        self.issue.append("    { const i64 w_ = (i64)grC >> 5; tw0@S@_ = a.tags[w_]; "
+                          "tw1@S@_ = a.tags[w_ + 1]; tw2@S@_ = a.tags[w_ + 2]; }")
+        if f.pair:
+            self.issue.append("    { const i64 w_ = (i64)grC >> 5; tw0@S@b_ = a.tags_b[w_]; "
+                              "tw1@S@b_ = a.tags_b[w_ + 1]; tw2@S@b_ = a.tags_b[w_ + 2]; }")
+        for sl in f.p12:
+            # 24 dwords (96 bytes) per lane: its 64-row group's 12-bit packed codes
+            pp = args.add("p", f"P12_{sl}", "const unsigned*")
+            args.add("q", f"P12O_{sl}", "long long")
+            b.append(f"  unsigned x{sl}qA[24], x{sl}qB[24];")
+            self.issue.append(
+                f"    bload<24>(hs_rsrc((const char*){pp} + (tbC >> 6) * 96, "
+                f"@LIVE@((a.nrows + 63 - tbC) >> 6) * 96), (unsigned)(ln * 96), x{sl}q@S@);")
+        for name, ct, ptr in ([] if f.p12 or f.cand else J._vec_loads(self.g1, self.pslots)):
+            es = J._SIZEOF[ct]
+            nw = 64 * es // 4
+            per = 4 // es
+            b.append(f"  unsigned {name}wA[{nw}], {name}wB[{nw}];")
+            # the group's rows past the table end read as 0 (buffer range check); they are outside
+            # every row range, so the range mask drops them
+            if RS_LDS:
+                self.issue.append(f"    bload_t<{nw}>(hs_rsrc((const char*){ptr} + tbC * {es}, "
+                                  f"@LIVE@(a.nrows - tbC) * {es}), ln, {name}w@S@);")
+                self.xpose.append(f"    hs_lds_t<{nw}>(&xt_[wq][0], ln, {name}w@S@);")
+                self.slab = max(self.slab, nw // 4 * 64)
+            else:
+                self.issue.append(f"    bload<{nw}>(hs_rsrc((const char*){ptr} + tbC * {es}, "
+                                  f"@LIVE@(a.nrows - tbC) * {es}), (unsigned)(64 * ln * {es}), "
+                                  f"{name}w@S@);")
+            self.elem[name] = (ct, f"{name}w@S@[({{i}}) / {per}]" if per > 1
+                               else f"{name}w@S@[{{i}}]", 8 * es, per)
+        return b
+
+    def lds_decls(self) -> List[str]:
+        """The LDS arrays and the nibble table's fill; after ``loads``, which sizes RS_LDS's slab."""
+        f, b = self.f, []
+        WV, CAP, CC, KB = f.WV, f.CAP, f.CC, f.KB  # noqa: N806
+        if f.topk:
+            b.append(f"  __shared__ unsigned short lrn_[{WV}][{CAP}];")
+        if RS_LUT:
+            # dlut_[m | w << 4]: the 4 row tags of a nibble with run-start bits m, tag window w
+            b += ["  __shared__ unsigned char dlut_[512];",
+                  f"  for (int e_ = (int)threadIdx.x; e_ < 512; e_ += {J.BLOCK}) {{",
+                  "    unsigned k_ = 0u, o_ = 0u;",
+                  "    for (int j_ = 0; j_ < 4; ++j_) { k_ += (e_ >> j_) & 1; "
+                  "o_ |= (((unsigned)e_ >> (4u + k_)) & 1u) << j_; }",
+                  "    dlut_[e_] = (unsigned char)o_; }",
+                  "  __syncthreads();"]
+        if f.cand:
+            b.append(f"  __shared__ unsigned short clst_[{WV}][{CC}];")
+        if f.keep:
+            # (pair form: A's ring at 0 and B's at KB; the dense path uses A's for one query at a time)
+            b.append(f"  __shared__ u64 kw_[{WV}][{(2 if f.pair else 1) * KB}];")
+        elif self.xpose:
+            # the transpose slab and the passing-row list share the LDS: a tile's list is built
+            # after its columns left the slab, and walked before the next tile's transpose
+            nslot = max(self.slab, (CAP * 2 + 15) // 16)
+            # lst_[w] = wavefront w's own slab, seen as 16-bit entries
+            b += [f"  __shared__ hs_v4u xt_[{WV}][{nslot}];",
+                  f"  unsigned short (*lst_)[{nslot * 8}] = "
+                  f"(unsigned short (*)[{nslot * 8}])&xt_[0][0];"]
+        else:
+            # (pair form: A's list at 0 and B's at CAP in the union path; the dense path uses
+            # [0, CAP + CC) for one query at a time)
+            b.append(f"  __shared__ unsigned short lst_[{WV}]"
+                     f"[{((2 if f.pair else 1) * CAP + CC) if f.cand else CAP}];")
+        return b
+
+    def split(self) -> List[str]:
+        """The wavefront's tiles, its first tile's row range (binary search), pipeline registers."""
+        WV = self.f.WV  # noqa: N806
+        return ["  const int ln = (int)(threadIdx.x & 63);",
+                "  const int wq = (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
+                "  const i64 ntiles = a.tile_prefix[a.R];",
+                f"  const i64 nwv = (i64)gridDim.x * {WV};",
+                f"  const i64 wid = (i64)blockIdx.x * {WV} + wq;",
+                "  const i64 per = (ntiles + nwv - 1) / nwv;",
+                "  const i64 t0 = wid * per;",
+                "  const i64 t1 = ntiles < t0 + per ? ntiles : t0 + per;",
+                "  int r = 0;",
+                "  if (t0 < t1) { int lo = 0, hi = (int)a.R;",
+                "    while (hi - lo > 1) { const int m = (lo + hi) >> 1; "
+                "if (a.tile_prefix[m] <= t0) lo = m; else hi = m; }",
+                "    r = lo; }",
+                # software pipeline (RS_PIPE), one exposed memory round trip per tile: tile t's tag
+                # words and predicate columns were issued during tile t-1 (after its masks were
+                # formed, before its list walk, so the walk's aggregate-input loads wait on them
+                # together) and the run-form words of tile t+1 one tile earlier still (the tag words'
+                # address needs them).  The tile loop is unrolled by two over two named buffers (A, B):
+                # a loop-carried array is copied register to register at the back edge otherwise,
+                # after a wait for its loads, and held twice.
+                "  i64 rsC = 0, reC = 0, tbC = 0; u64 gmC = 0ull; int grC = 0;",
+                "  i64 rsN = 0, reN = 0, tbN = 0; u64 gmN = 0ull; int grN = 0;",
+                "  unsigned tw0A_ = 0u, tw1A_ = 0u, tw2A_ = 0u, tw0B_ = 0u, tw1B_ = 0u, tw2B_ = 0u;"] + \
+            (["  unsigned tw0Ab_ = 0u, tw1Ab_ = 0u, tw2Ab_ = 0u;"] if self.f.pair else [])
+
+    def geom(self, tv: str, sfx: str) -> List[str]:
         """Tile ``tv``'s range / row geometry and its group's run-form words (suffix sfx).  The
         words stay in their loaded types (no OR / widening here): an operation on a loaded value
         makes the compiler wait for the load on the spot, and these are prefetched a tile ahead."""
+        lk = self.lk
         return [f"    while (r + 1 < (int)a.R && a.tile_prefix[r + 1] <= {tv}) ++r;",
                 f"    rs{sfx} = a.rstart[r]; re{sfx} = rs{sfx} + a.rlen[r];",
-                f"    tb{sfx} = (rs{sfx} & ~(i64)63) + ({tv} - a.tile_prefix[r]) * {T};",
+                f"    tb{sfx} = (rs{sfx} & ~(i64)63) + ({tv} - a.tile_prefix[r]) * {self.f.T};",
                 f"    {{ const i64 r0_ = tb{sfx} + 64 * ln; "
                 f"const i64 g_ = (r0_ < a.nrows ? r0_ : a.nrows - 1) >> 6;",
                 f"      gm{sfx} = a.GM{lk}[g_]; gr{sfx} = a.GR{lk}[g_]; }}"]
-    if tk is not None:
-        b.append(f"  __shared__ unsigned short lrn_[{WV}][{CAP}];")
-    if RS_LUT:
-        # dlut_[m | w << 4]: the 4 row tags of a nibble with run-start bits m, tag window w
-        b += ["  __shared__ unsigned char dlut_[512];",
-              f"  for (int e_ = (int)threadIdx.x; e_ < 512; e_ += {BLOCK}) {{",
-              "    unsigned k_ = 0u, o_ = 0u;",
-              "    for (int j_ = 0; j_ < 4; ++j_) { k_ += (e_ >> j_) & 1; "
-              "o_ |= (((unsigned)e_ >> (4u + k_)) & 1u) << j_; }",
-              "    dlut_[e_] = (unsigned char)o_; }",
-              "  __syncthreads();"]
-    CC = 64 * EW  # noqa: N806 — candidate form: candidates per filter pass
-    if cand:
-        b.append(f"  __shared__ unsigned short clst_[{WV}][{CC}];")
-    # RS_KEEP: a passing candidate's tail word stays in a per-wavefront ring kw_ of KB entries -
-    # the leftover of a 64-entry group (at most 63) plus one filter pass's appends (at most CC)
-    keep = bool(cand) and bool(RS_KEEP)
-    KB = 63 + CC  # noqa: N806
-    if keep:
-        # (pair form: A's ring at 0 and B's at KB; the dense path uses A's for one query at a time)
-        b.append(f"  __shared__ u64 kw_[{WV}][{(2 if pair else 1) * KB}];")
-    else:
-        # (pair form: A's list at 0 and B's at CAP in the union path; the dense path uses
-        # [0, CAP + CC) for one query at a time)
-        b.append(f"  __shared__ unsigned short lst_[{WV}]"
-                 f"[{((2 if pair else 1) * CAP + CC) if cand else CAP}];")
-    b += ["  const int ln = (int)(threadIdx.x & 63);",
-          "  const int wq = (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
-          "  const i64 ntiles = a.tile_prefix[a.R];",
-          f"  const i64 nwv = (i64)gridDim.x * {WV};",
-          f"  const i64 wid = (i64)blockIdx.x * {WV} + wq;",
-          "  const i64 per = (ntiles + nwv - 1) / nwv;",
-          "  const i64 t0 = wid * per;",
-          "  const i64 t1 = ntiles < t0 + per ? ntiles : t0 + per;",
-          "  int r = 0;",
-          "  if (t0 < t1) { int lo = 0, hi = (int)a.R;",
-          "    while (hi - lo > 1) { const int m = (lo + hi) >> 1; "
-          "if (a.tile_prefix[m] <= t0) lo = m; else hi = m; }",
-          "    r = lo; }",
-          # software pipeline (RS_PIPE), one exposed memory round trip per tile: tile t's tag
-          # words and predicate columns were issued during tile t-1 (after its masks were
-          # formed, before its list walk, so the walk's aggregate-input loads wait on them
-          # together) and the run-form words of tile t+1 one tile earlier still (the tag words'
-          # address needs them).  The tile loop is unrolled by two over two named buffers (A, B):
-          # a loop-carried array is copied register to register at the back edge otherwise,
-          # after a wait for its loads, and held twice.
-          "  i64 rsC = 0, reC = 0, tbC = 0; u64 gmC = 0ull; int grC = 0;",
-          "  i64 rsN = 0, reN = 0, tbN = 0; u64 gmN = 0ull; int grN = 0;",
-          "  unsigned tw0A_ = 0u, tw1A_ = 0u, tw2A_ = 0u, tw0B_ = 0u, tw1B_ = 0u, tw2B_ = 0u;"]
-    # per-query name infix of the tag words, row masks and counts ("" alone: the single forms)
-    QS = ("", "b") if pair else ("",)  # noqa: N806
-    if pair:
-        b.append("  unsigned tw0Ab_ = 0u, tw1Ab_ = 0u, tw2Ab_ = 0u;")
-    g1 =J._Gen(args, cols, SPLIT, ("row0", "row0"), approx, True)
-    elem = {}   # array name -> C expression of element (idx) from its packed 32-bit words
-    issue = []  # the current tile's (C) tag-word and predicate-column loads into buffer @S@
-    xpose = []  # RS_LDS: the loaded columns' chunks moved to their rows' lanes
-    slab = 0    # RS_LDS: 16-byte LDS slots per wavefront
-    issue.append("    { const i64 w_ = (i64)grC >> 5; tw0@S@_ = a.tags[w_]; "
-                 "tw1@S@_ = a.tags[w_ + 1]; tw2@S@_ = a.tags[w_ + 2]; }")
-    if pair:
-        issue.append("    { const i64 w_ = (i64)grC >> 5; tw0@S@b_ = a.tags_b[w_]; "
-                     "tw1@S@b_ = a.tags_b[w_ + 1]; tw2@S@b_ = a.tags_b[w_ + 2]; }")
-    p12 = () if cand else _p12_slots(p, compacts)
-    pipe = 0 if cand else RS_PIPE
-    for sl in p12:
-        # 24 dwords (96 bytes) per lane: its 64-row group's 12-bit packed codes
-        pp = args.add("p", f"P12_{sl}", "const unsigned*")
-        args.add("q", f"P12O_{sl}", "long long")
-        b.append(f"  unsigned x{sl}qA[24], x{sl}qB[24];")
-        issue.append(f"    bload<24>(hs_rsrc((const char*){pp} + (tbC >> 6) * 96, "
-                     f"@LIVE@((a.nrows + 63 - tbC) >> 6) * 96), (unsigned)(ln * 96), x{sl}q@S@);")
-    for name, ct, ptr in ([] if p12 or cand else J._vec_loads(g1, pslots)):
-        es = J._SIZEOF[ct]
-        nw = NI * es // 4
-        per = 4 // es
-        b.append(f"  unsigned {name}wA[{nw}], {name}wB[{nw}];")
-        # the group's rows past the table end read as 0 (buffer range check); they are outside
-        # every row range, so the range mask drops them
-        if RS_LDS:
-            issue.append(f"    bload_t<{nw}>(hs_rsrc((const char*){ptr} + tbC * {es}, "
-                         f"@LIVE@(a.nrows - tbC) * {es}), ln, {name}w@S@);")
-            xpose.append(f"    hs_lds_t<{nw}>(&xt_[wq][0], ln, {name}w@S@);")
-            slab = max(slab, nw // 4 * 64)
+
+    def prologue(self) -> List[str]:
+        """The first tile's geometry (pipelined: its loads and the second tile's geometry too).
+        The next tile's run-form words are prefetched during the current tile."""
+        b = ["  if (t0 < t1) {"]
+        if self.f.pipe:
+            b += self.geom("t0", "C")
+            b += self.subst(self.issue, S="A", LIVE="")
+            b += ["    if (t0 + 1 < t1) {"]
+            b += self.subst(self.geom("(t0 + 1)", "N"), "  ")
+            b += ["    }"]
         else:
-            issue.append(f"    bload<{nw}>(hs_rsrc((const char*){ptr} + tbC * {es}, "
-                         f"@LIVE@(a.nrows - tbC) * {es}), (unsigned)(64 * ln * {es}), "
-                         f"{name}w@S@);")
-        elem[name] = (ct, f"{name}w@S@[({{i}}) / {per}]" if per > 1 else f"{name}w@S@[{{i}}]",
-                      8 * es, per)
+            b += self.geom("t0", "N")
+        return b + ["  }"]
 
-    def buf(lines: List[str], sfx: str) -> List[str]:
-        return [x.replace("@S@", sfx).replace("@LIVE@", "") for x in lines]
+    def tile_rows(self) -> List[str]:
+        """Head of a tile's body: (not pipelined) its loads, then the lane's 64 rows, the part
+        ``am`` of them inside the tile's row range, and the tag window's shift."""
+        body: List[str] = []
+        if not self.f.pipe:
+            # this tile's loads, then the next tile's run-form words: two round trips per tile (the
+            # column stream, then the walk's aggregate inputs), fewer registers
+            body += ["    rsC = rsN; reC = reN; tbC = tbN; gmC = gmN; grC = grN;"]
+            body += self.subst(self.issue, LIVE="")
+            body += ["    if (@T@ + 1 < t1) {"]
+            body += self.subst(self.geom("(@T@ + 1)", "N"), "  ")
+            body += ["    }"]
+        body += ["    const i64 rs = rsC, re = reC, tb0 = tbC; const u64 m_ = gmC | 1ull; "
+                 "const i64 q0 = (i64)grC;"]
+        if self.f.topk:
+            # key run of a list entry, relative to the tile's first run (lrn_)
+            body.append("    const i64 qb_ = __shfl(q0, 0, 64); const int qr_ = (int)(q0 - qb_);")
+        body += ["    const i64 row0 = tb0 + 64 * ln;",
+                 "    const i64 lo_ = rs - row0, hi_ = re - row0;",
+                 "    const int alo = lo_ <= 0 ? 0 : (lo_ >= 64 ? 64 : (int)lo_);",
+                 "    const int ahi = hi_ <= 0 ? 0 : (hi_ >= 64 ? 64 : (int)hi_);",
+                 "    const u64 am = alo >= ahi ? 0ull : ((ahi == 64 ? ~0ull : ((1ull << ahi) - 1ull)) & "
+                 "~((1ull << alo) - 1ull));",
+                 "    const unsigned sh_ = (unsigned)(q0 & 31);"]
+        return body
 
-    b.append("  if (t0 < t1) {")
-    if pipe:
-        b += geom("t0", "C")
-        b += buf(issue, "A")
-        b += ["    if (t0 + 1 < t1) {"]
-        b += ["  " + x for x in geom("(t0 + 1)", "N")]
-        b += ["    }"]
-    else:
-        b += geom("t0", "N")
-    b += ["  }"]
-    body: List[str] = []   # one tile (@T@), its buffer @S@, the next tile's buffer @O@
-    if not pipe:
-        # this tile's loads, then the next tile's run-form words: two round trips per tile (the
-        # column stream, then the walk's aggregate inputs), fewer registers
-        body += ["    rsC = rsN; reC = reN; tbC = tbN; gmC = gmN; grC = grN;"]
-        body += [x.replace("@LIVE@", "") for x in issue]
-        body += ["    if (@T@ + 1 < t1) {"]
-        body += ["  " + x for x in geom("(@T@ + 1)", "N")]
-        body += ["    }"]
-    body += ["    const i64 rs = rsC, re = reC, tb0 = tbC; const u64 m_ = gmC | 1ull; "
-             "const i64 q0 = (i64)grC;"]
-    if tk is not None:
-        # key run of a list entry, relative to the tile's first run (lrn_)
-        body.append("    const i64 qb_ = __shfl(q0, 0, 64); const int qr_ = (int)(q0 - qb_);")
-    body += ["    const i64 row0 = tb0 + 64 * ln;",
-             "    const i64 lo_ = rs - row0, hi_ = re - row0;",
-             "    const int alo = lo_ <= 0 ? 0 : (lo_ >= 64 ? 64 : (int)lo_);",
-             "    const int ahi = hi_ <= 0 ? 0 : (hi_ >= 64 ? 64 : (int)hi_);",
-             "    const u64 am = alo >= ahi ? 0ull : ((ahi == 64 ? ~0ull : ((1ull << ahi) - 1ull)) & "
-             "~((1ull << alo) - 1ull));",
-             "    const unsigned sh_ = (unsigned)(q0 & 31);"]
-    for q in QS:
-        body += [f"    const u64 lw{q}_ = (u64)tw0@S@{q}_ | ((u64)tw1@S@{q}_ << 32);",
-                 f"    const u64 hw{q}_ = (u64)tw2@S@{q}_;",
-                 f"    const u64 T{q}_ = sh_ ? ((lw{q}_ >> sh_) | (hw{q}_ << (64 - sh_))) : lw{q}_;"]
-    if RS_LUT:
+    def tag_mask(self) -> List[str]:
+        """Step 1, the tag mask d<q>_: the tag bits of the group's runs (gruns / 3 tag words)
+        deposited at the run starts (gmask) and spread over each run's rows, limited to the
+        tile's range rows - ~1.5 instructions per row."""
+        body = []
+        for q in self.QS:
+            body += [f"    const u64 lw{q}_ = (u64)tw0@S@{q}_ | ((u64)tw1@S@{q}_ << 32);",
+                     f"    const u64 hw{q}_ = (u64)tw2@S@{q}_;",
+                     f"    const u64 T{q}_ = sh_ ? ((lw{q}_ >> sh_) | (hw{q}_ << (64 - sh_))) : lw{q}_;"]
+        return body + (self.tag_mask_lut() if RS_LUT else self.tag_mask_loop())
+
+    def tag_mask_lut(self) -> List[str]:
         # row tags by nibble: rows 4i..4i+3 take their tags from a 5-run window of T (the run
         # covering row 4i-1, then the runs starting in the nibble) through a 512-entry LDS
         # table indexed by (nibble of run starts, window) - 16 fixed steps instead of a loop
         # over the group's run starts (~15 VALU per start, ~20-28 starts for the slowest lane)
         # (pair form: the run starts and their running count are shared, one lookup per query)
-        body += [f"    u64 d{q}_ = (u64)dlut_[((unsigned)m_ & 15u) | "
-                 f"((((unsigned)T{q}_ << 1) & 31u) << 4)];" for q in QS]
+        QS = self.QS  # noqa: N806
+        body = [f"    u64 d{q}_ = (u64)dlut_[((unsigned)m_ & 15u) | "
+                f"((((unsigned)T{q}_ << 1) & 31u) << 4)];" for q in QS]
         body += ["    unsigned P_ = (unsigned)__popc((unsigned)m_ & 15u);",
                  "    #pragma unroll",
                  "    for (int i_ = 1; i_ < 16; ++i_) {",
@@ -1622,9 +1653,12 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
                      f"      d{q}_ |= (u64)dlut_[ix{q}_] << (4 * i_);"]
         body += ["      P_ += (unsigned)__popc(mn_);",
                  "    }"]
-        body += [f"    d{q}_ &= am;" for q in QS]
-    else:
-        body += [
+        return body + [f"    d{q}_ &= am;" for q in QS]
+
+    def tag_mask_loop(self) -> List[str]:
+        """The loop form: one step per run start of the group, then a prefix XOR spreads each
+        run's tag over its rows (as hs_run_rowmask)."""
+        return [
              # only the group's own runs' tags (popc(m) of them) decide whether any row is set
              "    const int nr_ = __popcll(m_);",
              "    const u64 Tm_ = nr_ >= 64 ? T_ : (T_ & ((1ull << nr_) - 1ull));",
@@ -1634,21 +1668,15 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
              "    d_ ^= d_ << 1; d_ ^= d_ << 2; d_ ^= d_ << 4; d_ ^= d_ << 8; d_ ^= d_ << 16; "
              "d_ ^= d_ << 32;",
              "    d_ &= am;"]
-    if xpose:
-        # the transpose slab and the passing-row list share the LDS: a tile's list is built
-        # after its columns left the slab, and walked before the next tile's transpose
-        lst_i = next(i for i, x in enumerate(b) if "__shared__ unsigned short lst_" in x)
-        nslot = max(slab, (CAP * 2 + 15) // 16)
-        # lst_[w] = wavefront w's own slab, seen as 16-bit entries
-        b[lst_i:lst_i + 1] = [
-            f"  __shared__ hs_v4u xt_[{WV}][{nslot}];",
-            f"  unsigned short (*lst_)[{nslot * 8}] = (unsigned short (*)[{nslot * 8}])&xt_[0][0];"]
-        body += xpose
-    # (the candidate form tests the predicates per candidate row, on its tail word: below)
-    if not cand:
+
+    def pred_mask(self) -> List[str]:
+        """Step 2, the predicate mask: the lane's 64 rows of every left predicate column (vector
+        loads, in flight with the tag words), one compare + shift-or per row, ANDed into d_.
+        Adds the predicates' literal slots (``cnf`` first, then the sign forms')."""
+        g1, lpreds, pslots = self.g1, self.lpreds, self.pslots
         # predicate mask: 64 compares, shift-or into two 32-bit halves (a C loop: each row's
         # value is decoded where it is compared, not all 64 held decoded at once)
-        body.append("    unsigned plo_ = 0u, phi_ = 0u;")
+        body = ["    unsigned plo_ = 0u, phi_ = 0u;"]
         cond = J._rename(g1.cnf(lpreds), pslots, "k")
         # narrow compact-code ranges: fail bits from a sign word (no compares, no constants held in
         # registers for the select), else the generic condition's pass bits
@@ -1659,115 +1687,142 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
         # gathered in even/odd order per 32-row half, then unzipped (2.5 VALU per row instead of 5)
         sign2 = g1.cnf_sign2(lpreds, "x{}w@S@[w_]") if RS_PK16 and sign is not None and \
             all(J._SIZEOF.get(g1.raw_type(sl)) == 2 for sl in pslots) else None
-        if p12:
-            # 12-bit chunks: decode 8 rows per 3 dwords, pair them into 16-bit halves, packed tests
-            sign12 = g1.cnf_sign2(lpreds, "pw{}_", offset="a.P12O_{}")
-            assert sign12 is not None
-            for i in range(8):
-                body.append("    {")
-                for sl in p12:
-                    body += [f"      const unsigned a{sl}_ = x{sl}q@S@[{3 * i}], "
-                             f"b{sl}_ = x{sl}q@S@[{3 * i + 1}], c{sl}_ = x{sl}q@S@[{3 * i + 2}];",
-                             f"      const unsigned v{sl}_0 = a{sl}_ & 0xFFFu, "
-                             f"v{sl}_1 = (a{sl}_ >> 12) & 0xFFFu, "
-                             f"v{sl}_2 = ((a{sl}_ >> 24) | (b{sl}_ << 8)) & 0xFFFu, "
-                             f"v{sl}_3 = (b{sl}_ >> 4) & 0xFFFu;",
-                             f"      const unsigned v{sl}_4 = (b{sl}_ >> 16) & 0xFFFu, "
-                             f"v{sl}_5 = ((b{sl}_ >> 28) | (c{sl}_ << 4)) & 0xFFFu, "
-                             f"v{sl}_6 = (c{sl}_ >> 8) & 0xFFFu, v{sl}_7 = c{sl}_ >> 20;"]
-                for q in range(4):
-                    w = 4 * i + q
-                    half, wl = ("plo_", w) if w < 16 else ("phi_", w - 16)
-                    body.append("      {")
-                    for sl in p12:
-                        body.append(f"        const unsigned pw{sl}_ = v{sl}_{2 * q} | "
-                                    f"(v{sl}_{2 * q + 1} << 16);")
-                    body += [f"        const unsigned s2_ = {sign12};",
-                             f"        {half} |= (s2_ >> {15 - wl}) & {(1 << wl) | (1 << (wl + 16))}u;",
-                             "      }"]
-                body.append("    }")
-            body += ["    plo_ = hs_unzip16(plo_);", "    phi_ = hs_unzip16(phi_);"]
+        if self.f.p12:
+            body += self.pred_mask_p12()
         elif sign2 is not None:
-            for half, off in (("plo_", 0), ("phi_", 16)):
-                body += ["    #pragma unroll",
-                         "    for (int w_ = 0; w_ < 16; ++w_) {",
-                         f"      const unsigned s2_ = {sign2.replace('[w_]', f'[w_ + {off}]')};",
-                         f"      {half} |= (s2_ >> (15 - w_)) & ((1u << w_) | (1u << (w_ + 16)));",
-                         "    }",
-                         f"    {half} = hs_unzip16({half});"]
-        for half, off in ((("plo_", 0), ("phi_", 32)) if sign2 is None and not p12 else ()):
+            body += self.pred_mask_pk16(sign2)
+        else:
+            body += self.pred_mask_rows(cond, sign)
+        if sign is not None:
+            body += ["    d_ &= ~(((u64)phi_ << 32) | (u64)plo_);"]
+        else:
+            body += ["    d_ &= ((u64)phi_ << 32) | (u64)plo_;"]
+        return body
+
+    def pred_mask_p12(self) -> List[str]:
+        # 12-bit chunks: decode 8 rows per 3 dwords, pair them into 16-bit halves, packed tests
+        p12 = self.f.p12
+        sign12 = self.g1.cnf_sign2(self.lpreds, "pw{}_", offset="a.P12O_{}")
+        body = []
+        for i in range(8):
+            body.append("    {")
+            for sl in p12:
+                body += [f"      const unsigned a{sl}_ = x{sl}q@S@[{3 * i}], "
+                         f"b{sl}_ = x{sl}q@S@[{3 * i + 1}], c{sl}_ = x{sl}q@S@[{3 * i + 2}];",
+                         f"      const unsigned v{sl}_0 = a{sl}_ & 0xFFFu, "
+                         f"v{sl}_1 = (a{sl}_ >> 12) & 0xFFFu, "
+                         f"v{sl}_2 = ((a{sl}_ >> 24) | (b{sl}_ << 8)) & 0xFFFu, "
+                         f"v{sl}_3 = (b{sl}_ >> 4) & 0xFFFu;",
+                         f"      const unsigned v{sl}_4 = (b{sl}_ >> 16) & 0xFFFu, "
+                         f"v{sl}_5 = ((b{sl}_ >> 28) | (c{sl}_ << 4)) & 0xFFFu, "
+                         f"v{sl}_6 = (c{sl}_ >> 8) & 0xFFFu, v{sl}_7 = c{sl}_ >> 20;"]
+            for q in range(4):
+                w = 4 * i + q
+                half, wl = ("plo_", w) if w < 16 else ("phi_", w - 16)
+                body.append("      {")
+                for sl in p12:
+                    body.append(f"        const unsigned pw{sl}_ = v{sl}_{2 * q} | "
+                                f"(v{sl}_{2 * q + 1} << 16);")
+                body += [f"        const unsigned s2_ = {sign12};",
+                         f"        {half} |= (s2_ >> {15 - wl}) & {(1 << wl) | (1 << (wl + 16))}u;",
+                         "      }"]
+            body.append("    }")
+        return body + ["    plo_ = hs_unzip16(plo_);", "    phi_ = hs_unzip16(phi_);"]
+
+    def pred_mask_pk16(self, sign2: str) -> List[str]:
+        """16-bit codes, two rows per loaded word (``sign2``: their packed range test)."""
+        body = []
+        for half, off in (("plo_", 0), ("phi_", 16)):
+            body += ["    #pragma unroll",
+                     "    for (int w_ = 0; w_ < 16; ++w_) {",
+                     f"      const unsigned s2_ = {sign2.replace('[w_]', f'[w_ + {off}]')};",
+                     f"      {half} |= (s2_ >> (15 - w_)) & ((1u << w_) | (1u << (w_ + 16)));",
+                     "    }",
+                     f"    {half} = hs_unzip16({half});"]
+        return body
+
+    def pred_mask_rows(self, cond: str, sign: Optional[str]) -> List[str]:
+        """Any predicate, row by row: each column's element from its packed words, decoded, then
+        the sign test's fail bit or ``cond``'s pass bit.  Adds B<slot> of a based compact code."""
+        g1, cols, body = self.g1, self.cols, []
+
+        def raw_of(name: str, off: int) -> str:
+            et, word, bits, per = self.elem[name]
+            i = f"{off} + k_"
+            w = word.format(i=i)
+            return f"(({et})({w} >> ({bits} * (({i}) % {per}))))" if per > 1 else f"(({et}){w})"
+        for half, off in (("plo_", 0), ("phi_", 32)):
             body.append("    #pragma unroll")
             body.append("    for (int k_ = 0; k_ < 32; ++k_) {")
-
-            def raw_of(name: str) -> str:
-                et, word, bits, per = elem[name]
-                i = f"{off} + k_"
-                w = word.format(i=i)
-                return f"(({et})({w} >> ({bits} * (({i}) % {per}))))" if per > 1 else f"(({et}){w})"
-            for sl in pslots:
+            for sl in self.pslots:
                 ct = J._CTYPE[cols[sl][0]]
                 enc = cols[sl][2]
-                raw = raw_of(f"x{sl}")
+                raw = raw_of(f"x{sl}", off)
                 body.append(f"      const auto xr{sl}_k = {raw};")
                 raw = f"xr{sl}_k"
                 if enc:
                     body.append(f"      const int r{sl}_k = (int){raw};")
                 if enc and enc[1]:
-                    bq = args.add("q", f"B{sl}", "long long")
+                    bq = self.args.add("q", f"B{sl}", "long long")
                     body.append(f"      const i64 q{sl}_k = {bq} + (i64){raw};")
                 body.append(f"      const {ct} x{sl}_k = {g1.decode(sl, raw)};")
                 if cols[sl][1]:
-                    body.append(f"      const bool n{sl}_k = {raw_of(f'n{sl}')} != 0;")
+                    body.append(f"      const bool n{sl}_k = {raw_of(f'n{sl}', off)} != 0;")
             if sign is not None:
                 body.append(f"      {half} |= ((unsigned)({sign}) >> 31) << k_;")
             else:
                 body.append(f"      {half} |= ({cond} ? 1u : 0u) << k_;")
             body.append("    }")
-        if sign is not None:
-            body += ["    d_ &= ~(((u64)phi_ << 32) | (u64)plo_);"]
-        else:
-            body += ["    d_ &= ((u64)phi_ << 32) | (u64)plo_;"]
-    if pipe:
+        return body
+
+    def prefetch(self) -> List[str]:
+        """RS_PIPE: the next tile's loads into the other buffer, and the geometry of the tile
+        after it."""
         # this tile's column words are consumed: the next tile's loads go out now
         # (the scheduler must not hoist the next tile's loads above this tile's masks: both
         # buffers would be live at once)
         # The loads are unconditional - a load under a condition keeps the buffer's previous
         # contents live through the whole tile - and past the wavefront's last tile they read
         # an empty buffer range (no memory traffic; the tag words re-read this tile's).
-        body += ["    __builtin_amdgcn_sched_barrier(0);",
-                 "    { const bool nx_ = @T@ + 1 < t1;",
-                 "      if (nx_) { rsC = rsN; reC = reN; tbC = tbN; gmC = gmN; grC = grN; }"]
-        body += ["  " + x.replace("@S@", "@O@").replace("@LIVE@", "!nx_ ? 0ll : ")
-                 for x in issue]
-        body += ["      if (@T@ + 2 < t1) {"]
-        body += ["    " + x for x in geom("(@T@ + 2)", "N")]
-        body += ["      }", "    }"]
-    def scan(q: str, tot: bool = True) -> List[str]:
+        return ["    __builtin_amdgcn_sched_barrier(0);",
+                "    { const bool nx_ = @T@ + 1 < t1;",
+                "      if (nx_) { rsC = rsN; reC = reN; tbC = tbN; gmC = gmN; grC = grN; }"] + \
+            self.subst(self.issue, "  ", S="@O@", LIVE="!nx_ ? 0ll : ") + \
+            ["      if (@T@ + 2 < t1) {"] + \
+            self.subst(self.geom("(@T@ + 2)", "N"), "    ") + \
+            ["      }", "    }"]
+
+    def scan(self, q: str, tot: bool = True) -> List[str]:
         """Exclusive scan of the lanes' counts of row mask d<q>_ (cn / inc / tot <q>_)."""
         return [f"    const int cn{q}_ = __popcll(d{q}_);",
                 f"    int inc{q}_ = cn{q}_;",
                 f"    for (int o_ = 1; o_ < 64; o_ <<= 1) {{ const int y_ = __shfl_up(inc{q}_, o_, 64); "
                 f"if (ln >= o_) inc{q}_ += y_; }}"] + \
             ([f"    const int tot{q}_ = __shfl(inc{q}_, 63, 64);"] if tot else [])
-    if pair:
-        # both queries' candidate counts of the tile (each at most 4096) in one reduction; the
-        # scans run where a path needs them, so no lane count lives across the other path
-        body += ["    int sm_ = __popcll(d_) | (__popcll(db_) << 16);",
-                 "    for (int o_ = 32; o_ > 0; o_ >>= 1) sm_ += __shfl_xor(sm_, o_, 64);",
-                 "    const int tot_ = sm_ & 0xFFFF, totb_ = sm_ >> 16;"]
-    else:
-        body += scan("")
-    layout = pack_layout(p, compacts, cand)
-    packed = {sl: (off, nb) for sl, off, nb in layout} if layout else {}
-    carry_gen = J._Gen(args, cols, SPLIT, ("tcw_", "tcw_"), frozenset(), True) \
-        if tk is not None else None
 
-    def walk(at: str = "", hp: str = "hp_") -> List[str]:
-        """The walk of list entries [0, wn_) of ``lst_`` (from element ``at`` on): entry
-        cb + 64 k + ln goes to lane ln, k ascending.  RS_KEEP: of the wn_ ring entries of
-        ``kw_`` (ring at ``at``) from slot ``hp`` on; the entries are the tail words themselves."""
+    def walk(self, at: str = "", hp: str = "hp_") -> List[str]:
+        """Step 3's second half.  The walk of list entries [0, wn_) of ``lst_`` (from element
+        ``at`` on): entry cb + 64 k + ln goes to lane ln, k ascending; aggregate inputs loaded at
+        those rows only and accumulated.  RS_KEEP: of the wn_ ring entries of ``kw_`` (ring at
+        ``at``) from slot ``hp`` on; the entries are the tail words themselves.
+
+        With ``hk`` (an exec.hash_agg.KeyPlan over left columns) the walk groups by the hash key
+        instead: each pass's 64 list entries are consecutive passing rows, so a segmented shuffle
+        reduce folds a group's rows (one run = one left join key) before one table probe
+        (``jit_hash._hash_accumulate``); kernel ``hs_jit_run_bits_hash``, no partials.
+
+        With ``tk`` as well (an exec.hash_agg.TopKPlan: ORDER BY <aggregate> LIMIT k over those
+        groups), the windows are walked in row order with the last segment of each carried into
+        the next (``jit_hash._topk_accumulate``): a key is final when the walk leaves it and
+        competes for the wavefront's top-K registers instead of probing the table; only keys that
+        may continue into the neighbouring wavefronts' tiles (at most two per wavefront) go to
+        the table (kernel ``hs_jit_run_bits_topk``; every wavefront writes its list at the end).
+
+        Adds (first call) PK, group_base, num_groups, B<slot> and what the accumulation adds."""
+        f, p, args, tail, tk = self.f, self.p, self.args, self.tail, self.tk
+        keep, layout, packed, KB = f.keep, f.layout, self.packed, f.KB  # noqa: N806
         # (RS_KEEP: LDS reads need no batch in flight - one entry per lane and step, fewer registers)
-        WE = 1 if keep else EW  # noqa: N806
+        WE = 1 if keep else f.EW  # noqa: N806
         w = [f"    for (int cb = 0; cb < wn_; cb += {64 * WE}) {{"]
         if layout and not keep:
             w.append("      const u64* PKt_ = a.PK + tb0;")
@@ -1785,7 +1840,7 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
             if tk is not None:
                 w.append(f"{ind2}const unsigned crn{k} = cok{k} ? (unsigned)lrn_[wq][ce{k}] : "
                          f"0xFFFFFFFFu;")
-        gs = [J._Gen(args, cols, SPLIT, (f"crow{k}", f"crow{k}"), approx, True)
+        gs = [J._Gen(args, self.cols, SPLIT, (f"crow{k}", f"crow{k}"), self.approx, True)
               for k in range(WE)]
         if layout:
             args.add("p", "PK", "const unsigned long long*")
@@ -1807,7 +1862,7 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
             it = f"c{k}"
             w.append(f"{ind2}{{ bool cok = cok{k};")
             gvar = "gic"
-            if grouped:
+            if f.grouped:
                 base = args.add("q", "group_base", "long long")
                 ng = args.add("q", "num_groups", "long long")
                 w.append(f"{ind2}const i64 glc = (i64){J._rename(f'x{p.group_col}', tail, it)} - "
@@ -1815,233 +1870,295 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
                 w.append(f"{ind2}cok = cok && {J._rename(g.ok(p.group_col), tail, it)} && "
                          f"glc >= 0 && glc < {ng};")
                 w.append(f"{ind2}const int {gvar} = cok ? (int)glc : 0;")
-            if hk is not None:
+            if self.hk is not None:
                 w += [J._rename(x, tail, it)
-                      for x in JH._hash_accumulate(g, aggs, hk, "cok", ind2, tk=tk,
+                      for x in JH._hash_accumulate(g, self.aggs, self.hk, "cok", ind2, tk=tk,
                                                    seg=f"crn{k}" if tk is not None else None,
                                                    row=f"crow{k}", run=f"qb_ + (i64)crn{k}",
-                                                   carry_gen=carry_gen)]
+                                                   carry_gen=self.carry_gen)]
             else:
                 w += [J._rename(x, tail, it)
-                      for x in J._accumulate(g, aggs, grouped, "cok", gvar, ind2)]
+                      for x in J._accumulate(g, self.aggs, f.grouped, "cok", gvar, ind2)]
             w.append(f"{ind2}}}")
         w.append("    }")
         return w
 
-    if cand:
-        # candidates -> clst_ (CC per pass) -> tail word -> left predicates on its fields ->
-        # stable append to lst_; the walk runs after the tile's last pass (or when lst_
-        # holds more than CAP entries: a pass adds at most CC)
-        assert layout is not None
-        sign = g1.cnf_sign(lpreds)
-        assert sign is not None
-        fields = {sl: off for sl, off, nb in layout if sl in cand and nb == 2}
-        assert set(fields) == set(cand)
-        # (RS_KEEP: the walk has no row, only the word - every tail slot is one of its fields)
-        assert not keep or (not grouped and all(sl in packed for sl in tail))
-        sync = J._wave_sync(True)
-
-        def to_clst(q: str, entry: str) -> List[str]:
-            """Candidates [wb_, wb_ + CC) of row mask d<q>_ (in row order) -> ``clst_``."""
-            return [f"      {{ int pos_ = inc{q}_ - cn{q}_ - wb_; u64 e_ = (pos_ < " + str(CC) +
-                    f" && pos_ + cn{q}_ > 0) ? d{q}_ : 0ull;",
-                    "        while (e_) { const int bq_ = __builtin_ctzll(e_); "
-                    f"if (pos_ >= 0 && pos_ < {CC}) clst_[wq][pos_] = (unsigned short)({entry}); "
-                    "++pos_; e_ &= e_ - 1ull; } }",
-                    f"      {sync}",
-                    f"      const int cw_ = tot{q}_ - wb_ < {CC} ? tot{q}_ - wb_ : {CC};"]
-
-        def append(k: int, ok: str, at: str, np: str) -> List[str]:
-            """Stable append of pass entry k's rows that pass the left predicates."""
-            return [f"      {{ const bool fp_ = {ok} && (int)({J._rename(sign, pslots, f'f{k}')}) >= 0;",
-                    "        const u64 bl_ = __ballot(fp_);",
-                    f"        if (fp_) lst_[wq][{at}{np} + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bl_ >> 32), "
-                    f"__builtin_amdgcn_mbcnt_lo((unsigned)bl_, 0u))] = (unsigned short)fof{k};",
-                    f"        {np} += __popcll(bl_); }}"]
-
-        def fld(k: int) -> List[str]:
-            return [f"      const int r{sl}_f{k} = (int)(short)(unsigned short)(fw{k}_ >> {off});"
-                    for sl, off in fields.items()]
-
-        # RS_KEEP.  Per query four wavefront-uniform counters: np entries appended since the last
-        # reset (what ``np_ <= CAP`` tests, as in the listing form), ch of them consumed - a
-        # multiple of 64, so entry e still goes to lane e % 64 - and kp / hp, the ring slots of
-        # entries np / ch (np, ch modulo KB, kept by conditional subtraction).
-        def append_keep(k: int, ok: str, at: str, s: str) -> List[str]:
-            """``append`` with the entry's tail word written to ring slot (np + prefix) % KB."""
-            return [f"      {{ const bool fp_ = {ok} && (int)({J._rename(sign, pslots, f'f{k}')}) >= 0;",
-                    "        const u64 bl_ = __ballot(fp_);",
-                    f"        const int ix_ = kp{s}_ + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bl_ >> 32), "
-                    "__builtin_amdgcn_mbcnt_lo((unsigned)bl_, 0u));",
-                    f"        if (fp_) kw_[wq][{at}ix_ - (ix_ >= {KB} ? {KB} : 0)] = fw{k}_;",
-                    f"        const int nb_ = __popcll(bl_); np{s}_ += nb_; kp{s}_ += nb_; "
-                    f"if (kp{s}_ >= {KB}) kp{s}_ -= {KB}; }}"]
-
-        def consume(s: str, fin: str, at: str = "") -> List[str]:
-            """Sum the pending entries' whole groups of 64 - all of them where ``fin`` - from ring
-            ``at``: the walk of [ch, ch + wn_), in the listing form's order."""
-            w = walk(at, f"hp{s}_")
-            return [f"    {{ const int wn_ = ({fin} ? np{s}_ : (np{s}_ & ~63)) - ch{s}_;"] + \
-                (set_b(w) if s == "b" else w) + \
-                [f"      ch{s}_ += wn_; hp{s}_ += wn_; if (hp{s}_ >= {KB}) hp{s}_ -= {KB}; }}"]
-
-        def cand_loop_keep(q: str) -> List[str]:
-            """``cand_loop`` with the sums taken after every pass; ``fin_``: where the listing
-            form walks and resets."""
-            c = ["    int np_ = 0, wb_ = 0, kp_ = 0, ch_ = 0, hp_ = 0;",
-                 "    for (;;) {",
-                 f"    if (wb_ < tot{q}_) {{"]
-            c += to_clst(q, "64 * ln + bq_")
-            for k in range(EW):
-                c += [f"      const bool fok{k} = {64 * k} + ln < cw_;",
-                      f"      const int fof{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;"]
-            for k in range(EW):
-                c.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
-            c.append(f"      {sync}")
-            for k in range(EW):
-                c += fld(k) + append_keep(k, f"fok{k}", "", "")
-            c += [f"      wb_ += {CC};",
-                  "    }",
-                  f"    const bool fin_ = !(wb_ < tot{q}_ && np_ <= {CAP});",
-                  f"    {sync}"]
-            c += consume("", "fin_")
-            c += [f"    {sync}",
-                  "    if (fin_) { np_ = 0; kp_ = 0; ch_ = 0; hp_ = 0; "
-                  f"if (wb_ >= tot{q}_) break; }}",
-                  "    }"]
-            return c
-
-        def cand_loop(q: str) -> List[str]:
-            """One query's candidate loop over the tile (the single form's)."""
-            if keep:
-                return cand_loop_keep(q)
-            c = ["    int np_ = 0, wb_ = 0;",
-                 "    for (;;) {",
-                 f"    if (wb_ < tot{q}_) {{"]
-            c += to_clst(q, "64 * ln + bq_")
-            for k in range(EW):
-                c += [f"      const bool fok{k} = {64 * k} + ln < cw_;",
-                      f"      const int fof{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;"]
-            for k in range(EW):
-                c.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
-            c.append(f"      {sync}")
-            for k in range(EW):
-                c += fld(k) + append(k, f"fok{k}", "", "np_")
-            c += [f"      wb_ += {CC};",
-                  f"      if (wb_ < tot{q}_ && np_ <= {CAP}) continue;",
-                  "    }",
-                  "    const int wn_ = np_;",
-                  f"    {sync}"]
-            c += walk()
-            c += [f"    {sync}", "    np_ = 0;", f"    if (wb_ >= tot{q}_) break;", "    }"]
-            return c
-
-        body.append("    const u64* PKc_ = a.PK + tb0;")
-        if not pair:
-            body += cand_loop("")
-        else:
-            # union path: both queries at most CAP candidates in the tile (wavefront-uniform)
-            body += [f"    if (tot_ <= {CAP} && totb_ <= {CAP}) {{   // union path",
-                     "    const u64 du_ = d_ | db_;"]
-            body += scan("u")
-            body += ["    int npa_ = 0, npb_ = 0;"] + \
-                (["    int kpa_ = 0, cha_ = 0, hpa_ = 0, kpb_ = 0, chb_ = 0, hpb_ = 0;"]
-                 if keep else []) + \
-                [f"    for (int wb_ = 0; wb_ < totu_; wb_ += {CC}) {{"]
-            # entry: row offset (12 bits), bit 12: a candidate of A, bit 13: of B
-            body += to_clst("u", "(64 * ln + bq_) | (int)((d_ >> bq_) & 1ull) << 12 | "
-                                 "(int)((db_ >> bq_) & 1ull) << 13")
-            for k in range(EW):
-                body += [f"      const bool fok{k} = {64 * k} + ln < cw_;",
-                         f"      const int fen{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;",
-                         f"      const int fof{k} = fen{k} & 4095;"]
-            for k in range(EW):
-                body.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
-            body.append(f"      {sync}")
-            for k in range(EW):
-                body += fld(k) + (
-                    append_keep(k, f"(fen{k} & 4096)", "", "a") +
-                    set_b(append_keep(k, f"(fen{k} & 8192)", f"{KB} + ", "b")) if keep else
-                    append(k, f"(fen{k} & 4096)", "", "npa_") +
-                    set_b(append(k, f"(fen{k} & 8192)", f"{CAP} + ", "npb_")))
-            if keep:
-                # whole groups after every pass, the rest after the tile's last: A's, then B's
-                body += [f"      const bool fin_ = wb_ + {CC} >= totu_;",
-                         f"      {sync}"] + consume("a", "fin_") + \
-                    consume("b", "fin_", f"{KB} + ") + [f"      {sync}", "    }"]
-            else:
-                body += ["    }",
-                         f"    {sync}",
-                         "    { const int wn_ = npa_;"] + walk() + ["    }",
-                         "    { const int wn_ = npb_;"] + set_b(walk(f"{CAP} + ")) + ["    }",
-                         f"    {sync}"]
-            body += ["    } else {   // dense path",
-                     "    {"] + scan("", False) + cand_loop("") + ["    }",
-                     "    {"] + scan("b", False) + set_b(cand_loop("b")) + ["    }", "    }"]
-    else:
-        body += [
+    def stream_fill(self) -> List[str]:
+        """Step 3's first half, the streaming forms: the rows of (tag mask & predicate mask) -
+        the join's passing rows, a few percent - go to a per-wavefront LDS list (offsets from a
+        shuffle scan of the lanes' popcounts), which the wavefront walks EW entries per lane per
+        pass, CAP entries a round."""
+        CAP = self.f.CAP  # noqa: N806
+        return [
           f"    for (int wb_ = 0; wb_ < tot_; wb_ += {CAP}) {{",
           f"    const int wn_ = tot_ - wb_ < {CAP} ? tot_ - wb_ : {CAP};",
           "    { int pos_ = inc_ - cn_ - wb_; u64 e_ = d_;",
           "      while (e_) { const int bq_ = __builtin_ctzll(e_); "
           f"if (pos_ >= 0 && pos_ < {CAP}) {{ lst_[wq][pos_] = (unsigned short)(64 * ln + bq_); "
           + ("lrn_[wq][pos_] = (unsigned short)(qr_ + __popcll(m_ & ((2ull << bq_) - 1ull))); "
-             if tk is not None else "") +
+             if self.f.topk else "") +
           "} ++pos_; e_ &= e_ - 1ull; } }",
-          f"    {J._wave_sync(False)}"]
-        body += walk()
-        body += [f"    {J._wave_sync(False)}", "    }"]
+          f"    {J._wave_sync(False)}"] + self.walk() + [f"    {J._wave_sync(False)}", "    }"]
 
-    def tile(tv: str, cur: str, nxt: str) -> List[str]:
-        return ["   {"] + [x.replace("@T@", tv).replace("@S@", cur).replace("@O@", nxt)
-                          for x in body] + ["   }"]
-    if pipe == 2:
-        b += ["  for (i64 t = t0; t < t1; t += 2) {"]
-        b += tile("t", "A", "B")
-        b += ["    if (t + 1 >= t1) break;"]
-        b += tile("(t + 1)", "B", "A")
-        b += ["  }"]
-    elif pipe:
-        b += ["  for (i64 t = t0; t < t1; ++t) {"]
-        b += tile("t", "A", "A")
-        b += ["  }"]
-    else:
-        b += ["  for (i64 t = t0; t < t1; ++t) {"]
-        b += tile("t", "A", "A")
-        b += ["  }"]
-    if hk is None and pair:
-        # each query's block partials, folded as in its own launch
-        b += ["  {"] + J._flush(aggs, grouped) + ["  }", "  {"] + \
-            set_b(J._flush(aggs, grouped)) + ["  }"]
-    elif hk is None:
-        b += J._flush(aggs, grouped)
-    if tk is not None:
-        b += JH._topk_carry_final(aggs, hk, tk, "  ", carry_gen)
+    def append(self, k: int, ok: str, s: str) -> List[str]:
+        """Stable append (ballot + prefix count) of pass entry k's row for query ``s`` ("" the
+        single forms' / the dense path's, "a" / "b" the union path's) if it is a candidate of
+        the query (``ok``) and passes the left predicates.  Listing form: its row offset goes to
+        ``lst_`` at np<s>_ + prefix.  RS_KEEP: its tail word to ring slot (np + prefix) % KB.
+        Per query four wavefront-uniform counters: np entries appended since the last
+        reset (what ``np_ <= CAP`` tests, as in the listing form), ch of them consumed - a
+        multiple of 64, so entry e still goes to lane e % 64 - and kp / hp, the ring slots of
+        entries np / ch (np, ch modulo KB, kept by conditional subtraction)."""
+        KB, at = self.f.KB, self.at(s)  # noqa: N806
+        out = [f"      {{ const bool fp_ = {ok} && "
+               f"(int)({J._rename(self.sign, self.pslots, f'f{k}')}) >= 0;",
+               "        const u64 bl_ = __ballot(fp_);"]
+        if not self.f.keep:
+            return out + [
+                f"        if (fp_) lst_[wq][{at}np{s}_ + {_BALLOT_PREFIX}] = (unsigned short)fof{k};",
+                f"        np{s}_ += __popcll(bl_); }}"]
+        return out + [
+            f"        const int ix_ = kp{s}_ + {_BALLOT_PREFIX};",
+            f"        if (fp_) kw_[wq][{at}ix_ - (ix_ >= {KB} ? {KB} : 0)] = fw{k}_;",
+            f"        const int nb_ = __popcll(bl_); np{s}_ += nb_; kp{s}_ += nb_; "
+            f"if (kp{s}_ >= {KB}) kp{s}_ -= {KB}; }}"]
 
-        def key_lines(j: int, ind_: str) -> List[str]:
-            gk = J._Gen(args, cols, SPLIT, (f"tkr{j}", f"tkr{j}"), frozenset(), True)
-            out: List[str] = []
-            for c in hk.cols:
-                J._uload(gk, c.slot, "F", out, ind_)
-            out += JH._hash_key_lines(gk, hk, "tkey_l", "_F", ind_)
-            out.append(f"{ind_}const u64 tkey_ = tkey_l;")
-            return out
-        b += JH._topk_flush(aggs, tk, args, "wid", key_lines)
-    name = "hs_jit_run_bits_cand2" if pair else "hs_jit_run_bits_cand" if cand else \
-        "hs_jit_run_bits_scan" if hk is None else \
-        ("hs_jit_run_bits_hash" if tk is None else "hs_jit_run_bits_topk")
+    def filter_pass(self, q: str, entry: str, appends, member: bool = False) -> List[str]:
+        """One filter pass of the candidate forms: candidates [wb_, wb_ + CC) of row mask d<q>_
+        (in row order) -> ``clst_`` as ``entry`` (of lane ln's row bq_), each candidate's
+        row-packed tail word loaded (it holds the predicate columns' codes as extra fields), the
+        fields taken out, and ``appends(k)``: the stable append(s) of pass entry k.  ``member``:
+        the entry carries membership bits (fen<k>) over its 12-bit row offset (the union path)."""
+        f, sync = self.f, J._wave_sync(True)
+        CC, EW = f.CC, f.EW  # noqa: N806
+        fields = {sl: off for sl, off, nb in f.layout if sl in f.cand and nb == 2}
+        c = [f"      {{ int pos_ = inc{q}_ - cn{q}_ - wb_; u64 e_ = (pos_ < " + str(CC) +
+             f" && pos_ + cn{q}_ > 0) ? d{q}_ : 0ull;",
+             "        while (e_) { const int bq_ = __builtin_ctzll(e_); "
+             f"if (pos_ >= 0 && pos_ < {CC}) clst_[wq][pos_] = (unsigned short)({entry}); "
+             "++pos_; e_ &= e_ - 1ull; } }",
+             f"      {sync}",
+             f"      const int cw_ = tot{q}_ - wb_ < {CC} ? tot{q}_ - wb_ : {CC};"]
+        for k in range(EW):
+            c.append(f"      const bool fok{k} = {64 * k} + ln < cw_;")
+            if member:
+                c += [f"      const int fen{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;",
+                      f"      const int fof{k} = fen{k} & 4095;"]
+            else:
+                c.append(f"      const int fof{k} = fok{k} ? (int)clst_[wq][{64 * k} + ln] : 0;")
+        for k in range(EW):
+            c.append(f"      const u64 fw{k}_ = PKc_[fof{k}];")
+        c.append(f"      {sync}")
+        for k in range(EW):
+            c += [f"      const int r{sl}_f{k} = (int)(short)(unsigned short)(fw{k}_ >> {off});"
+                  for sl, off in fields.items()] + appends(k)
+        return c
+
+    def consume(self, s: str, fin: str) -> List[str]:
+        """RS_KEEP.  Sum the pending entries' whole groups of 64 - all of them where ``fin`` -
+        from query ``s``'s ring: the walk of [ch, ch + wn_), in the listing form's order."""
+        KB = self.f.KB  # noqa: N806
+        w = self.walk(self.at(s), f"hp{s}_")
+        return [f"    {{ const int wn_ = ({fin} ? np{s}_ : (np{s}_ & ~63)) - ch{s}_;"] + \
+            (self.set_b(w) if s == "b" else w) + \
+            [f"      ch{s}_ += wn_; hp{s}_ += wn_; if (hp{s}_ >= {KB}) hp{s}_ -= {KB}; }}"]
+
+    def cand_loop(self, q: str) -> List[str]:
+        """One query's candidate loop over the tile (the single form's): filter passes of CC
+        candidates; the walk runs once per tile, after its last candidate (so a tile's
+        passing-row sequence, and with it every lane's sum order, is that of the streaming form
+        while the tile has at most CAP passing rows), or earlier whenever ``lst_`` holds more
+        than CAP entries (a pass adds at most CC).  That is the *listing form* (RS_KEEP off): its
+        walk loads the tail word of a passing row again (an L2 hit a few hundred cycles after the
+        filter's load) - one more dependent round trip per tile.
+
+        With RS_KEEP (the default) the filter pass keeps the word instead: the stable append
+        writes the 64-bit word ``fw<k>_`` of a passing entry into a per-wavefront ring ``kw_`` at
+        slot (entries appended since the last reset + ballot prefix) mod KB, and nothing into
+        ``lst_``, which goes.  The walk hands entry e (counted since the reset) to lane e % 64 in
+        ascending order, so any complete group of 64 entries can be summed as soon as it exists:
+        after every pass the ``cb`` loop takes the pending whole groups from the ring (its head
+        stays a multiple of 64), and the rest where the listing form walks (``fin_``) - after the
+        tile's last pass, or once more than CAP entries were appended since the reset (``np_``
+        still counts appended, not pending, entries, so resets and with them the lane of every
+        later entry fall where they fell).  Each lane therefore adds the same values in the same
+        order; a different number of masked-off slots only adds +0.0 to sums that start at +0.0.
+        KB = 63 + CC: the most a ring can hold before a consumption (a leftover below 64 plus one
+        pass's CC appends) - 2.5 KB per wavefront instead of 8 (CAP + CC) for a whole tile's
+        words.  Every tail slot is a field of the word (``pack_layout`` is required here), so the
+        walk keeps no row offset and issues no global load; it takes one entry per lane and step
+        (LDS reads need no batch in flight), which with the addresses and in-flight loads gone
+        brings the single form from 70 to 62 VGPRs."""
+        f, sync = self.f, J._wave_sync(True)
+        keep, CAP, CC = f.keep, f.CAP, f.CC  # noqa: N806
+        more = f"wb_ < tot{q}_ && np_ <= {CAP}"
+        c = ["    int np_ = 0, wb_ = 0" + (", kp_ = 0, ch_ = 0, hp_ = 0;" if keep else ";"),
+             "    for (;;) {",
+             f"    if (wb_ < tot{q}_) {{"]
+        c += self.filter_pass(q, "64 * ln + bq_", lambda k: self.append(k, f"fok{k}", ""))
+        c += [f"      wb_ += {CC};"] + ([] if keep else [f"      if ({more}) continue;"]) + ["    }"]
+        if keep:
+            c += [f"    const bool fin_ = !({more});", f"    {sync}"] + self.consume("", "fin_") + \
+                [f"    {sync}",
+                 "    if (fin_) { np_ = 0; kp_ = 0; ch_ = 0; hp_ = 0; "
+                 f"if (wb_ >= tot{q}_) break; }}"]
+        else:
+            c += ["    const int wn_ = np_;", f"    {sync}"] + self.walk() + \
+                [f"    {sync}", "    np_ = 0;", f"    if (wb_ >= tot{q}_) break;"]
+        return c + ["    }"]
+
+    def pair_union(self) -> List[str]:
+        """Pair form, a tile in which neither query has more than CAP candidates - every tile of
+        the headline: the candidates of (mask A | mask B) go through ``clst_`` with two
+        membership bits beside the 12-bit row offset, each tail word is loaded once, either
+        query's predicates are tested with its literals under its membership bit, and the two
+        stable appends fill two lists (A at 0, B at CAP of one ``lst_`` of 2 CAP + CC entries:
+        neither can exceed CAP).  After the tile's last pass the single form's walk runs over A's
+        list into A's accumulators, then over B's into B's: the single form would not have walked
+        earlier either, so every lane adds the same values in the same order.  With RS_KEEP the
+        union path has two rings (A's at 0, B's at KB of one ``kw_``) and sums A's whole groups,
+        then B's, after every pass."""
+        f, sync = self.f, J._wave_sync(True)
+        body = ["    const u64 du_ = d_ | db_;"] + self.scan("u")
+        body += ["    int npa_ = 0, npb_ = 0;"] + \
+            (["    int kpa_ = 0, cha_ = 0, hpa_ = 0, kpb_ = 0, chb_ = 0, hpb_ = 0;"]
+             if f.keep else []) + \
+            [f"    for (int wb_ = 0; wb_ < totu_; wb_ += {f.CC}) {{"]
+        # entry: row offset (12 bits), bit 12: a candidate of A, bit 13: of B
+        body += self.filter_pass(
+            "u", "(64 * ln + bq_) | (int)((d_ >> bq_) & 1ull) << 12 | "
+            "(int)((db_ >> bq_) & 1ull) << 13",
+            lambda k: self.append(k, f"(fen{k} & 4096)", "a") +
+            self.set_b(self.append(k, f"(fen{k} & 8192)", "b")), member=True)
+        if f.keep:
+            # whole groups after every pass, the rest after the tile's last: A's, then B's
+            return body + [f"      const bool fin_ = wb_ + {f.CC} >= totu_;", f"      {sync}"] + \
+                self.consume("a", "fin_") + self.consume("b", "fin_") + [f"      {sync}", "    }"]
+        return body + ["    }", f"    {sync}",
+                       "    { const int wn_ = npa_;"] + self.walk() + ["    }",
+                       "    { const int wn_ = npb_;"] + self.set_b(self.walk(self.at("b"))) + \
+            ["    }", f"    {sync}"]
+
+    def candidates(self) -> List[str]:
+        """Step 3's first half, the candidate forms (``cand``: the predicate slots of
+        ``prune_plan``; kernel ``hs_jit_run_bits_cand``): phase 1 tagged only runs that may hold a
+        passing row, so step 2's row stream goes.  The rows of (tag mask & range mask) are the
+        tile's *candidates*; they go to a small per-wavefront LDS list ``clst_``, 64 * RS_WALK at
+        a time, the wavefront loads each candidate's row-packed tail word, tests the left
+        predicates on its fields and appends the passing entries stably to ``lst_`` (or their
+        words to the ring), which the walk consumes (``filter_pass``, ``cand_loop``).
+
+        Pair form (``pair``, ``cand_pair``; kernel ``hs_jit_run_bits_cand2``): two queries tagged
+        by the pair phase 1 (bitmaps ``tags`` / ``tags_b``, the second literal set and partials
+        with ``PAIR_SFX``) in one pass over the same tiles.  Both row masks come from one LUT
+        expansion of the shared run starts.  A tile takes the *union path* (``pair_union``) or the
+        *dense path*: the single form's candidate loop, emitted by the same code, once per query
+        (its early walks depend on where the candidate batches fall, which a union pass cannot
+        reproduce; RS_KEEP: it uses A's ring for one query at a time).  Grid, tile split and
+        flush are the single form's, so each query's partials are bit for bit those of its own
+        launch.  Adds the left predicates' literal slots (``cnf_sign``), before the first walk's."""
+        # candidates -> clst_ (CC per pass) -> tail word -> left predicates on its fields ->
+        # stable append to lst_; the walk runs after the tile's last pass (or when lst_
+        # holds more than CAP entries: a pass adds at most CC)
+        CAP = self.f.CAP  # noqa: N806
+        self.sign = self.g1.cnf_sign(self.lpreds)
+        body = ["    const u64* PKc_ = a.PK + tb0;"]
+        if not self.f.pair:
+            return body + self.cand_loop("")
+        # union path: both queries at most CAP candidates in the tile (wavefront-uniform)
+        return body + [f"    if (tot_ <= {CAP} && totb_ <= {CAP}) {{   // union path"] + \
+            self.pair_union() + ["    } else {   // dense path", "    {"] + \
+            self.scan("", False) + self.cand_loop("") + ["    }", "    {"] + \
+            self.scan("b", False) + self.set_b(self.cand_loop("b")) + ["    }", "    }"]
+
+    def tile_body(self) -> List[str]:
+        """One tile (@T@), its buffer @S@, the next tile's buffer @O@ (``subst``)."""
+        f = self.f
+        body = self.tile_rows() + self.tag_mask() + self.xpose
+        # (the candidate form tests the predicates per candidate row, on its tail word)
+        if not f.cand:
+            body += self.pred_mask()
+        if f.pipe:
+            body += self.prefetch()
+        if not f.pair:
+            return body + self.scan("") + (self.candidates() if f.cand else self.stream_fill())
+        # both queries' candidate counts of the tile (each at most 4096) in one reduction; the
+        # scans run where a path needs them, so no lane count lives across the other path
+        return body + ["    int sm_ = __popcll(d_) | (__popcll(db_) << 16);",
+                       "    for (int o_ = 32; o_ > 0; o_ >>= 1) sm_ += __shfl_xor(sm_, o_, 64);",
+                       "    const int tot_ = sm_ & 0xFFFF, totb_ = sm_ >> 16;"] + self.candidates()
+
+    def tile_loop(self, body: List[str]) -> List[str]:
+        """The wavefront's tiles; RS_PIPE 2: unrolled by two over the buffers A and B."""
+        def tile(tv: str, cur: str, nxt: str) -> List[str]:
+            return ["   {"] + self.subst(body, T=tv, S=cur, O=nxt) + ["   }"]
+        if self.f.pipe == 2:
+            return ["  for (i64 t = t0; t < t1; t += 2) {"] + tile("t", "A", "B") + \
+                ["    if (t + 1 >= t1) break;"] + tile("(t + 1)", "B", "A") + ["  }"]
+        return ["  for (i64 t = t0; t < t1; ++t) {"] + tile("t", "A", "A") + ["  }"]
+
+    def epilogue(self) -> List[str]:
+        """The block partials (none with a hash table) and the top-K lists.  Adds the top-K
+        output slots."""
+        aggs, hk, tk, grouped, b = self.aggs, self.hk, self.tk, self.f.grouped, []
+        if hk is None and self.f.pair:
+            # each query's block partials, folded as in its own launch
+            b += ["  {"] + J._flush(aggs, grouped) + ["  }", "  {"] + \
+                self.set_b(J._flush(aggs, grouped)) + ["  }"]
+        elif hk is None:
+            b += J._flush(aggs, grouped)
+        if tk is not None:
+            b += JH._topk_carry_final(aggs, hk, tk, "  ", self.carry_gen)
+
+            def key_lines(j: int, ind_: str) -> List[str]:
+                gk = J._Gen(self.args, self.cols, SPLIT, (f"tkr{j}", f"tkr{j}"), frozenset(), True)
+                out: List[str] = []
+                for c in hk.cols:
+                    J._uload(gk, c.slot, "F", out, ind_)
+                out += JH._hash_key_lines(gk, hk, "tkey_l", "_F", ind_)
+                out.append(f"{ind_}const u64 tkey_ = tkey_l;")
+                return out
+            b += JH._topk_flush(aggs, tk, self.args, "wid", key_lines)
+        return b
+
+
+def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
+                        cand: tuple = (), pair: bool = False) -> J.Kernel:
+    """Phase 2 for 1-bit tags, bit-parallel: the dense per-row scan spends ~20 VALU
+    instructions per row (decode, predicate, run index by popcount, tag extract, compaction
+    ballot + mbcnt), which bounds it below HBM speed.  Here a wavefront takes 4096-row tiles of
+    the left ranges, lane l the 64-row group l of its tile, and works on 64-bit row masks: the
+    tag mask (1), the predicate mask (2), and the rows of their AND through an LDS list into the
+    walk (3).  The forms, and the ``_BitsScan`` stages a tile takes after ``tag_mask``:
+
+    * streaming (``hs_jit_run_bits_scan``): ``pred_mask``, ``stream_fill``, ``walk``;
+    * ``hk`` / ``hk, tk`` (``..._hash`` / ``..._topk``): the same, ``walk`` probing a table /
+      keeping a top-K, which ``epilogue`` writes;
+    * ``cand`` (``..._cand``): ``candidates`` -> ``cand_loop`` -> ``filter_pass`` with ``append``,
+      then ``walk`` (RS_KEEP: through ``consume``);
+    * ``cand, pair`` (``..._cand2``): ``candidates`` -> ``pair_union``, or ``cand_loop`` per query
+      (``set_b`` for the second).
+
+    The driver is the kernel top to bottom; its order is also the order in which argument slots
+    are added (``_BitsScan``), so it is part of the sources' text."""
+    s = _BitsScan(p, compacts, hk, tk, cand, pair)
+    acc = s.acc_decls()
+    bufs = s.loads()        # (before the LDS declarations: RS_LDS sizes its slab by the loads)
+    b = acc + s.lds_decls() + s.split() + bufs + s.prologue()
+    b += s.tile_loop(s.tile_body())
+    b += s.epilogue()
     # (pair form: the second accumulator set and mask put it past the 72 VGPRs of seven waves;
     # left alone the compiler takes 97 - four waves - and bounded to six it spills nine, so it
     # is bounded to five: 96 VGPRs, no scratch.  RS_KEEP: 93 at five; bounded to six it spills 18
     # and to seven 27 - the peak is now in the dense path, whose loop holds the other query's
     # accumulators and mask; the union path alone fits six (73) - so five stays)
-    waves = RS_WAVES or (5 if pair else 0)
+    waves = RS_WAVES or (5 if s.f.pair else 0)
     occ = f" __attribute__((amdgpu_waves_per_eu({waves}, {waves})))" if waves else ""
-    src = (J._PRELUDE + args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({BLOCK}){occ} void {name}(Args a) '
+    src = (J._PRELUDE + s.args.struct_src() +
+           f'extern "C" __global__ __launch_bounds__({J.BLOCK}){occ} void {s.f.name}(Args a) '
            f'{{\n' + "\n".join(b) + "\n}\n")
-    lds = (len(aggs) * p.num_groups * 32) if grouped else 0
-    return J.Kernel(src, name, args, lds)
+    lds = (len(s.aggs) * p.num_groups * 32) if s.f.grouped else 0
+    return J.Kernel(src, s.f.name, s.args, lds)
 
 
 class TwoPhaseLauncher:

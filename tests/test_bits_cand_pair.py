@@ -37,6 +37,7 @@ def _cand(p, c):
 
 def test_lowering_selects_the_pair_form():
     from hyperspace_amd.exec import jit_runs, kernel_config
+    assert (CAP, TILE) == (jit_runs.BITS_CAP, jit_runs.BITS_TILE)
     p, c = _q3_params(), _k16_compacts()
     with kernel_config.use(rs_pair=True):
         cand = _cand(p, c)
