@@ -70,7 +70,7 @@ def release_process_device_memory() -> None:
     inputs), then the caching allocator's free blocks: sessions created one after another in
     one process (e.g. ``bench.py``'s side configs) each size their cache for the whole device."""
     import torch
-    from . import device_cache, jit_join, jit_runs
+    from . import device_cache, jit, jit_join, jit_runs
     for be in list(_BACKENDS):
         be.release_device_memory()
     device_cache.clear_seeds()
@@ -78,6 +78,7 @@ def release_process_device_memory() -> None:
     jit_join._RUNS_HASH_LOWERED.clear()
     jit_runs._PACKS.clear()
     jit_runs._P12.clear()
+    jit._ROWPACKS.clear()
     jit_runs._RBOUNDS.clear()
     jit_join.LAST_MJ_LAUNCHER[0] = None
     # a plain gc.collect() skips what utils/hostgc.py froze: the released sessions' cycles

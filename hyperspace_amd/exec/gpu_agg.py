@@ -863,6 +863,8 @@ class AggOps:
                     _use_on(x, side)
             for x in g.buffers():
                 _use_on(x, side)
+            if prep.pack is not None:
+                _use_on(prep.pack, side)
             prep.marked = side
         for x in keep:      # per-query predicate buffers (IN sets, key bitmaps)
             _use_on(x, side)
@@ -877,8 +879,11 @@ class AggOps:
         grid = jit.SCAN_GRID or NL.lib().hs_scan_grid()
         compacts = self._compacts(descs or {})
         vec = jit.scan_vec(p, compacts, t.num_rows)
-        shape = jit.scan_agg_shape(p, compacts, vec)
-        k = jit.kernel_for(shape, lambda: jit.gen_scan_agg(p, compacts, vec))
+        # the row-packed copy of the scan's columns: built at the table's first such scan
+        pk = jit.scan_pack(p, compacts, vec)
+        lay = pk[0] if pk is not None else None
+        shape = jit.scan_agg_shape(p, compacts, vec, None, lay)
+        k = jit.kernel_for(shape, lambda: jit.gen_scan_agg(p, compacts, vec, None, lay))
         key = (shape, kc.data.data_ptr(), kc.valid.data_ptr() if kc.valid is not None else 0,
                kc.hs_type, t.bucket_offsets.data_ptr(), nb, grid, GA)
         shmem = GA * 32 if p.group_col >= 0 else 0
@@ -888,7 +893,9 @@ class AggOps:
         values.update({"num_groups": p.num_groups, "group_base": p.group_base,
                        "nrows": t.num_rows})
         jit._fill_cols(values, p.cols, compacts)
-        return _GraphPrep(key, g, k, compacts, values, GA)
+        if pk is not None:
+            values.update(pk[2])
+        return _GraphPrep(key, g, k, compacts, values, GA, pk[1] if pk is not None else None)
 
     def _scan_side_stream(self, g):
         """The side stream warm scan pipelines replay on (None: replay on the current stream)."""

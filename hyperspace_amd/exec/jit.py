@@ -43,6 +43,7 @@ from . import kernel_config as _KC  # noqa: E402
 _CFG = _KC.active()
 SCAN_ITEMS, SCAN_GRID, SCAN_VEC = _CFG.scan_items, _CFG.scan_grid, _CFG.scan_vec
 SCAN_COMPACT, SCAN_EAGER = _CFG.scan_compact, _CFG.scan_eager
+SCAN_PACK, SCAN_PACK_LDS = _CFG.scan_pack, _CFG.scan_pack_lds
 JOIN_ITEMS, JOIN_BLOCK, JOIN_LDS_KEYS, JOIN_GRID = (_CFG.join_items, _CFG.join_block,
                                                     _CFG.join_lds_keys, _CFG.join_grid)
 JOIN_EAGER, JOIN_STAGE_RIGHT, JOIN_PIPELINE = (_CFG.join_eager, _CFG.join_stage_right,
@@ -848,7 +849,244 @@ def _col_specs(p, compacts) -> Dict[int, tuple]:
     return out
 
 
-def scan_agg_shape(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None) -> tuple:
+# Row-packed scan input (SCAN_PACK).  A scan whose columns are all plain compact codes reads, in
+# its full tiles, one bit-packed row stream instead of the code columns: a row is the columns'
+# fields back to back in slot order, a field is code - (lo - base) in bit_length(hi - lo) bits,
+# and the row's B bits (the sum rounded up to a multiple of 4) put 8 rows into exactly B / 4
+# dwords - the 8 rows a thread of the vectorized scan owns.  The copy is derived once per
+# resident table (ops.kernels.pack_rows), like the compact codes themselves.
+PACK_MAX_BITS = 64
+PACK_MAX_COLS = 8
+
+
+class RowPack(tuple):
+    """Compile-time layout of a row-packed scan input: ``fields`` = ((slot, first bit, bits),
+    ...) in slot order and ``B`` bits per row.  Part of the kernel's shape key; the per-column
+    offsets ``lo - base`` are kernel arguments (``PO<slot>``)."""
+    __slots__ = ()
+
+    def __new__(cls, fields, B: int):
+        return tuple.__new__(cls, (tuple(fields), int(B)))
+
+    fields = property(lambda self: self[0])
+    B = property(lambda self: self[1])
+
+    @property
+    def words(self) -> int:
+        """Dwords per 8 rows."""
+        return self.B // 4
+
+    def field(self, slot: int) -> Tuple[int, int]:
+        for s, pos, bits in self.fields:
+            if s == slot:
+                return pos, bits
+        raise KeyError(slot)
+
+
+def pack_field_bits(lo: int, hi: int) -> int:
+    """Bits of a field holding ``code - (lo - base)`` for values in [lo, hi]."""
+    return max(1, (int(hi) - int(lo)).bit_length())
+
+
+def pack_offset(c) -> int:
+    """The smallest code of compact column ``c``: what its field subtracts."""
+    return int(c.lo) - int(c.base)
+
+
+def row_pack_layout(slots, compacts, valid=()) -> Optional[RowPack]:
+    """The row-packed layout of column ``slots`` (``compacts``: slot -> encoding, ``valid``:
+    slots with a validity mask), or None: every column must be a plain ``Compact`` code of
+    width 1, 2 or 4 with known ``lo`` / ``hi``, no validity mask and no run form, the row must
+    fit 64 bits, and the packed row must be smaller than the columns' code bytes."""
+    slots = sorted(set(slots))
+    if not slots or len(slots) > PACK_MAX_COLS or any(s in set(valid) for s in slots):
+        return None
+    fields, pos, unpacked = [], 0, 0
+    for s in slots:
+        c = (compacts or {}).get(s)
+        if c is None or type(c).__name__ != "Compact" or c.width not in (1, 2, 4) or \
+                getattr(c, "runs", None) or c.lo is None or c.hi is None or \
+                int(c.hi) < int(c.lo):
+            return None
+        bits = pack_field_bits(c.lo, c.hi)
+        if bits > 32:
+            return None
+        fields.append((s, pos, bits))
+        pos += bits
+        unpacked += c.width
+    B = (pos + 3) // 4 * 4
+    if B > PACK_MAX_BITS or B >= 8 * unpacked:
+        return None
+    return RowPack(fields, B)
+
+
+def scan_pack_layout(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None) -> Optional[RowPack]:
+    """``row_pack_layout`` of the columns scan ``p`` touches, for the shapes the packed form
+    covers: the ungrouped vectorized scan with 8 rows per thread (register accumulators; the
+    aggregate inputs through the LDS lists or already among the predicate columns)."""
+    if not SCAN_PACK or vec != 8 or hk is not None or p.group_col >= 0:
+        return None
+    preds = [(k, p.preds[k]) for k in range(p.npreds)]
+    pslots = _pred_slots(preds)
+    aslots = [s for s in _agg_slots([p.aggs[i] for i in range(p.naggs)]) if s not in pslots]
+    if aslots and not (SCAN_COMPACT or SCAN_EAGER):
+        return None
+    slots = pslots + aslots
+    return row_pack_layout(slots, compacts, [s for s in slots if p.cols[s].valid])
+
+
+# row-packed copies, per identity of their code tensors (like jit_runs._P12)
+_ROWPACKS: dict = {}
+PACK_HBM_MARGIN = 8 << 30
+
+
+def row_pack(lay: RowPack, compacts):
+    """The row-packed copy of ``lay``'s columns (int32 device tensor), cached per identity of
+    the code tensors; None when free HBM is short (the scan then reads its columns)."""
+    import torch
+    from ..ops import kernels as K
+    from .device_cache import track_derived
+    cs = [compacts[s] for s, _, _ in lay.fields]
+    key = (lay,) + tuple(id(c.codes) for c in cs)
+    hit = _ROWPACKS.get(key)
+    if hit is not None and all(a is c.codes for a, c in zip(hit[0], cs)):
+        return hit[1]
+    dev = cs[0].codes.device
+    n = int(cs[0].codes.numel())
+    need = (n + 2047) // 2048 * 2048 // 8 * lay.B
+    free, _ = torch.cuda.mem_get_info(dev)
+    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    if free < need + PACK_HBM_MARGIN:
+        return None
+    try:
+        w = K.pack_rows([c.codes for c in cs], [pack_offset(c) for c in cs],
+                        [pos for _, pos, _ in lay.fields], [b for _, _, b in lay.fields], lay.B)
+    except torch.OutOfMemoryError:
+        return None     # an optional copy
+    track_derived(w)
+    if len(_ROWPACKS) >= 8:
+        _ROWPACKS.pop(next(iter(_ROWPACKS)))
+    _ROWPACKS[key] = ([c.codes for c in cs], w)
+    return w
+
+
+def scan_pack(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None):
+    """(layout, packed copy, its kernel argument values) of scan ``p``, or None when the scan
+    keeps the unpacked kernel (no layout, or no room for the copy)."""
+    lay = scan_pack_layout(p, compacts, vec, hk)
+    if lay is None:
+        return None
+    w = row_pack(lay, compacts)
+    if w is None:
+        return None
+    v = {"PK": w.data_ptr()}
+    for s, _, _ in lay.fields:
+        v[f"PO{s}"] = pack_offset(compacts[s])
+    return lay, w, v
+
+
+_PACK_PRELUDE = r"""
+// NW dwords of the row-packed stream at a dword-aligned address
+template <int NW>
+__device__ __forceinline__ void pload(const unsigned* __restrict__ p, long long i, unsigned (&x)[NW]) {
+  __builtin_memcpy(x, p + i, NW * sizeof(unsigned));
+}
+// the same dwords read lane-coalesced: ``i`` is the first dword of the wavefront's 64 row groups,
+// instruction k covers the 256 contiguous bytes at dword 64 k; hs_pk_t then moves every dword to
+// the lane that owns its row group through the wavefront's LDS slab (a lane's NW dwords lie NW
+// apart: an odd NW spreads them over all banks)
+template <int NW>
+__device__ __forceinline__ void ploadc(const unsigned* __restrict__ p, long long i, int ln,
+                                       unsigned (&x)[NW]) {
+#pragma unroll
+  for (int k = 0; k < NW; ++k) x[k] = p[i + 64 * k + ln];
+}
+template <int NW>
+__device__ __forceinline__ void hs_pk_t(unsigned* slab, int ln, unsigned (&x)[NW]) {
+#pragma unroll
+  for (int k = 0; k < NW; ++k) slab[64 * k + ln] = x[k];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+  for (int j = 0; j < NW; ++j) x[j] = slab[ln * NW + j];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+"""
+
+
+def _pack_extract(lay: RowPack, slot: int, it: int, arr: str) -> str:
+    """Field of ``slot`` of the thread's row ``it`` from its dword array ``arr``: constant
+    shifts and masks."""
+    pos, bits = lay.field(slot)
+    o = it * lay.B + pos
+    k, sh = o >> 5, o & 31
+    mask = "" if bits == 32 else f" & {hex((1 << bits) - 1)}u"
+    if sh + bits <= 32:
+        word = f"({arr}[{k}] >> {sh})" if sh else f"{arr}[{k}]"
+        return word if sh + bits == 32 else f"({word}{mask})"   # (the shift clears the rest)
+    return f"((unsigned)((((u64){arr}[{k + 1}] << 32) | {arr}[{k}]) >> {sh}){mask})"
+
+
+def _pack_decode(b: List[str], gen: "_Gen", lay: RowPack, slot: int, it, field: str,
+                 ind: str) -> None:
+    """The registers ``_uload`` / ``_vec_load_slots`` make for column ``slot`` / item ``it``
+    from its packed ``field`` expression: adding the offset back gives the stored code."""
+    ct = _CTYPE[gen.cols[slot][0]]
+    off = gen.a.add("q", f"PO{slot}", "long long")
+    b.append(f"{ind}const int r{slot}_{it} = (int)({field} + (unsigned){off});")
+    if gen.cols[slot][2][1]:
+        base = gen.a.add("q", f"B{slot}", "long long")
+        b.append(f"{ind}const i64 q{slot}_{it} = {base} + (i64)r{slot}_{it};")
+    b.append(f"{ind}const {ct} x{slot}_{it} = {gen.decode(slot, f'r{slot}_{it}')};")
+
+
+def _packed_tail(args, cols, approx, aggs, allslots, lay: RowPack, NI: int, ind: str) -> List[str]:
+    """``_compacted_tail`` of a row-packed full tile: the per-wavefront list (same ballot
+    positions) holds each passing row's aggregate-input fields instead of its row offset, so the
+    walk decodes them from LDS - the same values in the same lanes and order, and no gather."""
+    tail = list(dict.fromkeys(_agg_slots(aggs)))
+    epos, o = {}, 0
+    for s in tail:
+        epos[s] = o
+        o += lay.field(s)[1]
+    b = [f"{ind}int wtot = 0;"]
+    for it in range(NI):
+        ent = " | ".join(f"((crow_t)f{s}_{it} << {epos[s]})" if epos[s] else f"(crow_t)f{s}_{it}"
+                         for s in tail) or "(crow_t)0"
+        b += [f"{ind}{{ const bool pz = pass{it}; const u64 bm = __ballot(pz);",
+              f"{ind}  const int pos{it} = wtot + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), "
+              f"__builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));",
+              f"{ind}  if (pz) {{ crow_s[wv][pos{it}] = {ent}; }}",
+              f"{ind}  wtot += __popcll(bm); }}"]
+    b += [f"{ind}{_wave_sync()}",
+          f"{ind}for (int cb = 0; cb < wtot; cb += 64) {{",
+          f"{ind}  const int ce = cb + cln;",
+          f"{ind}  bool cok = ce < wtot;",
+          f"{ind}  const crow_t cent = cok ? crow_s[wv][ce] : (crow_t)0;"]
+    ind2 = ind + "  "
+    g = _Gen(args, cols, NL.MAX_COLS, ("crow", "crow"), approx, True)
+    for s in tail:
+        bits = lay.field(s)[1]
+        sh = f"(cent >> {epos[s]})" if epos[s] else "cent"
+        mask = "" if bits == 32 else f" & {hex((1 << bits) - 1)}u"
+        _pack_decode(b, g, lay, s, "c", f"((unsigned){sh}{mask})", ind2)
+    b += [_rename(x, allslots, "c") for x in _accumulate(g, aggs, False, "cok", "gic", ind2)]
+    b += [f"{ind}}}", f"{ind}{_wave_sync()}"]
+    return b
+
+
+def _pack_list_t(lay: RowPack, aggs) -> str:
+    """Entry type of a packed kernel's lists: the aggregate inputs' fields side by side (the
+    partial tile's row offsets fit either)."""
+    n = sum(lay.field(s)[1] for s in dict.fromkeys(_agg_slots(aggs)))
+    return "unsigned int" if n <= 32 else "u64"
+
+
+def scan_agg_shape(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None,
+                   pack: Optional[RowPack] = None) -> tuple:
+    if pack is not None:
+        return scan_agg_shape(p, compacts, vec, hk) + (("pack", SCAN_PACK_LDS) + tuple(pack),)
     cols = tuple(sorted(_col_specs(p, compacts).items()))
     preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
                    p.preds[k].group) for k in range(p.npreds))
@@ -858,13 +1096,19 @@ def scan_agg_shape(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None) -> tu
             SCAN_COMPACT, WAVE_SYNC, VEC_PREFETCH, hk.shape() if hk is not None else None)
 
 
-def gen_scan_agg(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None) -> Kernel:
+def gen_scan_agg(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None,
+                 pack: Optional[RowPack] = None) -> Kernel:
     """Filter + aggregate over row ranges, phase-major over the SCAN_ITEMS rows of each thread
     and branch-free: (1) the predicate columns of every item are loaded together; (2) the
     aggregate inputs (and group column) of every item, where rows that failed the predicates
     read the tile's first row instead of branching around the load — their lanes coalesce into
     one line, so only passing rows cost HBM bytes; (3) accumulate.  SCAN_EAGER loads every
-    column in phase 1."""
+    column in phase 1.
+
+    ``pack`` (``scan_pack_layout``): the full tiles read the thread's 8 rows as ``pack.words``
+    dwords of the row-packed copy (argument ``PK``) and list a passing row's aggregate-input
+    fields instead of its offset; the last, partial tiles keep the element loads of the
+    columns.  Same partials bit for bit."""
     args = Args()
     for n, ct in (("rstart", "const long long*"), ("rlen", "const long long*"),
                   ("tile_prefix", "const long long*")):
@@ -902,7 +1146,17 @@ def gen_scan_agg(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None) -> Kern
 
     def body(b: List[str], full: Optional[bool]) -> None:
         """Tile body; ``full`` = vectorized full tile / vectorized last tile / None (scalar)."""
-        if full is not None:     # raw vector arrays come from the tile loop (_vec_tiles)
+        if full and pack is not None:     # fields of the packed dwords the tile loop loaded
+            tail = _agg_slots(aggs) if compact else []
+            if SCAN_PACK_LDS:
+                b.append(f"{ind}hs_pk_t<{pack.words}>(pks_s[wv], cln, pkv);")
+            for it in range(NI):
+                for s in dict.fromkeys(pslots + tail):
+                    b.append(f"{ind}const unsigned f{s}_{it} = "
+                             f"{_pack_extract(pack, s, it, 'pkv')};")
+                for s in pslots:
+                    _pack_decode(b, g0_, pack, s, it, f"f{s}_{it}", ind)
+        elif full is not None:     # raw vector arrays come from the tile loop (_vec_tiles)
             _vec_load_slots(b, g0_, pslots, NI, ind)
         else:
             b.extend(["    const i64 tb0 = a.rstart[r] + off;",
@@ -917,6 +1171,9 @@ def gen_scan_agg(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None) -> Kern
         for it in range(NI):
             g1 = _Gen(args, cols, NL.MAX_COLS, (f"row{it}", f"row{it}"), approx, True)
             b.append(f"{ind}bool pass{it} = act{it} && {_rename(g1.cnf(preds), allslots, it)};")
+        if compact and full and pack is not None:
+            b.extend(_packed_tail(args, cols, approx, aggs, allslots, pack, NI, ind))
+            return
         if compact:
             b.extend(_compacted_tail(args, cols, NL.MAX_COLS, approx, aggs, grouped, p.group_col,
                                      aslots, allslots, NI, ind, with_j=False, hk=hk))
@@ -944,7 +1201,13 @@ def gen_scan_agg(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None) -> Kern
             b.extend(_rename(x, allslots, it) for x in
                      _accumulate(g2, aggs, grouped, f"pass{it}", gvar, ind))
 
-    if vec:
+    if pack is not None:
+        assert vec == 8 and NI == 8 and not grouped and hk is None and (compact or not aslots)
+        pk = args.add("p", "PK", "const unsigned*")
+        _vec_tiles(b, T, NI, ind, _vec_loads(g0_, pslots), [], body,
+                   full_loads=[("pk", "unsigned", pk, pack.words) +
+                               (("cln",) if SCAN_PACK_LDS else ())])
+    elif vec:
         _vec_tiles(b, T, NI, ind, _vec_loads(g0_, pslots), [], body)
     else:
         _tile_loop(b, T, NI, 0)
@@ -954,9 +1217,14 @@ def gen_scan_agg(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None) -> Kern
         b += _flush(aggs, grouped)
     if compact:
         W = BLOCK // 64
-        b.insert(0, f"  typedef {_crow_t(T)} crow_t; __shared__ crow_t crow_s[{W}][{64 * NI}];")
+        lt = _pack_list_t(pack, aggs) if pack is not None else _crow_t(T)
+        b.insert(0, f"  typedef {lt} crow_t; __shared__ crow_t crow_s[{W}][{64 * NI}];")
         b.insert(1, "  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;")
-    src = (_PRELUDE + args.struct_src() +
+    if pack is not None and SCAN_PACK_LDS:
+        if not compact:
+            b.insert(0, "  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;")
+        b.insert(0, f"  __shared__ unsigned pks_s[{BLOCK // 64}][{64 * pack.words}];")
+    src = (_PRELUDE + (_PACK_PRELUDE if pack is not None else "") + args.struct_src() +
            f'extern "C" __global__ __launch_bounds__({BLOCK}) void hs_jit_scan_agg(Args a) {{\n' +
            "\n".join(b) + "\n}\n")
     lds = (len(aggs) * p.num_groups * 32) if grouped else 0
@@ -1501,7 +1769,7 @@ def _tile_loop(b: List[str], T: int, NI: int, vec: int, ind: str = "    ") -> No
 
 
 def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
-               tscalars=()) -> None:
+               tscalars=(), full_loads=None) -> None:
     """Tile loops of a vectorized streaming kernel (``body(b, mode)`` emits one tile's work;
     ``loads`` = (name, C type, pointer) vector arrays, ``scalars`` = (name, C type, expression
     over ``G0``) per-thread values loaded with them).
@@ -1516,13 +1784,18 @@ def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
     keeps the next tile's stream in flight across this tile's dependent round trips.  Full
     tiles precede partial ones in a block's run, so the pipelined loop runs first and the
     element-wise loop finishes the run.  ``tscalars`` = (name, C type, expression over ``{t}``)
-    per-tile values (span bounds, run windows) prefetched the same way."""
+    per-tile values (span bounds, run windows) prefetched the same way.
+
+    ``full_loads`` = what the full tiles load instead of ``loads`` (the partial tiles keep
+    those): (name, "unsigned", pointer, W) entries read the thread's W dwords of a row-packed
+    stream (W dwords per NI rows) into ``<name>v``."""
+    fl = loads if full_loads is None else full_loads
     if not VEC_PREFETCH:
         _tile_loop(b, T, NI, 1, ind)
         for name, ct, expr in tscalars:
             b.append(f"{ind}const {ct} {name} = {expr.format(t='t')};")
         b.append(f"{ind}if (tb0 + {T} <= a.nrows) {{")
-        _vec_issue(b, loads, NI, ind, True)
+        _vec_issue(b, fl, NI, ind, True)
         for name, ct, expr in scalars:
             b.append(f"{ind}const {ct} {name} = {expr.replace('G0', 'g0')};")
         body(b, True)
@@ -1545,15 +1818,15 @@ def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
         for name, ct, expr in tscalars:
             b.append(f"{i2}{name}P = {expr.format(t=texpr)};")
         b.append(f"{i2}if (fullP) {{")
-        for name, ct, ptr in loads:
-            b.append(f"{i2}  vload<{ct}, {NI}>({ptr}, g0P, {name}vP);")
+        for e in fl:
+            b.append(f"{i2}  {_vec_load_stmt(e, NI, 'g0P', 'vP')}")
         for name, ct, expr in scalars:
             b.append(f"{i2}  {name}P = {expr.replace('G0', 'g0P')};")
         b.append(f"{i2}}}")
 
     b.append("  i64 rsP = 0, reP = 0, tb0P = 0, g0P = 0; bool fullP = false;")
-    for name, ct, _ in loads:
-        b.append(f"  {ct} {name}vP[{NI}];")
+    for e in fl:
+        b.append(f"  {e[1]} {e[0]}vP[{_vec_load_len(e, NI)}];")
     for name, ct, _ in list(scalars) + list(tscalars):
         b.append(f"  {ct} {name}P = ({ct})0;")
     b.append("  i64 t = t0;")
@@ -1562,9 +1835,10 @@ def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
     b.append("  }")
     b += ["  for (; t < t1 && fullP; ++t) {",
           "    const i64 rs = rsP, re = reP, tb0 = tb0P, g0 = g0P;"]
-    for name, ct, _ in loads:
-        b.append(f"{ind}{ct} {name}v[{NI}]; " +
-                 " ".join(f"{name}v[{k}] = {name}vP[{k}];" for k in range(NI)))
+    for e in fl:
+        name, ct, n = e[0], e[1], _vec_load_len(e, NI)
+        b.append(f"{ind}{ct} {name}v[{n}]; " +
+                 " ".join(f"{name}v[{k}] = {name}vP[{k}];" for k in range(n)))
     for name, ct, _ in list(scalars) + list(tscalars):
         b.append(f"{ind}const {ct} {name} = {name}P;")
     b.append(f"{ind}if (t + 1 < t1) {{")
@@ -1585,13 +1859,30 @@ def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
     body(b, False)
 
 
+def _vec_load_len(e, NI: int) -> int:
+    """Elements of a tile load's register array (``_vec_tiles`` ``loads`` / ``full_loads``)."""
+    return e[3] if len(e) > 3 else NI
+
+
+def _vec_load_stmt(e, NI: int, g: str, suffix: str) -> str:
+    """The load of entry ``e`` for the NI rows at ``g`` into ``<name><suffix>``."""
+    name, ct, ptr = e[:3]
+    if len(e) > 4:      # lane-coalesced: from the first dword of the wavefront's row groups
+        return (f"ploadc<{e[3]}>({ptr}, (({g} >> {NI.bit_length() - 1}) - {e[4]}) * {e[3]}, "
+                f"{e[4]}, {name}{suffix});")
+    if len(e) > 3:
+        return f"pload<{e[3]}>({ptr}, ({g} >> {NI.bit_length() - 1}) * {e[3]}, {name}{suffix});"
+    return f"vload<{ct}, {NI}>({ptr}, {g}, {name}{suffix});"
+
+
 def _vec_issue(b: List[str], loads, NI: int, ind: str, full: bool) -> None:
     """Loads of the NI consecutive rows at ``g0`` into ``<name>v`` for every (name, C type,
     pointer) of ``loads``: aligned vector loads in full tiles, guarded element loads otherwise."""
-    for name, ct, ptr in loads:
-        b.append(f"{ind}{ct} {name}v[{NI}];")
+    for e in loads:
+        name, ct, ptr = e[:3]
+        b.append(f"{ind}{ct} {name}v[{_vec_load_len(e, NI)}];")
         if full:
-            b.append(f"{ind}vload<{ct}, {NI}>({ptr}, g0, {name}v);")
+            b.append(f"{ind}{_vec_load_stmt(e, NI, 'g0', 'v')}")
         else:
             b.append(f"{ind}" + " ".join(
                 f"{name}v[{k}] = act{k} ? {ptr}[g0 + {k}] : ({ct})0;" for k in range(NI)))
@@ -2133,10 +2424,11 @@ def scan_vec(p: NL.ScanParams, compacts=None, nrows: int = 0) -> int:
 
 
 def scan_agg(p: NL.ScanParams, rstart, rlen, tile_prefix=None, compacts=None, nrows: int = 0,
-             hk=None, htab=None):
+             hk=None, htab=None, parts_out: Optional[list] = None):
     """``tile_prefix`` must use this kernel's tile (BLOCK * SCAN_ITEMS); None computes it.
     ``compacts``: slot -> ``encoding.Compact`` read instead of the full-width column.
-    ``nrows``: rows of the scanned table (enables the vectorized kernel)."""
+    ``nrows``: rows of the scanned table (enables the vectorized kernel).
+    ``parts_out``: a list that receives the per-block partial arrays (psum, pcnt, pmin, pmax)."""
     from ..ops import kernels as K
     vec = scan_vec(p, compacts, nrows)
     if vec:
@@ -2145,7 +2437,10 @@ def scan_agg(p: NL.ScanParams, rstart, rlen, tile_prefix=None, compacts=None, nr
         tile_prefix = K.ranges_to_tiles(rlen, BLOCK * SCAN_ITEMS)
     grid = SCAN_GRID or NL.lib().hs_scan_grid()
     GA = p.naggs * (p.num_groups if p.group_col >= 0 else 1)
-    k = kernel_for(scan_agg_shape(p, compacts, vec, hk), lambda: gen_scan_agg(p, compacts, vec, hk))
+    pk = scan_pack(p, compacts, vec, hk)
+    lay = pk[0] if pk is not None else None
+    k = kernel_for(scan_agg_shape(p, compacts, vec, hk, lay),
+                   lambda: gen_scan_agg(p, compacts, vec, hk, lay))
     if hk is not None:
         v = scan_agg_values(p, rstart, rlen, tile_prefix, (_NULLT,) * 4, compacts)
         v["nrows"] = nrows
@@ -2156,7 +2451,11 @@ def scan_agg(p: NL.ScanParams, rstart, rlen, tile_prefix=None, compacts=None, nr
     parts = _partials(grid, GA, rstart.device)
     v = scan_agg_values(p, rstart, rlen, tile_prefix, parts, compacts)
     v["nrows"] = nrows
+    if pk is not None:
+        v.update(pk[2])
     k.launch(grid, v, NL.stream_ptr(), GA * 32 if p.group_col >= 0 else 0)
+    if parts_out is not None:
+        parts_out.extend(parts)
     return _final(parts, grid, GA, rstart.device)
 
 

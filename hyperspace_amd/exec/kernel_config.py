@@ -33,6 +33,14 @@ class KernelConfig:
     scan_vec: int = 8            # rows per thread of the vectorized scan (aligned vector loads)
     scan_compact: bool = True    # aggregate inputs loaded for passing rows only (LDS lists)
     scan_eager: bool = False     # alternative: every column in the first batch
+    scan_pack: bool = True       # full tiles of an ungrouped vectorized scan over plain compact
+    #                              codes read one bit-packed row stream (jit.scan_pack_layout,
+    #                              hs_pack_rows) instead of the code columns and a gather of the
+    #                              aggregate inputs: TPC-H Q6 4.5 instead of 6 B per row
+    #                              (profiles/scan_pack.txt)
+    scan_pack_lds: bool = False  # alternative: the packed dwords loaded lane-coalesced (256 B per
+    #                              instruction) and moved to their rows' lanes through LDS, else
+    #                              per-lane dwordx4s (profiles/scan_pack.txt)
     # --- generic join kernel (gen_join_agg); 512-row tiles on a 16384-block grid measured best
     # (profiles/microbench_join_r1*.jsonl) ------------------------------------------------------
     join_items: int = 2

@@ -143,6 +143,16 @@ class RangeValArgs(C.Structure):
                 ("bp", C.c_int64 * 6), ("nb", C.c_int32), ("pad", C.c_int32)]
 
 
+class PackCol(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("off", C.c_int64), ("width", C.c_int32),
+                ("pos", C.c_int32), ("bits", C.c_int32), ("vec", C.c_int32)]
+
+
+class PackArgs(C.Structure):
+    """``hs_pack_rows``'s column table (csrc/kernels/pack_rows.hip)."""
+    _fields_ = [("c", PackCol * 8), ("ncols", C.c_int32), ("pad", C.c_int32)]
+
+
 _lib = None
 
 
@@ -179,7 +189,8 @@ def lib():
                      ("hs_gather_params_size", GatherParams), ("hs_xch_params_size", XchParams),
                      ("hs_xch_copy_size", XchCopy), ("hs_merge_keys_size", MergeKeys),
                      ("hs_win_keys_size", WinKeys), ("hs_agg_fold_args_size", AggFoldArgs),
-                     ("hs_range_search_val_args_size", RangeValArgs)):
+                     ("hs_range_search_val_args_size", RangeValArgs),
+                     ("hs_pack_args_size", PackArgs)):
         f = getattr(L, name)
         f.restype = C.c_int
         if f() != C.sizeof(st):
@@ -244,6 +255,7 @@ def lib():
     _sig(L.hs_run_bitmap_tags, I, P, I64, I64, P, I64, P, P)
     _sig(L.hs_run_minmax16, I, P, P, P, I64, P, P, P)
     _sig(L.hs_group16_32, I, P, I64, I64, P, P, P)
+    _sig(L.hs_pack_rows, I, P, I64, I, P, I64, P)
     _sig(L.hs_key_bitmap, I, P, I64, I64, I64, P, P, P)
     _sig(L.hs_bitmap_popcount, I, P, I64, P, P)
     _sig(L.hs_dict_like, I, P, P, I64, P, P, I, P, P)

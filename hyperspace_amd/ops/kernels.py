@@ -920,6 +920,35 @@ def group16_32(x):
     return off, gbase
 
 
+PACK_TILE_ROWS = 2048
+
+
+def pack_rows(cols, offs, pos, bits, B: int):
+    """Row-packed copy of up to 8 code columns (``hs_pack_rows``): int32 tensor of
+    ``npad / 8 * (B / 4)`` dwords, row i's ``B`` bits at bit ``(i % 8) * B`` of the dword group
+    ``(i / 8) * (B / 4)``, column c's field ``(code - offs[c]) & (2^bits[c] - 1)`` at bit
+    ``pos[c]`` of the row.  ``npad`` is the row count rounded up to whole 2048-row tiles (at
+    least one); padding rows read as zero."""
+    torch = _torch()
+    assert 1 <= len(cols) <= 8 and len(cols) == len(offs) == len(pos) == len(bits)
+    n = int(cols[0].numel())
+    a = NL.PackArgs()
+    a.ncols = len(cols)
+    for i, c in enumerate(cols):
+        assert c.dtype in (torch.int8, torch.int16, torch.int32) and c.is_contiguous()
+        assert int(c.numel()) == n
+        w = c.element_size()
+        a.c[i].data = c.data_ptr() if n else None
+        a.c[i].off = int(offs[i])
+        a.c[i].width, a.c[i].pos, a.c[i].bits = w, int(pos[i]), int(bits[i])
+        a.c[i].vec = 1 if c.data_ptr() % (8 * w) == 0 else 0
+    npad = max(1, (n + PACK_TILE_ROWS - 1) // PACK_TILE_ROWS) * PACK_TILE_ROWS
+    out = torch.empty(npad // 8 * (B // 4), dtype=torch.int32, device=cols[0].device)
+    NL.check(NL.lib().hs_pack_rows(C.byref(a), n, int(B), NL.ptr(out), npad, NL.stream_ptr()),
+             "hs_pack_rows")
+    return out
+
+
 def sortable_image(value, hs_type: int) -> int:
     """Host mirror of hs_sortable for a literal."""
     import struct
