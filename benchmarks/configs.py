@@ -46,6 +46,10 @@ against the same query with Hyperspace disabled (the reference's correctness ora
 * ``data_skipping`` — a data-skipping index (MinMax + Bloom sketches) over 128 source files:
   device and host sketch build, a range filter and a point lookup with and without the index,
   and the host cost of probing the sketches (``--sf 10`` for the recorded run).
+* ``zorder`` — a Z-order covering index on ``lineitem (l_shipdate, l_suppkey)``
+  (``--zorder-sf``, default 10): device and host ``createIndex``, zone-map build and prune pass,
+  and 5 % range filters on either or both columns with the index, with pruning off, and with
+  Hyperspace disabled (one session each, alternating).
 """
 import argparse
 import datetime
@@ -1154,11 +1158,157 @@ def config_data_skipping(args):
     return out
 
 
+def config_zorder(args):
+    """A Z-order covering index on ``lineitem (l_shipdate, l_suppkey)`` including
+    ``l_extendedprice`` and ``l_discount``: ``createIndex`` on the device against the host
+    builder, the zone-map build and the ``hs_zone_prune`` pass alone, and - for a 5 % range on
+    ``l_suppkey`` alone, on ``l_shipdate`` alone and on both - the kept share of zones and the
+    query time with the index, with pruning switched off, and with Hyperspace disabled (the
+    source table resident in HBM: what runs without this index kind).  Each index variant
+    alternates with the disabled run, a new literal every run, medians; 40 consecutive queries
+    per variant besides; results cross-checked against the host executor."""
+    from hyperspace_amd import Hyperspace, ZOrderCoveringIndexConfig, col, count, sum_
+    from hyperspace_amd.ops import kernels as K
+    sf, runs = args.zorder_sf, max(5, args.ds_runs)
+    data, _ = _tpch(args, sf)
+    root = os.path.join(args.data_dir, f"cfg_zorder_sf{sf:g}")
+    shutil.rmtree(root, ignore_errors=True)
+    src = os.path.join(data, "lineitem")
+    cfg = lambda: ZOrderCoveringIndexConfig(                     # noqa: E731
+        "li_z", ["l_shipdate", "l_suppkey"], ["l_extendedprice", "l_discount"])
+    out = {"config": "zorder", "device": args.device, "sf": sf, "runs": runs}
+    # host builder: a CPU session over the same files
+    hsess = _session(os.path.join(root, "host"), "cpu", args.buckets)
+    t0 = time.perf_counter()
+    Hyperspace(hsess).createIndex(hsess.read.parquet(src), cfg())
+    out["create_index_host_s"] = round(time.perf_counter() - t0, 3)
+    rule = {"spark.hyperspace.index.zorder.filterRule.enabled": "true"}
+    if args.zorder_zone_rows:
+        rule["spark.hyperspace.mi.zorder.zoneRows"] = str(args.zorder_zone_rows)
+    s = _session(os.path.join(root, "dev"), args.device, args.buckets, **rule)
+    hs = Hyperspace(s)
+    li = s.read.parquet(src)
+    dt, _ = _build(hs, li, cfg(), args.device)
+    out["create_index_s"] = round(dt, 3)
+    nsupp = max(1, int(round(sf * 10_000)))
+    day0, days = datetime.date(1992, 1, 2), 2500
+
+    def window(i, span, width):
+        lo = (i * 7919) % max(1, span - width)
+        return lo, lo + width
+
+    def cond(which, i):
+        c = None
+        if which in ("suppkey", "both"):
+            lo, hi = window(i, nsupp, max(1, nsupp // 20))
+            c = (col("l_suppkey") >= lo + 1) & (col("l_suppkey") <= hi)
+        if which in ("shipdate", "both"):
+            lo, hi = window(i + 3, days, days // 20)
+            d = (col("l_shipdate") >= day0 + datetime.timedelta(days=lo)) & \
+                (col("l_shipdate") < day0 + datetime.timedelta(days=hi))
+            c = d if c is None else c & d
+        return c
+
+    def q(df, which, i):
+        return df.filter(cond(which, i)).agg(
+            sum_(col("l_extendedprice") * col("l_discount")).alias("rev"), count("*").alias("n"))
+    # one session per variant over the same files and index store, so the alternating runs
+    # flip no session state (enabling Hyperspace or changing the conf between two queries costs
+    # the next query its plan-cache entry or a heap settle): with the index, with the index
+    # but every zone scanned, and without Hyperspace
+    Hyperspace.enable(s)
+    s_np = _session(os.path.join(root, "dev"), args.device, args.buckets,
+                    **dict(rule, **{"spark.hyperspace.mi.zorder.prune": "false"}))
+    Hyperspace.enable(s_np)
+    s_off = _session(os.path.join(root, "dev"), args.device, args.buckets)
+    sessions = {"index": s, "noprune": s_np, "disabled": s_off}
+    frames = {k: x.read.parquet(src) for k, x in sessions.items()}
+    be = s.backend()
+
+    def timed(which, i, mode):
+        _sync(args.device)
+        t0 = time.perf_counter()
+        rows = _rows(q(frames[mode], which, i))
+        _sync(args.device)
+        return rows, (time.perf_counter() - t0) * 1e3
+    out["queries"] = {}
+    hli = hsess.read.parquet(src)
+    for which in ("suppkey", "shipdate", "both"):
+        ts = {"index": [], "noprune": [], "disabled": [], "disabled2": []}
+        shares, ok = [], True
+        for mode in sessions:                  # load tables, plan, compile kernels
+            timed(which, 1000, mode)
+            timed(which, 1001, mode)
+        # alternating pairs, one index variant against the disabled run at a time: the two index
+        # sessions run the SAME generated kernel over different tables, and two such sessions
+        # taking turns slow each other down on the device, which is not what is measured here
+        for mode, off in (("index", "disabled"), ("noprune", "disabled2")):
+            for i in range(runs):
+                if mode == "index" and args.device == "gpu":
+                    be.metrics.pop("scan_zones_kept", None)
+                a, t = timed(which, i, mode)
+                ts[mode].append(t)
+                if mode == "index" and be.metrics.get("scan_zones_kept") is not None:
+                    shares.append(int(be.metrics["scan_zones_kept"]) / be.metrics["scan_zones"])
+                r, t = timed(which, i, "disabled")
+                ts[off].append(t)
+                ok = ok and _close(a, r) and a[0][1] > 0
+        Hyperspace.disable(hsess)
+        ok = ok and _close(_rows(q(hli, which, 0)), timed(which, 0, "index")[0])
+        out["queries"][which] = {
+            "kept_share": round(_med(shares), 4) if shares else None,
+            "with_index_ms": round(_med(ts["index"]), 3),
+            "prune_off_ms": round(_med(ts["noprune"]), 3),
+            "disabled_ms": round(_med(ts["disabled"]), 3),
+            "disabled_beside_prune_off_ms": round(_med(ts["disabled2"]), 3),
+            "disabled_spread_ms": round(max(ts["disabled"] + ts["disabled2"]) -
+                                        min(ts["disabled"] + ts["disabled2"]), 3),
+            "plan_used_index": "Name: li_z" in q(frames["index"], which, 0)
+            .queryExecution.executed_plan.tree_string(),
+            "path": getattr(be, "last_path", None), "match": ok}
+    # the same three variants without alternation: 40 consecutive queries of one session each
+    # (l_suppkey range, a new literal every query)
+    cons = {}
+    for mode in sessions:
+        for i in range(2000, 2004):
+            timed("suppkey", i, mode)
+        _sync(args.device)
+        t0 = time.perf_counter()
+        for i in range(40):
+            q(frames[mode], "suppkey", 3000 + i).collect()
+        _sync(args.device)
+        cons[mode] = round((time.perf_counter() - t0) / 40 * 1e3, 3)
+    out["consecutive_ms"] = cons
+    if args.device == "gpu":
+        # the zone-map build and the prune pass alone, on the resident index table
+        from hyperspace_amd.exec.zorder import resident_zone_maps
+        table, names, zone, maps = resident_zone_maps(be)[0]
+        cols = [table.columns[c] for c in names]
+        lo = K.sortable_image(nsupp // 2, cols[1].hs_type)
+        hi = K.sortable_image(nsupp // 2 + nsupp // 20, cols[1].hs_type)
+        tm, tp = [], []
+        for _ in range(runs):
+            _sync("gpu")
+            t0 = time.perf_counter()
+            K.zone_minmax(cols, zone)
+            _sync("gpu")
+            tm.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            K.zone_prune(maps, table.num_rows, zone, [(1, lo, hi)])
+            _sync("gpu")
+            tp.append((time.perf_counter() - t0) * 1e3)
+        out.update({"rows": table.num_rows, "zones": int(maps[0].shape[1]), "zone_rows": zone,
+                    "zone_map_build_ms": round(_med(tm), 3), "zone_prune_ms": round(_med(tp), 3)})
+    out["match"] = all(r["match"] for r in out["queries"].values())
+    return out
+
+
 CONFIGS = {"csv10k": config_csv10k, "sf10_filter": config_sf10_filter, "hybrid": config_hybrid,
            "q3_3way": config_q3_3way, "tpcds_3way": config_tpcds_3way,
            "streamed": config_streamed, "like": config_like,
            "count_distinct": config_count_distinct, "window": config_window,
-           "broadcast_join": config_broadcast_join, "data_skipping": config_data_skipping}
+           "broadcast_join": config_broadcast_join, "data_skipping": config_data_skipping,
+           "zorder": config_zorder}
 
 
 def main():
@@ -1178,6 +1328,10 @@ def main():
                     help="broadcast_join: time the hash-join probe kernel alone, per rows per lane")
     ap.add_argument("--ds-runs", type=int, default=5,
                     help="data_skipping: runs per measurement (at least 5; medians reported)")
+    ap.add_argument("--zorder-sf", type=float, default=10.0,
+                    help="zorder: TPC-H scale factor of the lineitem table")
+    ap.add_argument("--zorder-zone-rows", type=int, default=0,
+                    help="zorder: spark.hyperspace.mi.zorder.zoneRows (0 = automatic)")
     ap.add_argument("--probe-rows", type=int, default=1 << 26,
                     help="broadcast_join --probe-sweep: stream rows")
     args = ap.parse_args()

@@ -9,12 +9,14 @@ from .exceptions import HyperspaceException, NoChangesException
 from .hyperspace import Hyperspace, get_context
 from .index.config import IndexConfig
 from .index.dataskipping import BloomFilterSketch, DataSkippingIndexConfig, MinMaxSketch
+from .index.zorder import ZOrderCoveringIndexConfig
 from .session import Session
 from .plan.column import (col, lit, sum_, count, countDistinct, count_distinct, min_, max_,
                           avg, row_number, rank, dense_rank, Window, WindowSpec)
 
 __all__ = ["Hyperspace", "IndexConfig", "DataSkippingIndexConfig", "MinMaxSketch",
-           "BloomFilterSketch", "Session", "HyperspaceException", "NoChangesException",
+           "BloomFilterSketch", "ZOrderCoveringIndexConfig", "Session",
+           "HyperspaceException", "NoChangesException",
            "col", "lit", "sum_", "count", "countDistinct", "count_distinct", "min_", "max_",
            "avg", "row_number", "rank", "dense_rank", "Window", "WindowSpec", "get_context"]
 

@@ -9,10 +9,12 @@ from ..exceptions import HyperspaceException
 from ..index import constants as C
 from ..index import signatures as S
 from ..index import dataskipping as DS
-from ..index.builder import build_from_source
+from ..index import zorder as ZO
+from ..index.builder import build_from_source, build_zorder_from_source
 from ..index.config import IndexConfig
 from ..index.log_entry import (Content, CoveringIndex, DataSkippingIndex, FileIdTracker,
-                               IndexLogEntry, LogicalPlanFingerprint, Signature, Source, SparkPlan)
+                               IndexLogEntry, LogicalPlanFingerprint, Signature, Source, SparkPlan,
+                               ZOrderCoveringIndex)
 from ..plan import logical as L
 from ..plan.types import schema_to_json
 from ..telemetry.events import CreateActionEvent
@@ -47,6 +49,12 @@ class CreateActionBase:
 
     def has_lineage(self) -> bool:
         return HyperspaceConf.index_lineage_enabled(self.session.conf)
+
+    def zorder_num_files(self, df) -> int:
+        """Key-range files of a Z-order index over ``df``: one per ``targetSourceBytesPerPartition``
+        of source data."""
+        size = sum(f.length for f in self._relation(df).relation.location.all_files())
+        return ZO.num_files(size, HyperspaceConf.zorder_target_source_bytes(self.session.conf))
 
     def _sketches(self, df, config) -> List[dict]:
         """``properties.sketches`` of a data-skipping config over ``df`` (columns resolved)."""
@@ -126,6 +134,15 @@ class CreateActionBase:
                 config.indexName, derived, Content.from_directory(abs_path, self.file_id_tracker),
                 Source(SparkPlan(relations, None, None,
                                  LogicalPlanFingerprint([Signature(provider.name, sig)]))), {})
+        if isinstance(config, ZO.ZOrderCoveringIndexConfig):
+            ZO.check_indexed_types(df.schema, idx)
+            derived = ZOrderCoveringIndex(
+                idx, inc, schema_to_json(self.index_schema(df, idx, inc, extra)),
+                self.zorder_num_files(df), props)
+            return IndexLogEntry(
+                config.indexName, derived, Content.from_directory(abs_path, self.file_id_tracker),
+                Source(SparkPlan(relations, None, None,
+                                 LogicalPlanFingerprint([Signature(provider.name, sig)]))), {})
         return IndexLogEntry(
             config.indexName,
             CoveringIndex(idx, inc, schema_to_json(self.index_schema(df, idx, inc, extra)),
@@ -162,6 +179,11 @@ class CreateActionBase:
         # make sure every file has an id before lineage is attached
         for f in lr.relation.location.all_files():
             self.file_id_tracker.add_file(f)
+        if isinstance(config, ZO.ZOrderCoveringIndexConfig):
+            ZO.check_indexed_types(df.schema, idx)
+            return build_zorder_from_source(self.session, lr.relation, files, idx + inc + extra,
+                                            idx, self.zorder_num_files(df),
+                                            self.index_data_path, self.lineage_ids(files), mode)
         return build_from_source(self.session, lr.relation, files, idx + inc + extra, idx,
                                  self.num_buckets_for_index(), self.index_data_path,
                                  self.lineage_ids(files), mode)

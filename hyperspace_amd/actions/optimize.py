@@ -59,7 +59,7 @@ class OptimizeAction(CreateActionBase, Action):
         return self._split
 
     def validate(self) -> None:
-        if self.previous_entry.is_data_skipping:
+        if self.previous_entry.is_data_skipping or self.previous_entry.is_zorder:
             raise HyperspaceException(
                 f"optimizeIndex is not supported by index kind "
                 f"{self.previous_entry.derived_dataset.kind}.")

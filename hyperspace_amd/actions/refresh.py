@@ -60,7 +60,7 @@ class RefreshActionBase(CreateActionBase, Action):
     @property
     def index_config(self) -> IndexConfig:
         p = self.previous_entry
-        if p.is_data_skipping:
+        if p.is_data_skipping or p.is_zorder:
             return p.config
         return IndexConfig(p.name, p.indexed_columns, p.included_columns)
 
@@ -129,6 +129,10 @@ class RefreshIncrementalAction(RefreshActionBase):
 
     def validate(self) -> None:
         super().validate()
+        if self.previous_entry.is_zorder:
+            raise HyperspaceException(
+                f"Incremental refresh is not supported by index kind "
+                f"{self.previous_entry.derived_dataset.kind}.")
         if not self.appended_files and not self.deleted_files:
             raise NoChangesException("Refresh incremental aborted as no source data change found.")
         if self.deleted_files and not self.has_lineage():
@@ -176,7 +180,7 @@ class RefreshQuickAction(RefreshActionBase):
 
     def validate(self) -> None:
         super().validate()
-        if self.previous_entry.is_data_skipping:
+        if self.previous_entry.is_data_skipping or self.previous_entry.is_zorder:
             raise HyperspaceException(
                 f"Quick refresh is not supported by index kind "
                 f"{self.previous_entry.derived_dataset.kind}.")

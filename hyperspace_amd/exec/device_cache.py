@@ -153,6 +153,11 @@ class DeviceTableCache:
     def resident_bytes(self) -> int:
         return self._bytes
 
+    def tables(self) -> list:
+        """The resident tables, least recently used first."""
+        with self._lock:
+            return list(self._lru.values())
+
     def clear(self):
         with self._lock:
             self.epoch += 1

@@ -56,6 +56,7 @@ from .gpu_hash import HashAggOps
 from .gpu_hash_join import HashJoinOps
 from .gpu_join import JoinOps
 from .gpu_semi import SemiJoinOps
+from .zorder import ZoneSpec, zone_ranges, zone_rows_of, zone_spec
 # re-exported for tests and diagnostics scripts
 from .gpu_common import _strip_exchange, bucket_chunks  # noqa: F401
 
@@ -745,6 +746,8 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
         d = self._dist()
         rank, world = (d.rank, d.world) if d is not None else (0, 1)
         names = [a.name for a in p.output]
+        if bucketed is None and rel.is_index() and rel.index.is_zorder:
+            return self._scan_zorder(p, files)
         if bucketed is None:
             bucketed = rel.is_index() and \
                 self._all_bucket_files(rel.location, files, rel.index.num_buckets)
@@ -797,6 +800,39 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
         table.global_key = gkey
         return DRel(table, {a.expr_id: a.name for a in p.output}, list(p.output),
                     split=world > 1)
+
+    def _scan_zorder(self, p: X.FileSourceScanExec, files) -> DRel:
+        """A Z-order index relation: its key-range files loaded back to back in file order
+        (the bucketed loader, no sort columns).  The rows are in Z-address order, which is no
+        key order: the relation carries no sort or bucket attributes and is not ``bucketed``,
+        so no range search, merge join or sort elision reads it as sorted.  ``zone_attrs``
+        names the indexed columns whose zone maps prune its scans (exec/zorder.py)."""
+        d = self._dist()
+        if d is not None and d.world > 1:
+            raise Unsupported("Z-order index scan under torch.distributed")
+        if getattr(self, "_bucket_chunk", None) is not None:
+            # bucket-range streaming cuts hash buckets; this table is only ever loaded whole
+            raise Unsupported("Z-order index scan inside a bucket-range pass")
+        idx = p.relation.index
+        ncol = {n.lower(): n for n in idx.schema.names}
+        cols = [ncol[a.name.lower()] for a in p.output]
+        zone_cols = [ncol[c.lower()] for c in idx.indexed_columns]
+        load_cols = list(dict.fromkeys(cols + zone_cols))
+        table = self.cache.get(
+            files, load_cols, ("zorder",),
+            lambda: load_bucketed_index(files, load_cols, idx.num_buckets, [], self.device))
+        table.global_key = ("zorder", _files_key(files), tuple(load_cols), 1)
+        colmap = {a.expr_id: c for a, c in zip(p.output, cols)}
+        zone_attrs = []
+        for c in zone_cols:
+            a = next((x for x in p.output if x.name.lower() == c.lower()), None)
+            if a is None:
+                a = E.Attribute(c, idx.schema.field(c).type)
+                colmap[a.expr_id] = c
+            zone_attrs.append(a)
+        r = DRel(table, colmap, list(p.output))
+        r.zone_attrs = zone_attrs
+        return r
 
     def _hybrid_split(self, p: X.FileSourceScanExec, files):
         """(bucket files, appended files, load columns, sort columns, output columns) of an
@@ -919,13 +955,20 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
         spec = self._range_spec(r, conds, implied)
         if spec is None:
             return self._full_ranges(r.table)
+        if isinstance(spec, ZoneSpec):
+            zone = zone_rows_of(self.session.conf, r.table.num_rows)
+            return zone_ranges(r.table, spec, zone, self.metrics)
         kc, lo, lo_incl, hi, hi_incl, buckets = spec
         return K.range_search(kc, r.table.bucket_offsets, buckets, lo, lo_incl, hi, hi_incl)
 
     def _range_spec(self, r: DRel, conds: list, implied: Optional[set] = None):
         """(key column, lo, lo_incl, hi, hi_incl, buckets) of the range search ``_ranges``
-        runs, or None when every row of every bucket is in range."""
+        runs, or None when every row of every bucket is in range.  A Z-order relation
+        (``zone_attrs``) gets a ``ZoneSpec`` instead, the input of the zone prune pass; it
+        implies nothing: every predicate stays a per-row predicate of the scan."""
         t = r.table
+        if not r.bucketed and r.zone_attrs and not r.parts and t is not None:
+            return zone_spec(r, conds, self.session.conf)
         if not (r.bucketed and r.sort_attrs):
             return None
         lead = r.sort_attrs[0]

@@ -17,6 +17,7 @@ from .arrow_eval import key
 from .device_table import DeviceColumn
 from .graphs import _cbuf, GraphPending as _GraphPending, range_bounds, ScanAggGraph
 from .pairing import HeldQuery
+from .zorder import ZoneSpec, zone_ranges, zone_rows_of
 from .gpu_common import (arrow_table, _compact_buffers, _eval_scalar, _GraphPrep, _group_limit,
                          _JoinPrep, _NeedHash, _ScanPrep, _Stale, _use_on, bucket_chunks, DRel,
                          GROUP_LDS_SCAN, log, MAX_GROUPS_SCAN, skipping_scan, Unsupported)
@@ -128,7 +129,9 @@ class AggOps:
         total = 0
         for sc in scans:
             rel = sc.relation
-            if not rel.is_index():
+            if not rel.is_index() or rel.index.is_zorder:
+                # a Z-order index's files are key-range files, not hash buckets: its scan
+                # (_scan_zorder) always loads all of them, so it is never cut into passes
                 return None
             files = rel.location.all_files()
             nb = rel.index.num_buckets
@@ -750,11 +753,17 @@ class AggOps:
         else:
             spec, bound, specs = low
         graph = graph_ok and self._graph_eligible(spec, descs)
-        self.metrics["scan_key_ranges"] = spec is not None   # leading-key range pruning
+        zoned = isinstance(spec, ZoneSpec)      # Z-order relation: zone pruning, no key order
+        self.metrics["scan_key_ranges"] = spec is not None and not zoned   # leading-key ranges
         if not graph:
             with stage("scan.ranges"):
-                rstart, rlen, _ = self._ranges(r, r.conds) if spec is not None else \
-                    self._full_ranges(r.table)
+                if zoned:
+                    # the spec of this literal vector (prep.lowered), not a second lowering
+                    zone = zone_rows_of(self.session.conf, r.table.num_rows)
+                    rstart, rlen, _ = zone_ranges(r.table, spec, zone, self.metrics)
+                else:
+                    rstart, rlen, _ = self._ranges(r, r.conds) if spec is not None else \
+                        self._full_ranges(r.table)
         if prep is None:
             gs = self._group_spec(r, group, _group_limit(MAX_GROUPS_SCAN, GROUP_LDS_SCAN,
                                                          len(fns)))
@@ -805,8 +814,8 @@ class AggOps:
         """Replay a captured hipGraph for this scan (exec/graphs.py): generated kernels and a
         range search over all of this rank's buckets (equality bucket pruning changes the
         launch shape)."""
-        if spec is None or spec[5] is not None:
-            return False
+        if spec is None or isinstance(spec, ZoneSpec) or spec[5] is not None:
+            return False        # (a zone-pruned scan is not captured)
         conf = self.session.conf
         return HyperspaceConf.codegen_enabled(conf) and HyperspaceConf.hipgraph_enabled(conf)
 

@@ -74,6 +74,10 @@ class DRel:
         self.split = split
         # computed projection columns of this query (exec/project.py), by colmap name
         self.extra: Dict[str, DeviceColumn] = {}
+        # Z-order index relation: its indexed attributes, whose per-zone min/max maps prune the
+        # scan's row ranges (exec/zorder.py).  Such a relation is in no key order: it carries
+        # no sort_attrs / bucket_attrs and is not ``bucketed``
+        self.zone_attrs: List[E.Attribute] = []
 
     def col(self, a: E.Attribute) -> DeviceColumn:
         if self.parts:
@@ -91,6 +95,7 @@ class DRel:
         d = DRel(self.table, dict(self.colmap), list(self.attrs), list(self.conds), self.bucketed,
                  self.sort_attrs, self.bucket_attrs, self.num_buckets, self.parts, self.split)
         d.extra = dict(self.extra)
+        d.zone_attrs = self.zone_attrs
         for k, v in kw.items():
             setattr(d, k, v)
         return d

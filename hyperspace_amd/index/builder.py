@@ -62,6 +62,33 @@ def build_from_source(session, rel, files: List[str], columns: List[str], indexe
                                 job_uuid=str(uuid.uuid4()))
 
 
+def build_zorder_from_source(session, rel, files: List[str], columns: List[str],
+                             indexed: List[str], nfiles: int, out_path: str,
+                             lineage_ids: Optional[Dict[str, int]],
+                             mode: str = "overwrite") -> List[str]:
+    """Z-order covering index data (``index/zorder.py``): rows ordered by the Z-address of
+    ``indexed``, cut into ``nfiles`` key-range files.  Single rank only: a multi-rank session
+    is refused rather than built by one rank while the others wait."""
+    from . import zorder as ZO
+    dist = getattr(session, "dist", None)
+    if dist is not None and dist.world > 1:
+        from ..exceptions import HyperspaceException
+        raise HyperspaceException(
+            "A Z-order index is built by a single rank; create it from a session without "
+            "torch.distributed.")
+    if session.device_kind() == "gpu":
+        from ..exec.zorder import device_build_fits, device_build_zorder
+        if not device_build_fits(session, rel, files, columns, lineage_ids):
+            # the device build is one pass: a source beyond the build's HBM budget is built
+            # by the host builder (same files, row for row)
+            t = read_index_input(rel, files, columns, lineage_ids)
+            return ZO.host_build(session, t, indexed, nfiles, out_path, mode)
+        return device_build_zorder(session, rel, files, columns, indexed, nfiles, out_path,
+                                   lineage_ids, mode)
+    t = read_index_input(rel, files, columns, lineage_ids)
+    return ZO.host_build(session, t, indexed, nfiles, out_path, mode)
+
+
 def _device_hashable(rel, indexed: List[str]) -> bool:
     """The device Murmur3 kernel hashes decimals from float64 storage, exact only up to
     precision 15 (``ops.kernels.hash_xform``); wider decimal keys use the host build."""

@@ -38,7 +38,7 @@ class IndexConfig:
         return self.includedColumns
 
     def __eq__(self, o):
-        return isinstance(o, IndexConfig) and self.indexName.lower() == o.indexName.lower() and \
+        return type(o) is type(self) and self.indexName.lower() == o.indexName.lower() and \
             self._lower_idx == o._lower_idx and set(self._lower_inc) == set(o._lower_inc)
 
     def __hash__(self):

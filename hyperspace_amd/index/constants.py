@@ -159,3 +159,18 @@ HBM_RESERVE_BYTES_DEFAULT = str(64 * 1024 ** 3)
 BUILD_HBM_BUDGET_BYTES = "spark.hyperspace.mi.build.hbmBudgetBytes"
 BUILD_HBM_BUDGET_BYTES_DEFAULT = "0"
 FAULT_INJECTION = "spark.hyperspace.mi.faultInjection"
+# Z-order covering index (index/zorder.py): source bytes per key-range file of the index
+ZORDER_TARGET_SOURCE_BYTES = "spark.hyperspace.index.zorder.targetSourceBytesPerPartition"
+ZORDER_TARGET_SOURCE_BYTES_DEFAULT = str(1024 ** 3)
+# FilterIndexRule may pick a Z-order index for a filter no covering index serves.  Off by
+# default: with the source table resident in HBM the unpruned scan measured faster than the
+# indexed query at SF10 / SF30 (profiles/zorder.txt)
+ZORDER_FILTER_RULE_ENABLED = "spark.hyperspace.index.zorder.filterRule.enabled"
+ZORDER_FILTER_RULE_ENABLED_DEFAULT = "false"
+# rows per zone of the resident table's min/max maps, a multiple of the scan tile
+# (0 = one scan tile, doubled until the table has at most 4096 zones, exec/zorder.py)
+ZORDER_ZONE_ROWS = "spark.hyperspace.mi.zorder.zoneRows"
+ZORDER_ZONE_ROWS_DEFAULT = "0"
+# prune zones on the device before a scan of a Z-order index (off: every zone is scanned)
+ZORDER_PRUNE = "spark.hyperspace.mi.zorder.prune"
+ZORDER_PRUNE_DEFAULT = "true"

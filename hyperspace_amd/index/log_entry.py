@@ -276,9 +276,41 @@ class DataSkippingIndex:
                                  o.get("kind", "DataSkippingIndex"), o.get("kindAbbr", "DS"))
 
 
+@dataclass
+class ZOrderCoveringIndex:
+    """Covering columns laid out in Z-order of ``indexed`` (``index/zorder.py``).
+    ``num_buckets``: the number of key-range files, written with the bucket-file naming."""
+    indexed: List[str]
+    included: List[str]
+    schema_string: str
+    num_buckets: int
+    properties: Dict[str, str] = field(default_factory=dict)
+    kind: str = "ZOrderCoveringIndex"
+    kind_abbr: str = "ZCI"
+
+    def to_json_obj(self):
+        return {"properties": {"columns": {"indexed": list(self.indexed),
+                                           "included": list(self.included)},
+                               "schemaString": self.schema_string,
+                               "numBuckets": self.num_buckets,
+                               "properties": dict(self.properties)},
+                "kind": self.kind, "kindAbbr": self.kind_abbr}
+
+    @staticmethod
+    def from_json_obj(o) -> "ZOrderCoveringIndex":
+        p = o["properties"]
+        return ZOrderCoveringIndex(list(p["columns"]["indexed"]), list(p["columns"]["included"]),
+                                   p["schemaString"], int(p["numBuckets"]),
+                                   dict(p.get("properties") or {}),
+                                   o.get("kind", "ZOrderCoveringIndex"), o.get("kindAbbr", "ZCI"))
+
+
 def derived_dataset_from_json_obj(o):
-    if o.get("kind", "CoveringIndex") == "DataSkippingIndex":
+    kind = o.get("kind", "CoveringIndex")
+    if kind == "DataSkippingIndex":
         return DataSkippingIndex.from_json_obj(o)
+    if kind == "ZOrderCoveringIndex":
+        return ZOrderCoveringIndex.from_json_obj(o)
     return CoveringIndex.from_json_obj(o)
 
 
@@ -540,6 +572,10 @@ class IndexLogEntry(LogEntry):
         if self.is_data_skipping:
             from .dataskipping import config_of
             return config_of(self.name, self.derived_dataset.sketches)
+        if self.is_zorder:
+            from .zorder import ZOrderCoveringIndexConfig
+            return ZOrderCoveringIndexConfig(self.name, self.indexed_columns,
+                                             self.included_columns)
         from .config import IndexConfig
         return IndexConfig(self.name, self.indexed_columns, self.included_columns)
 
@@ -550,6 +586,10 @@ class IndexLogEntry(LogEntry):
     @property
     def is_data_skipping(self) -> bool:
         return self.derived_dataset.kind == "DataSkippingIndex"
+
+    @property
+    def is_zorder(self) -> bool:
+        return self.derived_dataset.kind == "ZOrderCoveringIndex"
 
     @property
     def signature(self) -> Signature:

@@ -306,6 +306,11 @@ def lib():
     _sig(L.hs_sketch_minmax, I, P, P, I64, P, I64, P, P, P, P, P, P, P)
     _sig(L.hs_sketch_bloom, I, P, P, P, I64, P, I64, I, I, P, P, P)
     _sig(L.hs_sketch_hash_entries, I, P, P, I64, P, P)
+    _sig(L.hs_zorder_max_cols, I)
+    _sig(L.hs_zorder_keys, I, P, I, P, P, P, I64, P, P)
+    _sig(L.hs_zone_minmax, I, P, I, I64, I64, P, P, P, P)
+    _sig(L.hs_zone_prune_workspace, I64, I64)
+    _sig(L.hs_zone_prune, I, P, P, P, I, I64, I64, I64, P, P, P, I, P, P, P, P, P)
     _lib = L
     return L
 

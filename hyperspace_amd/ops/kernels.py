@@ -1268,3 +1268,123 @@ def sketch_bloom(col, file_rows: Sequence[int], num_words: int, k: int, entry_ha
         C.byref(desc), NL.ptr(entry_hashes), NL.ptr(slabs), ns, NL.ptr(off), nf, num_words, k,
         NL.ptr(partials), NL.ptr(out), NL.stream_ptr()), "hs_sketch_bloom")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Z-order covering indexes (csrc/kernels/zorder.hip)
+# ------------------------------------------------------------------------------------------------
+ZORDER_RANGE_ZONE_ROWS = 1 << 16
+_ZORDER_TYPES = (NL.I8, NL.I16, NL.I32, NL.I64, NL.F32, NL.F64)
+
+
+def _zorder_descs(cols):
+    L = NL.lib()
+    if not 1 <= len(cols) <= int(L.hs_zorder_max_cols()):
+        raise ValueError(f"zorder: {len(cols)} columns")
+    n = len(cols[0])
+    descs = (NL.ColDesc * len(cols))()
+    for i, c in enumerate(cols):
+        if c.hs_type not in _ZORDER_TYPES or c.dictionary is not None:
+            raise ValueError(f"zorder: unsupported storage type {c.data.dtype}")
+        if len(c) != n or (c.valid is not None and c.valid.numel() != n):
+            raise ValueError("zorder: columns differ in length")
+        descs[i] = c.desc()
+    return descs, n
+
+
+def _u64_bits_min(t):
+    """Unsigned minimum of int64 words holding uint64 bits, as a Python int."""
+    top = -(1 << 63)
+    return (int((t ^ top).min().item()) ^ top) & 0xFFFFFFFFFFFFFFFF
+
+
+def _u64_bits_max(t):
+    top = -(1 << 63)
+    return (int((t ^ top).max().item()) ^ top) & 0xFFFFFFFFFFFFFFFF
+
+
+def zone_minmax(cols, zone_rows: int):
+    """Zone maps of device columns: ``(mn, mx, cnt)`` int64 tensors of shape ``[K, NZ]``, zone z
+    = rows ``[z * zone_rows, min(n, (z + 1) * zone_rows))``.  mn / mx hold the uint64
+    ``hs_sortable`` images (nothing canonicalised); an all-null zone has mn = ~0 > mx = 0."""
+    torch = _torch()
+    zone_rows = int(zone_rows)
+    if zone_rows < 1:
+        raise ValueError("zone_minmax: zone_rows must be positive")
+    descs, n = _zorder_descs(cols)
+    k = len(cols)
+    nz = -(-n // zone_rows)
+    dev = cols[0].data.device
+    out = torch.empty((3, k, nz), dtype=torch.int64, device=dev)
+    if nz:
+        NL.check(NL.lib().hs_zone_minmax(descs, k, n, zone_rows, NL.ptr(out[0]), NL.ptr(out[1]),
+                                         NL.ptr(out[2]), NL.stream_ptr()), "hs_zone_minmax")
+    return out[0], out[1], out[2]
+
+
+def zorder_column_ranges(cols):
+    """Per column ``(min image, max image)`` over its non-null rows, or None without one - the
+    ``hs_sortable`` images the Z-address is defined on.  One small readback."""
+    if not len(cols[0]):
+        return [None] * len(cols)
+    mn, mx, cnt = zone_minmax(cols, ZORDER_RANGE_ZONE_ROWS)
+    out = []
+    for j in range(len(cols)):
+        if int(cnt[j].sum().item()) == 0:
+            out.append(None)
+        else:
+            out.append((_u64_bits_min(mn[j]), _u64_bits_max(mx[j])))
+    return out
+
+
+def zorder_keys(cols, mins, shifts, bits):
+    """int64 Z-address per row of device columns (``index/zorder.py``): column j contributes
+    ``bits[j]`` bits of ``(image - mins[j]) >> shifts[j]`` (0 for a null), interleaved from the
+    most significant bit."""
+    torch = _torch()
+    descs, n = _zorder_descs(cols)
+    k = len(cols)
+    if not (len(mins) == len(shifts) == len(bits) == k) or sum(bits) > 63:
+        raise ValueError("zorder_keys: bad key plan")
+    out = torch.empty(n, dtype=torch.int64, device=cols[0].data.device)
+    mn = (C.c_uint64 * k)(*[int(m) for m in mins])
+    sh = (C.c_int32 * k)(*[int(s) for s in shifts])
+    bt = (C.c_int32 * k)(*[int(b) for b in bits])
+    NL.check(NL.lib().hs_zorder_keys(descs, k, mn, sh, bt, n, NL.ptr(out), NL.stream_ptr()),
+             "hs_zorder_keys")
+    return out
+
+
+def zone_prune(maps, n: int, zone_rows: int, constraints):
+    """Row ranges of the zones that may hold a row inside every constraint.  ``maps``: ``(mn, mx,
+    cnt)`` of ``zone_minmax`` over ``n`` rows; ``constraints``: ``(map column, lo image, hi
+    image)`` triples, inclusive (``lo > hi``: nothing).  Returns ``(rstart, rlen, counts)``:
+    int64 tensors of NZ entries - adjacent kept zones coalesced, live ranges first in ascending
+    order, the rest zero-length, the last zone clipped to ``n`` - and the device pair {ranges,
+    kept zones}.  No host sync."""
+    torch = _torch()
+    mn, mx, cnt = maps
+    k, nz = int(mn.shape[0]), int(mn.shape[1])
+    n, zone_rows = int(n), int(zone_rows)
+    if zone_rows < 1 or nz != -(-n // zone_rows) or len(constraints) > k:
+        raise ValueError("zone_prune: zone maps do not match the table")
+    for t in (mn, mx, cnt):
+        if t.dtype != torch.int64 or not t.is_contiguous() or tuple(t.shape) != (k, nz):
+            raise ValueError("zone_prune: bad zone map")
+    nc = len(constraints)
+    col = (C.c_int32 * max(nc, 1))(*[int(c[0]) for c in constraints])
+    lo = (C.c_uint64 * max(nc, 1))(*[int(c[1]) for c in constraints])
+    hi = (C.c_uint64 * max(nc, 1))(*[int(c[2]) for c in constraints])
+    if any(not 0 <= int(c[0]) < k for c in constraints):
+        raise ValueError("zone_prune: constraint on an unknown map column")
+    dev = mn.device
+    L = NL.lib()
+    # one allocation per call (this runs once per query): counts, ranges, workspace
+    m = max(nz, 1)
+    nws = int(L.hs_zone_prune_workspace(nz))
+    buf = torch.empty(2 + 2 * m + nws, dtype=torch.int64, device=dev)
+    counts, rstart, rlen, ws = buf[:2], buf[2:2 + m], buf[2 + m:2 + 2 * m], buf[2 + 2 * m:]
+    NL.check(L.hs_zone_prune(NL.ptr(mn), NL.ptr(mx), NL.ptr(cnt), k, nz, n, zone_rows, col, lo,
+                             hi, nc, NL.ptr(ws), NL.ptr(rstart), NL.ptr(rlen), NL.ptr(counts),
+                             NL.stream_ptr()), "hs_zone_prune")
+    return rstart[:nz], rlen[:nz], counts

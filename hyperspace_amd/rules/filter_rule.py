@@ -3,6 +3,8 @@
 Replaces the relation under ``Project(Filter(Relation))`` / ``Filter(Relation)`` with a covering
 index whose first indexed column appears in the predicate and which covers every referenced
 column.  The index is read *without* its bucket spec to keep scan parallelism (``:59-65``).
+When no covering index qualifies, a Z-order covering index (``index/zorder.py``) whose indexed
+columns include ANY filtered column and which covers the plan is used instead.
 Any exception leaves the plan unchanged — an index must never break a query.
 """
 from __future__ import annotations
@@ -55,12 +57,58 @@ def find_covering_indexes(session, filt, out_cols, filt_cols) -> list:
     return RU.get_candidate_indexes(session, cands, rel)
 
 
+def zorder_index_covers_plan(session, out_cols, filt_cols, indexed, included) -> bool:
+    """A Z-order index serves a filter on ANY of its indexed columns."""
+    cs = session.case_sensitive
+    return any(resolve_one(c, filt_cols, cs) is not None for c in indexed) and \
+        resolve(out_cols + filt_cols, list(indexed) + list(included), cs) is not None
+
+
+def find_zorder_indexes(session, filt, out_cols, filt_cols) -> list:
+    """Z-order candidates: active, covering the plan, source signature matching exactly
+    (Hybrid Scan never applies to this kind).  None unless
+    ``spark.hyperspace.index.zorder.filterRule.enabled`` is set: the kind is opt-in."""
+    from ..hyperspace import get_context
+    from ..utils.conf import HyperspaceConf
+    if not HyperspaceConf.zorder_filter_rule_enabled(session.conf):
+        return []
+    rel = RU.get_logical_relation(filt)
+    if rel is None:
+        return []
+    all_idx = get_context(session).index_collection_manager.get_indexes([states.ACTIVE])
+    cands = [i for i in all_idx
+             if i.is_zorder and zorder_index_covers_plan(session, out_cols, filt_cols,
+                                                         i.indexed_columns, i.included_columns)]
+    return RU.get_signature_matched_indexes(session, cands, rel)
+
+
+def rank_zorder(session, filt_cols, candidates: list):
+    """Largest share of indexed columns named in the filter, then the smallest index."""
+    if not candidates:
+        return None
+    cs = session.case_sensitive
+
+    def key(i):
+        named = sum(resolve_one(c, filt_cols, cs) is not None for c in i.indexed_columns)
+        return (-named / len(i.indexed_columns), sum(f.size for f in i.content.file_infos),
+                i.name)
+    return min(candidates, key=key)
+
+
 def _window_keys(p):
     """The partition column names of a Window directly over a filter node, else None."""
     if isinstance(p, L.Window) and p.partition_by and \
             all(isinstance(e, E.Attribute) for e in p.partition_by):
         return [e.name for e in p.partition_by]
     return None
+
+
+def _log_usage(session, index, filt, transformed) -> None:
+    logger = get_event_logger(session.conf)
+    if not isinstance(logger, NoOpEventLogger):  # plan strings only when someone listens
+        logger.log_event(HyperspaceIndexUsageEvent(
+            AppInfo(session.user, session.app_id, session.app_name), [index],
+            filt.tree_string(), transformed.tree_string(), "Filter index rule applied."))
 
 
 def FilterIndexRule(session, plan):
@@ -77,7 +125,16 @@ def FilterIndexRule(session, plan):
             cands = find_covering_indexes(session, filt, out_cols, filt_cols)
             index = rank_filter(session, filt, cands)
             if index is None:
-                return None
+                # no covering index leads with a filtered column: a Z-order index serves a
+                # filter on any of its indexed columns
+                index = rank_zorder(session, filt_cols,
+                                    find_zorder_indexes(session, filt, out_cols, filt_cols))
+                if index is None or wkeys is not None:
+                    return None      # under a Window: the child is visited next, unbucketed
+                transformed = RU.transform_plan_to_use_index_only_scan(session, index, original,
+                                                                       False)
+                _log_usage(session, index, filt, transformed)
+                return _Done(transformed)
             if wkeys is not None:
                 cs = session.case_sensitive
                 fold = (lambda n: n) if cs else str.lower
@@ -85,11 +142,7 @@ def FilterIndexRule(session, plan):
                     return None      # the child is visited next and rewritten as usual
             transformed = RU.transform_plan_to_use_index(session, index, original,
                                                          wkeys is not None)
-            logger = get_event_logger(session.conf)
-            if not isinstance(logger, NoOpEventLogger):  # plan strings only when someone listens
-                logger.log_event(HyperspaceIndexUsageEvent(
-                    AppInfo(session.user, session.app_id, session.app_name), [index],
-                    filt.tree_string(), transformed.tree_string(), "Filter index rule applied."))
+            _log_usage(session, index, filt, transformed)
             if wkeys is not None:
                 return p.with_children((_Done(transformed),))
             return _Done(transformed)

@@ -31,6 +31,24 @@ def is_index_applied(rel: L.HadoopFsRelation) -> bool:
     return rel.options.get(k) == v
 
 
+def _signature_valid(session, entry, plan: L.LogicalRelation, sig_cache: dict) -> bool:
+    def compute():
+        sig = entry.signature
+        if sig.provider not in sig_cache:
+            sig_cache[sig.provider] = S.create(sig.provider).signature(plan, session)
+        s = sig_cache[sig.provider]
+        return s is not None and s == sig.value
+    return entry.with_cached_tag(plan, T.SIGNATURE_MATCHED, compute)
+
+
+def get_signature_matched_indexes(session, indexes: list, plan: L.LogicalRelation) -> list:
+    """Candidates by exact source signature only, whatever the Hybrid Scan setting (index kinds
+    Hybrid Scan never applies to)."""
+    sig_cache: dict = {}
+    return [i for i in indexes if i.created and not i.has_source_update and
+            _signature_valid(session, i, plan, sig_cache)]
+
+
 def get_candidate_indexes(session, indexes: list, plan: L.LogicalRelation) -> list:
     conf = session.conf
     hybrid = HyperspaceConf.hybrid_scan_enabled(conf)
@@ -38,13 +56,7 @@ def get_candidate_indexes(session, indexes: list, plan: L.LogicalRelation) -> li
     sig_cache = {}
 
     def signature_valid(entry) -> bool:
-        def compute():
-            sig = entry.signature
-            if sig.provider not in sig_cache:
-                sig_cache[sig.provider] = S.create(sig.provider).signature(plan, session)
-            s = sig_cache[sig.provider]
-            return s is not None and s == sig.value
-        return entry.with_cached_tag(plan, T.SIGNATURE_MATCHED, compute)
+        return _signature_valid(session, entry, plan, sig_cache)
 
     if not hybrid:
         return [i for i in indexes if i.created and signature_valid(i)]

@@ -197,3 +197,20 @@ class HyperspaceConf:
     @staticmethod
     def hbm_compression_enabled(conf) -> bool:
         return _b(conf.get(C.HBM_COMPRESSION_ENABLED, C.HBM_COMPRESSION_ENABLED_DEFAULT))
+
+    @staticmethod
+    def zorder_target_source_bytes(conf) -> int:
+        return int(conf.get(C.ZORDER_TARGET_SOURCE_BYTES, C.ZORDER_TARGET_SOURCE_BYTES_DEFAULT))
+
+    @staticmethod
+    def zorder_filter_rule_enabled(conf) -> bool:
+        return _b(conf.get(C.ZORDER_FILTER_RULE_ENABLED, C.ZORDER_FILTER_RULE_ENABLED_DEFAULT))
+
+    @staticmethod
+    def zorder_zone_rows(conf) -> int:
+        """Rows per zone; 0 stands for one scan tile (the executor resolves it)."""
+        return int(conf.get(C.ZORDER_ZONE_ROWS, C.ZORDER_ZONE_ROWS_DEFAULT))
+
+    @staticmethod
+    def zorder_prune_enabled(conf) -> bool:
+        return _b(conf.get(C.ZORDER_PRUNE, C.ZORDER_PRUNE_DEFAULT))
