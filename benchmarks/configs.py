@@ -50,6 +50,10 @@ against the same query with Hyperspace disabled (the reference's correctness ora
   (``--zorder-sf``, default 10): device and host ``createIndex``, zone-map build and prune pass,
   and 5 % range filters on either or both columns with the index, with pruning off, and with
   Hyperspace disabled (one session each, alternating).
+* ``case_when`` — conditional aggregates over the bench's lineitem / orders index pair
+  (``--case-sf``, default 10): a Q12-style grouped join, a Q14-style ratio and an ungrouped
+  Q6-style query, each as fused guards, as a hidden computed column, with the guard in WHERE
+  and on the host engine (alternating runs, medians).
 """
 import argparse
 import datetime
@@ -686,6 +690,102 @@ def config_like(args):
     return out
 
 
+def config_case_when(args):
+    """Conditional aggregates over the lineitem / orders index pair of the bench (TPC-H SF
+    ``--case-sf``): a Q12-style grouped join query, a Q14-style ratio over the join and an
+    ungrouped Q6-style single-table query.  Each is cross-checked against the host engine and
+    timed four ways: fused guards (``condAgg.fused`` on), the CASE as a hidden computed column
+    (off) - alternating pairs in one process, medians of ``--case-runs`` - the same query with
+    the guard moved into WHERE (it reads the same columns without the feature: a floor), and the
+    host engine."""
+    from hyperspace_amd import Hyperspace, IndexConfig
+    sf = args.case_sf
+    data, _ = _tpch(args, sf)
+    root = os.path.join(args.data_dir, f"cfg_case_when_sf{sf:g}")
+    shutil.rmtree(root, ignore_errors=True)
+    s = _session(root, args.device, args.buckets)
+    hs = Hyperspace(s)
+    li = s.read.parquet(os.path.join(data, "lineitem"))
+    od = s.read.parquet(os.path.join(data, "orders"))
+    for df, cfg in ((li, IndexConfig("li_shipdate", ["l_shipdate"],
+                                     ["l_discount", "l_quantity", "l_extendedprice"])),
+                    (li, IndexConfig("li_orderkey", ["l_orderkey"],
+                                     ["l_extendedprice", "l_discount", "l_shipdate",
+                                      "l_returnflag"])),
+                    (od, IndexConfig("ord_orderkey", ["o_orderkey"],
+                                     ["o_orderdate", "o_shippriority", "o_orderpriority"]))):
+        _build(hs, df, cfg, args.device)
+    Hyperspace.enable(s)
+    li.createOrReplaceTempView("lineitem")
+    od.createOrReplaceTempView("orders")
+    join = "FROM lineitem JOIN orders ON l_orderkey = o_orderkey"
+    rev = "l_extendedprice * (1 - l_discount)"
+    queries = {
+        # (the query, the same query with its guard as a WHERE conjunct)
+        "q12_grouped": (
+            f"SELECT l_returnflag, sum(CASE WHEN o_orderpriority IN ('1-URGENT', '2-HIGH') "
+            f"THEN 1 ELSE 0 END) high, count(*) n {join} "
+            f"WHERE l_shipdate >= DATE '1994-01-01' AND l_shipdate < DATE '1995-01-01' "
+            f"GROUP BY l_returnflag",
+            f"SELECT l_returnflag, count(*) high {join} "
+            f"WHERE l_shipdate >= DATE '1994-01-01' AND l_shipdate < DATE '1995-01-01' "
+            f"AND o_orderpriority IN ('1-URGENT', '2-HIGH') GROUP BY l_returnflag"),
+        "q14_ratio": (
+            f"SELECT 100.0 * sum(CASE WHEN o_orderdate < DATE '1995-09-16' THEN {rev} ELSE 0 END)"
+            f" / sum({rev}) early {join} "
+            f"WHERE l_shipdate >= DATE '1995-09-01' AND l_shipdate < DATE '1995-10-01'",
+            f"SELECT sum({rev}) early {join} "
+            f"WHERE l_shipdate >= DATE '1995-09-01' AND l_shipdate < DATE '1995-10-01' "
+            f"AND o_orderdate < DATE '1995-09-16'"),
+        "q6_ungrouped": (
+            "SELECT sum(CASE WHEN l_discount >= 0.05 AND l_discount <= 0.07 "
+            "THEN l_extendedprice * l_discount ELSE 0 END) revenue, "
+            "count(CASE WHEN l_quantity < 24 THEN 1 END) small, count(*) n FROM lineitem "
+            "WHERE l_shipdate >= DATE '1994-01-01' AND l_shipdate < DATE '1995-01-01'",
+            "SELECT sum(l_extendedprice * l_discount) revenue, count(*) n FROM lineitem "
+            "WHERE l_shipdate >= DATE '1994-01-01' AND l_shipdate < DATE '1995-01-01' "
+            "AND l_discount >= 0.05 AND l_discount <= 0.07"),
+    }
+    key = "spark.hyperspace.mi.condAgg.fused"
+    be = s.backend()
+    out = {"config": "case_when", "device": args.device, "sf": sf, "runs": args.case_runs,
+           "queries": {}}
+
+    def route(text, fused):
+        s.conf.set(key, "true" if fused else "false")
+        rows = _rows(s.sql(text))
+        return rows, getattr(be, "last_path", None), \
+            getattr(be, "metrics", {}).get("cond_agg"), getattr(be, "fallback_reason", None)
+    for name, (text, floor) in queries.items():
+        got, path, how, why = route(text, True)
+        got_c, path_c, how_c, why_c = route(text, False)
+        _rows(s.sql(floor))
+        tf, tc, tw = [], [], []
+        for _ in range(args.case_runs):            # alternating, one run each
+            s.conf.set(key, "true")
+            tf.append(_median_ms(lambda: s.sql(text).collect(), 1, args.device))
+            s.conf.set(key, "false")
+            tc.append(_median_ms(lambda: s.sql(text).collect(), 1, args.device))
+            tw.append(_median_ms(lambda: s.sql(floor).collect(), 1, args.device))
+        s.conf.set(key, "true")
+        s.conf.set("spark.hyperspace.mi.execution.device", "cpu")
+        ref = _rows(s.sql(text))
+        th = _median_ms(lambda: s.sql(text).collect(), 3, "cpu")
+        s.conf.set("spark.hyperspace.mi.execution.device", args.device)
+
+        def med(ts):
+            return sorted(ts)[len(ts) // 2]
+        out["queries"][name] = {
+            "fused_ms": med(tf), "column_ms": med(tc), "guard_in_where_ms": med(tw),
+            "host_ms": th, "fused_ms_min_max": [min(tf), max(tf)],
+            "column_ms_min_max": [min(tc), max(tc)],
+            "path": path, "cond_agg": how, "fallback_reason": why,
+            "column_path": path_c, "column_cond_agg": how_c, "column_fallback_reason": why_c,
+            "match": _close(got, ref), "column_match": _close(got_c, ref)}
+    out["match"] = all(q["match"] and q["column_match"] for q in out["queries"].values())
+    return out
+
+
 def config_count_distinct(args):
     """``count(DISTINCT x)`` under a range filter on the index key, three shapes: ungrouped, one
     dictionary group column (few groups) and one integer group column (rows / 10 groups).  Each
@@ -1305,7 +1405,7 @@ def config_zorder(args):
 
 CONFIGS = {"csv10k": config_csv10k, "sf10_filter": config_sf10_filter, "hybrid": config_hybrid,
            "q3_3way": config_q3_3way, "tpcds_3way": config_tpcds_3way,
-           "streamed": config_streamed, "like": config_like,
+           "streamed": config_streamed, "like": config_like, "case_when": config_case_when,
            "count_distinct": config_count_distinct, "window": config_window,
            "broadcast_join": config_broadcast_join, "data_skipping": config_data_skipping,
            "zorder": config_zorder}
@@ -1324,6 +1424,10 @@ def main():
                     help="streamed: the build and resident-table HBM budgets")
     ap.add_argument("--like-runs", type=int, default=11,
                     help="like: timed runs per dictionary size and route (medians reported)")
+    ap.add_argument("--case-sf", type=float, default=10.0,
+                    help="case_when: TPC-H scale factor")
+    ap.add_argument("--case-runs", type=int, default=7,
+                    help="case_when: alternating timed runs per route (medians reported)")
     ap.add_argument("--probe-sweep", action="store_true",
                     help="broadcast_join: time the hash-join probe kernel alone, per rows per lane")
     ap.add_argument("--ds-runs", type=int, default=5,

@@ -18,7 +18,7 @@ import pyarrow.parquet as pq
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from hyperspace_amd import Hyperspace, IndexConfig, Session, col, count, sum_  # noqa: E402
+from hyperspace_amd import Hyperspace, IndexConfig, Session, col, count, sum_, when  # noqa: E402
 
 
 def banner(msg):
@@ -74,7 +74,10 @@ def main():
     banner("3. an equi-join served by two co-bucketed indexes (no shuffle, no sort)")
     j = emp.join(dept, emp["deptId"] == dept["deptId"]) \
         .groupBy(dept["deptName"]).agg(sum_(col("salary")).alias("payroll"),
-                                        count("*").alias("headcount"))
+                                        count("*").alias("headcount"),
+                                        # a conditional aggregate: a guard inside the join kernel
+                                        sum_(when(col("salary") >= 5000, 1).otherwise(0))
+                                        .alias("wellPaid"))
     hs.explain(j, verbose=True)
     j.show()
     print("executed on:", s.backend().last_path)

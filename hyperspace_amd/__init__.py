@@ -12,12 +12,12 @@ from .index.dataskipping import BloomFilterSketch, DataSkippingIndexConfig, MinM
 from .index.zorder import ZOrderCoveringIndexConfig
 from .session import Session
 from .plan.column import (col, lit, sum_, count, countDistinct, count_distinct, min_, max_,
-                          avg, row_number, rank, dense_rank, Window, WindowSpec)
+                          avg, row_number, rank, dense_rank, when, Window, WindowSpec)
 
 __all__ = ["Hyperspace", "IndexConfig", "DataSkippingIndexConfig", "MinMaxSketch",
            "BloomFilterSketch", "ZOrderCoveringIndexConfig", "Session",
            "HyperspaceException", "NoChangesException",
            "col", "lit", "sum_", "count", "countDistinct", "count_distinct", "min_", "max_",
-           "avg", "row_number", "rank", "dense_rank", "Window", "WindowSpec", "get_context"]
+           "avg", "row_number", "rank", "dense_rank", "when", "Window", "WindowSpec", "get_context"]
 
 __version__ = "0.1.0"

@@ -131,6 +131,24 @@ def eval_expr(e: E.Expression, t: pa.Table):
             return v
         return pc.if_else(pc.is_nan(v), pa.scalar(float("nan"), v.type),
                           pc.add(v, pa.scalar(0.0, v.type)))
+    if isinstance(e, E.CaseWhen):
+        # the first branch whose condition is TRUE (not NULL) wins; no branch: ELSE, or NULL
+        rt = e.data_type
+
+        def value(x):
+            v = eval_expr(x, t)
+            if pa.types.is_dictionary(v.type):
+                v = pc.cast(v, v.type.value_type)
+            if pa.types.is_decimal(v.type) and pa.types.is_floating(rt):
+                v = pc.cast(v, pa.float64())
+            return v if v.type == rt else pc.cast(v, rt, safe=False)
+        out = value(e.else_value) if e.else_value is not None else pa.nulls(t.num_rows, rt)
+        for c, v in reversed(e.branches):
+            cond = eval_expr(c, t)
+            if pa.types.is_null(cond.type):
+                continue
+            out = pc.if_else(pc.fill_null(cond, False), value(v), out)
+        return out
     if isinstance(e, E.Cast):
         v = eval_expr(e.child, t)
         if _is_num(v.type) and _is_num(e.dtype):

@@ -223,6 +223,15 @@ class Bound:
         self.always_false = False
         self.lits: list = []
         self.rebindable = True
+        # guarded aggregates (``bind_guards``): the row filter is ``preds[:nfilter]`` (None: all
+        # of them); ``guards[i]`` is None or (first, count, never true) - the guard CNF of
+        # aggregate i is ``preds[first:first + count]``
+        self.nfilter: Optional[int] = None
+        self.guards: list = []
+
+    @property
+    def filter_preds(self) -> List[NL.Pred]:
+        return self.preds if self.nfilter is None else self.preds[:self.nfilter]
 
 
 def _dict_code_bound(info: ColumnInfo, op: int, v: str) -> Tuple[str, int, int]:
@@ -389,6 +398,7 @@ def rebind(b: Bound) -> Optional[Bound]:
     out.preds = [NL.Pred.from_buffer_copy(p) for p in b.preds]
     out.buffers = b.buffers
     out.lits = b.lits
+    out.nfilter, out.guards = b.nfilter, b.guards
     for i, lit, dtype, flt in b.lits:
         v = lit.value
         if v is None or isinstance(v, (str, bool)):
@@ -402,6 +412,134 @@ def rebind(b: Bound) -> Optional[Bound]:
                 return None
             p.ilit = int(v)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Guarded aggregates: agg(CASE WHEN p THEN v [ELSE c] END) inside the fused kernels
+# ------------------------------------------------------------------------------------------------
+# The aggregate keeps its AggSpec.  Its guard p is a CNF of further Pred entries behind the row
+# filter's (``Bound.nfilter``): they bind, rebind and take their literals like filter predicates,
+# but no row filter reads them.  ``AggSpec.pad`` says where they are: flag bits, the index of
+# the first guard predicate in bits 8..15 and their count in bits 16..23 (0 for an unguarded
+# aggregate, which is what the field always held).  A constant THEN value is ``alpha[0]`` of an
+# aggregate without terms; the ELSE constant is the last ``alpha`` slot, so a guarded value has
+# at most ``GUARD_MAX_TERMS`` terms.  The kernels accumulate ``g ? v : c`` where
+# ``pass && (g ? valid(v) : has_else)``.
+GUARD_GROUP = 1 << 20                 # Pred.group of guard i's clauses: from GUARD_GROUP * (i + 1)
+GUARD_MAX_TERMS = NL.MAX_TERMS - 1
+G_ON, G_ELSE, G_NEVER = 1, 2, 4
+
+
+def guard_fields(pad: int) -> Optional[Tuple[int, int, bool, bool]]:
+    """(first predicate, count, has ELSE, never true) of an ``AggSpec.pad``; None: no guard."""
+    if not pad & G_ON:
+        return None
+    return (pad >> 8) & 0xFF, (pad >> 16) & 0xFF, bool(pad & G_ELSE), bool(pad & G_NEVER)
+
+
+class Guard:
+    """The normal form of a conditional aggregate's input: ``cond``, the THEN ``value`` (a
+    numeric literal or an affine product of columns) and the ELSE literal (None: no ELSE, or
+    ELSE NULL)."""
+    __slots__ = ("cond", "value", "else_lit")
+
+    def __init__(self, cond, value, else_lit):
+        self.cond, self.value, self.else_lit = cond, value, else_lit
+
+
+def _is_number(e) -> bool:
+    return isinstance(e, E.Literal) and isinstance(e.value, (int, float)) and \
+        not isinstance(e.value, bool)
+
+
+def guard_of(fn: E.AggregateFunction) -> Optional[Guard]:
+    """The guard of ``fn`` when it is ``agg(CASE WHEN p THEN v [ELSE c] END)`` in the normal
+    form the fused kernels take: agg one of sum / count / min / max / avg, ``p`` a predicate
+    ``to_cnf`` lowers, ``v`` a numeric literal or ``affine_terms`` input of at most
+    ``GUARD_MAX_TERMS`` columns, ``c`` absent, NULL or a numeric literal.  None otherwise (the
+    CASE is then computed as a column first)."""
+    if type(fn) not in (E.Sum, E.Count, E.Min, E.Max, E.Avg) or fn.child is None:
+        return None
+    c = fn.child
+    while isinstance(c, E.Alias):
+        c = c.child
+    if not isinstance(c, E.CaseWhen) or len(c.branches) != 1:
+        return None
+    cond, v = c.branches[0]
+    el = c.else_value
+    if el is not None and not (_is_number(el) or (isinstance(el, E.Literal) and el.value is None)):
+        return None
+    if E.contains_case(cond) or E.contains_case(v):
+        return None
+    if isinstance(v, E.Literal):
+        if not _is_number(v):
+            return None
+    else:
+        t = v.data_type
+        if not (pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_decimal(t) or
+                (pa.types.is_date32(t) and isinstance(fn, (E.Min, E.Max, E.Count)))):
+            return None
+        if isinstance(fn, E.Count):
+            if not isinstance(v, E.Attribute):
+                return None
+        else:
+            try:
+                scale, terms = affine_terms(v)
+            except Unsupported:
+                return None
+            if not terms or len(terms) > GUARD_MAX_TERMS:
+                return None
+            if isinstance(fn, (E.Min, E.Max)) and scale < 0:
+                return None
+    try:
+        to_cnf([cond])
+    except Unsupported:
+        return None
+    return Guard(cond, v, el if el is not None and el.value is not None else None)
+
+
+def bind_guards(b: Bound, guards: List[Optional[Guard]], col_info, device) -> Bound:
+    """Append the guard predicates of ``guards`` (one entry per aggregate, None: unguarded) to
+    the bound row filter ``b``: ``b.nfilter`` keeps the filter's length, ``b.guards`` each
+    guard's place.  A guard that can never be true (a string that is not in the dictionary, a
+    comparison with NULL) does not empty the query, as a filter would: it is flagged."""
+    b.nfilter = len(b.preds)
+    b.guards = []
+    for i, g in enumerate(guards):
+        if g is None:
+            b.guards.append(None)
+            continue
+        gb = bind(to_cnf([g.cond]), col_info, device, GUARD_GROUP * (i + 1))
+        first = len(b.preds)
+        b.preds += gb.preds
+        b.buffers += gb.buffers
+        b.lits += [(first + k, lit, dt, flt) for k, lit, dt, flt in gb.lits]
+        b.rebindable = b.rebindable and gb.rebindable and not gb.always_false
+        b.guards.append((first, len(gb.preds), gb.always_false))
+    if len(b.preds) > NL.MAX_PREDS:
+        raise Unsupported("too many predicates")
+    return b
+
+
+def guarded_agg_spec(fn: E.AggregateFunction, g: Guard, slot_of, where, base: int = 0) -> NL.AggSpec:
+    """The AggSpec of ``fn`` over ``g.value`` with its guard's place ``where`` (an entry of
+    ``Bound.guards``; ``base``: index of the bound list's first predicate in the kernel's)."""
+    first, count, never = where
+    v = g.value
+    if isinstance(v, E.Literal):
+        a = NL.AggSpec()
+        a.kind = {E.Sum: NL.AK_SUM, E.Count: NL.AK_COUNT, E.Min: NL.AK_MIN, E.Max: NL.AK_MAX,
+                  E.Avg: NL.AK_SUM}[type(fn)]
+        a.nterms = 0
+        a.alpha[0] = float(v.value)
+    else:
+        a = agg_spec(type(fn)(v), slot_of)
+    flags = G_ON | (G_NEVER if never else 0)
+    if g.else_lit is not None:
+        flags |= G_ELSE
+        a.alpha[NL.MAX_TERMS - 1] = float(g.else_lit.value)
+    a.pad = flags | ((base + first) << 8) | (count << 16)
+    return a
 
 
 # ------------------------------------------------------------------------------------------------
@@ -509,4 +647,5 @@ def _int_coded(t: pa.DataType) -> bool:
 
 
 __all__ = ["Unsupported", "to_cnf", "bind", "ColumnInfo", "agg_spec", "finalize_value",
-           "affine_terms", "np"]
+           "affine_terms", "np", "Guard", "guard_of", "bind_guards", "guarded_agg_spec",
+           "guard_fields"]

@@ -271,6 +271,7 @@ class GpuBackend(AggOps, JoinOps, SemiJoinOps, HashAggOps, HashJoinOps):
 
     def _fallback(self, plan, e, t0) -> "QueryFuture":
         log.info("device executor fallback: %s", e)
+        self.metrics.pop("cond_agg", None)      # (no device route of a conditional aggregate ran)
         out = self.cpu.collect(plan)
         return QueryFuture(self, plan, lambda: out, "fallback", str(e), t0)
 

@@ -51,6 +51,43 @@ class AggOps:
         aggregates (``_distinct_agg``)."""
         if any(not isinstance(g, E.Attribute) for g in final.grouping):
             final, child = self._named_groups(final, child)
+        cases = [fn for _, fn in X.agg_functions(final.aggregates)
+                 if fn.child is not None and E.contains_case(fn.child)]
+        if not cases:
+            self.metrics.pop("cond_agg", None)
+            return self._exec_agg_plain(final, child, order, limit)
+        # conditional aggregates: those in the guard normal form stay in the fused kernels
+        # (``_guards``); the others - all of them with condAgg.fused off, or when a kernel
+        # family on the query's path takes no guard - read their CASE as a hidden computed
+        # column of a projection below the aggregate, like a named grouping expression
+        fused = HyperspaceConf.cond_agg_fused(self.session.conf) and final.mode != "complete"
+        guards = self._guards(cases) if fused else None
+        if guards is not None and all(g is not None for g in guards):
+            try:
+                fin = self._exec_agg_plain(final, child, order, limit)
+                self.metrics["cond_agg"] = "fused"
+                return fin
+            except Unsupported as e:
+                log.debug("conditional aggregate as a computed column: %s", e)
+                guards = None
+        # "column": at least one aggregate took the column route (the normal-form ones beside
+        # it stay fused); a query that falls to the host has no entry
+        self.metrics.pop("cond_agg", None)
+        keep = {id(fn) for fn, g in zip(cases, guards or []) if g is not None}
+        if keep:
+            try:
+                f2, c2 = self._case_columns(final, child, keep)
+                fin = self._exec_agg_plain(f2, c2, order, limit)
+                self.metrics["cond_agg"] = "column"
+                return fin
+            except Unsupported as e:
+                log.debug("every conditional aggregate as a computed column: %s", e)
+        final, child = self._case_columns(final, child)
+        fin = self._exec_agg_plain(final, child, order, limit)
+        self.metrics["cond_agg"] = "column"
+        return fin
+
+    def _exec_agg_plain(self, final, child, order, limit):
         if final.mode == "complete":
             return self._distinct_agg(final, child)
         try:
@@ -58,6 +95,58 @@ class AggOps:
         except _NeedHash as e:
             log.debug("hash-mode aggregate: %s", e)
         return self._hash_agg(final, child, order, limit)
+
+    @staticmethod
+    def _case_columns(final: X.HashAggregateExec, child: X.SparkPlan, keep=frozenset()):
+        """Conditional aggregates as aggregates of hidden computed columns: the CASE input of
+        every aggregate function (but the fused ones, ``keep``: ids of function nodes) becomes a
+        named column of a projection (exec/project.py) and the function reads that column.  Over
+        a join the projection goes below it, onto the side that holds every column the CASE
+        reads, so the fused join aggregate still runs; a CASE over both sides is projected from
+        the joined rows."""
+        made: Dict[int, E.Alias] = {}
+
+        def swap(x):
+            if isinstance(x, E.AggregateFunction) and x.child is not None and \
+                    id(x) not in keep and E.contains_case(x.child):
+                a = made.get(id(x))
+                if a is None:
+                    a = made[id(x)] = E.Alias(x.child, f"__hs_case{len(made)}")
+                return type(x)(a.to_attribute())
+            return None
+        aggs = [e.transform_up(swap) for e in final.aggregates]
+        extra = list(made.values())
+        # the chain of pass-through projections down to a join
+        chain, node = [], child
+        while isinstance(node, X.ProjectExec) and \
+                all(isinstance(e, E.Attribute) for e in node.project_list):
+            chain.append(node)
+            node = node.child
+        top = list(extra)
+        if isinstance(node, X.SortMergeJoinExec) and node.join_type == "inner":
+            sides = [[], []]
+            top = []
+            for a in extra:
+                refs = {r.expr_id for r in a.child.references()}
+                for i, side in enumerate(node.children):
+                    if refs and refs <= {o.expr_id for o in side.output}:
+                        sides[i].append(a)
+                        break
+                else:
+                    top.append(a)
+            if sides[0] or sides[1]:
+                kids = [X.ProjectExec(list(s.output) + add, s) if add else s
+                        for s, add in zip(node.children, sides)]
+                node = X.SortMergeJoinExec(node.left_keys, node.right_keys, node.join_type,
+                                           node.condition, kids[0], kids[1])
+                below = [a.to_attribute() for a in sides[0] + sides[1]]
+                for pr in reversed(chain):
+                    node = X.ProjectExec(list(pr.project_list) + below, node)
+                child = node
+        if top:
+            child = X.ProjectExec(list(child.output) + top, child)
+        return X.HashAggregateExec(final.grouping, aggs, final.mode, final.child,
+                                   final.result_attrs), child
 
     @staticmethod
     def _named_groups(final: X.HashAggregateExec, child: X.SparkPlan):
@@ -582,8 +671,42 @@ class AggOps:
             self._domains[ck] = (c, dom)
         return dom
 
-    def _agg_specs(self, fns, col_info):
-        specs = [CP.agg_spec(fn, lambda a: col_info(a).slot) for fn in fns]
+    def _guards(self, fns) -> Optional[list]:
+        """Per aggregate of ``fns`` its guard (``CP.guard_of``: a conditional aggregate in the
+        fused kernels' normal form) or None; None when no aggregate has one.  Kept per function
+        node (a plan-cache hit submits the same nodes, with new values in their literals)."""
+        memo = self.__dict__.setdefault("_guard_memo", {})
+        out = []
+        for fn in fns:
+            hit = memo.get(id(fn))
+            if hit is None or hit[0] is not fn:
+                g = CP.guard_of(fn) if fn.child is not None and E.contains_case(fn.child) else None
+                if len(memo) > 1024:
+                    memo.clear()
+                hit = memo[id(fn)] = (fn, g)
+            out.append(hit[1])
+        return out if any(g is not None for g in out) else None
+
+    def _bind_guards(self, bound, fns, col_info):
+        """``bound`` (a bound row filter) with the guard predicates of ``fns`` behind it."""
+        guards = self._guards(fns)
+        if guards is not None:
+            CP.bind_guards(bound, guards, col_info, self.device)
+        return bound
+
+    def _agg_specs(self, fns, col_info, bound=None, base: int = 0):
+        """``bound``: the bound predicates that carry the guards of ``fns`` (``_bind_guards``),
+        ``base`` the index of its first predicate in the kernel's list."""
+        guards = self._guards(fns)
+        if guards is not None and (bound is None or len(bound.guards) != len(fns)):
+            raise Unsupported("guarded aggregate on a path that binds no guards")
+        specs = []
+        for i, fn in enumerate(fns):
+            if guards is None or guards[i] is None:
+                specs.append(CP.agg_spec(fn, lambda a: col_info(a).slot))
+            else:
+                specs.append(CP.guarded_agg_spec(fn, guards[i], lambda a: col_info(a).slot,
+                                                 bound.guards[i], base))
         star = NL.AggSpec()
         star.kind, star.nterms = NL.AK_COUNT_STAR, 0
         specs.append(star)
@@ -743,9 +866,10 @@ class AggOps:
             if bound is None:
                 bound = CP.bind(CP.to_cnf([c for c in r.conds if id(c) not in implied]),
                                 col_info, self.device)
+                self._bind_guards(bound, fns, col_info)
                 if prep is not None and bound.rebindable:
                     prep.tbound = (frozenset(implied), bound)
-            specs = self._agg_specs(fns, col_info)
+            specs = self._agg_specs(fns, col_info, bound)
             if lkey is not None:
                 if len(prep.lowered) >= 1024:
                     prep.lowered.clear()
@@ -786,7 +910,7 @@ class AggOps:
             p = prep.params
         for i, pr in enumerate(bound.preds):
             p.preds[i] = pr
-        p.npreds = len(bound.preds)
+        p.npreds = len(bound.filter_preds)    # (guard predicates lie behind the row filter's)
         for i, a in enumerate(specs):
             p.aggs[i] = a
         p.naggs = len(specs)
@@ -806,6 +930,8 @@ class AggOps:
                 if HyperspaceConf.codegen_enabled(self.session.conf):
                     out = jit.scan_agg(p, rstart, rlen, tp, self._compacts(descs),
                                        nrows=r.table.num_rows)
+                elif jit.has_guards(p):
+                    raise Unsupported("guarded aggregate needs code generation")
                 else:
                     out = K.scan_agg(p, rstart, rlen, tp)
         return (*out, G, gbase, gdict, gtype)
@@ -832,7 +958,7 @@ class AggOps:
                 prep.tpl = bytes(k.args.pack(prep.values, default=0))
             values: dict = {}
             jit.fill_preds_aggs(values, [(i, p.preds[i]) for i in range(p.npreds)],
-                                [p.aggs[i] for i in range(p.naggs)], compacts)
+                                jit.aggs_of(p), compacts)
             # (the per-query predicate buffers the block points to stay referenced with it)
             hit = (range_bounds(lo, lo_incl, hi, hi_incl),
                    _cbuf(k.args.patch(bytearray(prep.tpl), values)), list(keep))

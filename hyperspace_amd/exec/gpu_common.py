@@ -209,7 +209,7 @@ def _needs_eval(c: E.Expression) -> bool:
     the scan kernels' predicate compiler takes column / literal comparisons (it looks through
     value-preserving casts only), so such a conjunct is evaluated as a computed column."""
     for x in c.iter_tree():
-        if isinstance(x, E.BinaryArithmetic):
+        if isinstance(x, (E.BinaryArithmetic, E.CaseWhen)):
             return True
         if isinstance(x, E.Cast) and not isinstance(x.child, E.Literal) and \
                 not _lossless_cast(x.child.data_type, x.dtype):
@@ -453,10 +453,10 @@ class _JoinPrep:
                 if jp is None:
                     jp, col_info, descs, keep = be._join_params(
                         left, self.right, self.lk, self.rk, self.node.condition,
-                        lconds=self.lconds, slots=(self.col_info, self.descs))
+                        lconds=self.lconds, slots=(self.col_info, self.descs), fns=fns)
                     if keep[0].rebindable and keep[1].rebindable:
                         self.tjoin = (NL.JoinParams.from_buffer_copy(jp), keep)
-                specs = be._agg_specs(fns, col_info)
+                specs = be._agg_specs(fns, col_info, keep[1], len(keep[0].preds))
                 if len(descs) != nd:
                     raise _Stale()
                 if lkey is not None:

@@ -475,8 +475,10 @@ class HashAggOps:
             items.append((ci.slot, g, descs[ci.slot], doms[g.expr_id]))
         own = []
         for a in specs:
+            # (a guarded aggregate counts the rows its guard takes: never the group's rows)
             own.append(a.kind != NL.AK_COUNT_STAR and
-                       any(descs[a.col[t]].valid is not None for t in range(a.nterms)))
+                       (bool(a.pad) or
+                        any(descs[a.col[t]].valid is not None for t in range(a.nterms))))
         need_star = any(isinstance(fn, (E.Count, E.Avg)) for fn in fns)
         return H.plan_keys(items, tuple(own), need_star)
 
@@ -489,7 +491,8 @@ class HashAggOps:
                 self._full_ranges(r.table)
         bound = CP.bind(CP.to_cnf([c for c in r.conds if id(c) not in implied]), col_info,
                         self.device)
-        specs = self._agg_specs(fns, col_info)
+        self._bind_guards(bound, fns, col_info)
+        specs = self._agg_specs(fns, col_info, bound)
         hk = self._hash_keyplan(grouping, col_info, fns, doms, specs, descs)
         if not hk_box:
             hk_box.append(hk)
@@ -499,7 +502,7 @@ class HashAggOps:
             p.cols[s] = c.desc()
         for i, pr in enumerate(bound.preds):
             p.preds[i] = pr
-        p.npreds = len(bound.preds)
+        p.npreds = len(bound.filter_preds)
         for i, a in enumerate(specs):
             p.aggs[i] = a
         p.naggs = len(specs)
@@ -664,8 +667,8 @@ class HashAggOps:
             rstart, rlen, rbk = self._ranges(left, left.conds, implied)
         jp, col_info, descs, keep = self._join_params(
             left, right, lk, rk, node.condition,
-            lconds=[c for c in left.conds if id(c) not in implied])
-        specs = self._agg_specs(fns, col_info)
+            lconds=[c for c in left.conds if id(c) not in implied], fns=fns)
+        specs = self._agg_specs(fns, col_info, keep[1], len(keep[0].preds))
         hk = self._hash_keyplan(grouping, col_info, fns, doms, specs, descs)
         if not hk_box:
             hk_box.append(hk)

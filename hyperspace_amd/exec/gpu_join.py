@@ -417,7 +417,10 @@ class JoinOps:
         return r.copy(table=hit[1])
 
     def _join_params(self, left: DRel, right: DRel, lk, rk, residual, extra_attrs=(),
-                     lconds=None, slots=None):
+                     lconds=None, slots=None, fns=None):
+        """``fns``: the aggregates of a fused join aggregate - the guards of its conditional
+        aggregates are bound behind the right side's predicates (``_agg_specs`` takes the right
+        bound list and the left one's length as its base)."""
         col_info, descs = slots if slots is not None else \
             self._column_infos([(left, 0), (right, 8)])
         lslot = col_info(lk).slot
@@ -425,6 +428,8 @@ class JoinOps:
         lb = CP.bind(CP.to_cnf(left.conds if lconds is None else lconds), col_info, self.device, 0)
         rconds = list(right.conds) + ([residual] if residual is not None else [])
         rb = CP.bind(CP.to_cnf(rconds), col_info, self.device, 1000)
+        if fns is not None:
+            self._bind_guards(rb, fns, col_info)
         for a in extra_attrs:
             col_info(a)
         p = NL.JoinParams()
@@ -433,7 +438,7 @@ class JoinOps:
             raise Unsupported("too many join predicates")
         for i, pr in enumerate(preds):
             p.preds[i] = pr
-        p.nlp, p.npreds = len(lb.preds), len(preds)
+        p.nlp, p.npreds = len(lb.preds), len(lb.preds) + len(rb.filter_preds)
         p.lkey, p.rkey = lslot, rslot
         p.key_is_float = 1 if left.col(lk).is_float else 0
         p.group_col = -1
@@ -728,8 +733,8 @@ class JoinOps:
             rstart, rlen, rbk = self._ranges(left, left.conds, implied)
         jp, col_info, descs, keep = self._join_params(
             left, right, lk, rk, node.condition,
-            lconds=[c for c in left.conds if id(c) not in implied])
-        specs = self._agg_specs(fns, col_info)
+            lconds=[c for c in left.conds if id(c) not in implied], fns=fns)
+        specs = self._agg_specs(fns, col_info, keep[1], len(keep[0].preds))
         if group is not None:
             col_info(group)
             jp.group_col = col_info(group).slot if G > 1 else -1
@@ -785,4 +790,6 @@ class JoinOps:
                 return jit.join_agg(jp, rstart, rlen, rbk, right.table.bucket_offsets, max_tiles,
                                     self._compacts(descs),
                                     cache_spans=fr is not None and rstart is fr[0])
+            if jit.has_guards(jp):
+                raise Unsupported("guarded aggregate needs code generation")
             return K.join_agg(jp, rstart, rlen, rbk, right.table.bucket_offsets, max_tiles)

@@ -255,6 +255,8 @@ class SemiJoinOps:
         if r.table is None or r.parts or r.extra or r.split or not r.bucketed or \
                 not r.sort_attrs or r.sort_attrs[0].expr_id != key.expr_id:
             return None
+        if self._guards(fns) is not None:
+            return None     # the bit-parallel scan carries no per-aggregate guard
         col_info, descs = self._column_infos([(r, 0)])
         kslot = col_info(key).slot
         implied: set = set()

@@ -674,7 +674,9 @@ class _Gen:
         return " && ".join("(" + " || ".join(groups[g]) + ")" for g in order)
 
     def agg_value(self, i: int, a: NL.AggSpec) -> Tuple[str, str]:
-        """(value expr, validity expr) of aggregate i."""
+        """(value expr, validity expr) of aggregate i.  A guarded aggregate (``aggs_of``:
+        ``agg(CASE WHEN g THEN v [ELSE c] END)``) has the value ``g ? v : c``, valid where
+        ``g ? valid(v) : has_else`` - selects, so every accumulate site takes it as it is."""
         if a.kind == NL.AK_COUNT_STAR:
             return "1.0", "true"
         terms, oks = [], []
@@ -685,7 +687,21 @@ class _Gen:
             terms.append(f"({al} + {be} * (double)x{c})")
             if self.cols[c][1]:
                 oks.append(f"n{c}")
-        return " * ".join(terms) or "1.0", " && ".join(oks) or "true"
+        guard = getattr(a, "guard", None)
+        if guard is None:
+            return " * ".join(terms) or "1.0", " && ".join(oks) or "true"
+        gpreds, has_else, never = guard
+        # the guard's leaves compare decoded values (x<slot>, exact: _sum_only_slots), which
+        # every accumulate site has; the code-bound forms need registers only phase 1 makes
+        g = "false" if never else \
+            _Gen(self.a, self.cols, self.split, self.rows, self.approx, False).cnf(gpreds)
+        v = " * ".join(terms) or self.a.add("d", f"A{i}_0", "double")
+        ok = " && ".join(oks)
+        if not has_else:
+            # every accumulate site reads the value only where the validity holds
+            return v, f"(({g})" + (f" && {ok})" if ok else ")")
+        els = self.a.add("d", f"E{i}", "double")
+        return f"(({g}) ? ({v}) : {els})", (f"(!({g}) || ({ok}))" if ok else "true")
 
 
 def _sum_only_slots(preds, aggs, group_col: int = -1, cols=None) -> frozenset:
@@ -712,6 +728,8 @@ def _sum_only_slots(preds, aggs, group_col: int = -1, cols=None) -> frozenset:
             summed.update(cols)
         elif a.kind != NL.AK_COUNT_STAR:
             exact.update(cols)
+        # a guard compares decoded values: its columns decode exactly, like a predicate's
+        exact.update(_pred_slots(getattr(a, "guard", None) and a.guard[0] or []))
     return frozenset(summed - exact)
 
 
@@ -727,11 +745,50 @@ def _pred_slots(preds) -> List[int]:
 
 
 def _agg_slots(aggs) -> List[int]:
+    """Slots the aggregate phase reads: the aggregates' terms and their guards' columns (loaded
+    with them, for rows that passed the row filter only)."""
     s = []
     for a in aggs:
         if a.kind != NL.AK_COUNT_STAR:
             s += [a.col[t] for t in range(a.nterms)]
+            if getattr(a, "guard", None) is not None:
+                s += _pred_slots(a.guard[0])
     return list(dict.fromkeys(s))
+
+
+def aggs_of(p) -> list:
+    """The AggSpecs of scan / join parameters ``p``.  A guarded aggregate (``compile.py``:
+    ``AggSpec.pad`` places its guard predicates behind ``p.npreds``) carries ``guard`` =
+    ([(k, Pred)], has ELSE, never true), which ``_Gen.agg_value``, ``_agg_slots`` and
+    ``fill_preds_aggs`` read; an unguarded one is the plain structure."""
+    from .compile import guard_fields
+    out = []
+    for i in range(p.naggs):
+        a = p.aggs[i]
+        gf = guard_fields(a.pad)
+        if gf is not None:
+            first, count, has_else, never = gf
+            a.guard = ([(k, p.preds[k]) for k in range(first, first + count)], has_else, never)
+        out.append(a)
+    return out
+
+
+def has_guards(p) -> bool:
+    return any(p.aggs[i].pad for i in range(p.naggs))
+
+
+def aggs_shape(p) -> tuple:
+    """The aggregates' part of a kernel's shape key; an unguarded aggregate's entry is (kind,
+    terms, columns) as it always was, a guarded one adds its flags and guard predicates."""
+    out = []
+    for a in aggs_of(p):
+        e = (a.kind, a.nterms, tuple(a.col[:a.nterms]))
+        if getattr(a, "guard", None) is not None:
+            gp, has_else, never = a.guard
+            e += (("guard", has_else, never,
+                   tuple((k, q.kind, q.op, q.col, q.col2, q.group) for k, q in gp)),)
+        out.append(e)
+    return tuple(out)
 
 
 def _accumulate(gen: _Gen, aggs, grouped: bool, pass_var: str, gvar: str, ind: str) -> List[str]:
@@ -926,9 +983,11 @@ def scan_pack_layout(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None) -> 
     aggregate inputs through the LDS lists or already among the predicate columns)."""
     if not SCAN_PACK or vec != 8 or hk is not None or p.group_col >= 0:
         return None
+    if has_guards(p):
+        return None     # the packed tail lists the aggregates' term fields only
     preds = [(k, p.preds[k]) for k in range(p.npreds)]
     pslots = _pred_slots(preds)
-    aslots = [s for s in _agg_slots([p.aggs[i] for i in range(p.naggs)]) if s not in pslots]
+    aslots = [s for s in _agg_slots(aggs_of(p)) if s not in pslots]
     if aslots and not (SCAN_COMPACT or SCAN_EAGER):
         return None
     slots = pslots + aslots
@@ -1090,8 +1149,7 @@ def scan_agg_shape(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None,
     cols = tuple(sorted(_col_specs(p, compacts).items()))
     preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
                    p.preds[k].group) for k in range(p.npreds))
-    aggs = tuple((p.aggs[i].kind, p.aggs[i].nterms, tuple(p.aggs[i].col[:p.aggs[i].nterms]))
-                 for i in range(p.naggs))
+    aggs = aggs_shape(p)
     return ("scan_agg", cols, preds, aggs, p.group_col, SCAN_ITEMS, SCAN_EAGER, vec,
             SCAN_COMPACT, WAVE_SYNC, VEC_PREFETCH, hk.shape() if hk is not None else None)
 
@@ -1117,7 +1175,7 @@ def gen_scan_agg(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None,
     _common_args(args)
     cols = _col_specs(p, compacts)
     preds = [(k, p.preds[k]) for k in range(p.npreds)]
-    aggs = [p.aggs[i] for i in range(p.naggs)]
+    aggs = aggs_of(p)
     grouped = p.group_col >= 0
     assert not (grouped and hk is not None)
     pslots = _pred_slots(preds)
@@ -1238,7 +1296,7 @@ def scan_agg_values(p: NL.ScanParams, rstart, rlen, tile_prefix, parts,
          "pmin": parts[2].data_ptr(), "pmax": parts[3].data_ptr(),
          "num_groups": p.num_groups, "group_base": p.group_base}
     _fill_common(v, p.cols, [(k, p.preds[k]) for k in range(p.npreds)],
-                 [p.aggs[i] for i in range(p.naggs)], compacts)
+                 aggs_of(p), compacts)
     return v
 
 
@@ -1337,7 +1395,16 @@ def _fill_cols(v: Dict[str, object], cols, compacts=None) -> None:
 
 
 def fill_preds_aggs(v: Dict[str, object], preds, aggs, compacts=None) -> None:
-    """Literal-dependent argument slots: predicate values / code bounds and aggregate terms."""
+    """Literal-dependent argument slots: predicate values / code bounds and aggregate terms
+    (``aggs``: ``aggs_of`` - a guarded aggregate brings its guard's predicates, its constant
+    THEN value and its ELSE constant)."""
+    guarded = [(i, a) for i, a in enumerate(aggs) if getattr(a, "guard", None) is not None]
+    if guarded:
+        preds = list(preds) + [kp for _, a in guarded for kp in a.guard[0]]
+        for i, a in guarded:
+            if a.nterms == 0:
+                v[f"A{i}_0"] = a.alpha[0]
+            v[f"E{i}"] = a.alpha[NL.MAX_TERMS - 1]
     for k, p in preds:
         v[f"L{k}"] = p.ilit
         v[f"F{k}"] = p.flit
@@ -1362,8 +1429,7 @@ def join_agg_shape(p: NL.JoinParams, compacts=None) -> tuple:
     cols = tuple(sorted(_col_specs(p, compacts).items()))
     preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
                    p.preds[k].group) for k in range(p.npreds))
-    aggs = tuple((p.aggs[i].kind, p.aggs[i].nterms, tuple(p.aggs[i].col[:p.aggs[i].nterms]))
-                 for i in range(p.naggs))
+    aggs = aggs_shape(p)
     return ("join_agg", cols, preds, p.nlp, aggs, p.group_col, p.lkey, p.rkey, p.key_is_float,
             JOIN_ITEMS, JOIN_LDS_KEYS, JOIN_EAGER, JOIN_BLOCK, JOIN_STAGE_RIGHT, JOIN_PIPELINE,
             JOIN_DIRECT, JOIN_DIRECT_SLOTS)
@@ -1403,7 +1469,7 @@ def gen_join_agg(p: NL.JoinParams, compacts=None) -> Kernel:
     gen = _Gen(args, cols, split, ("lrow", "j"))
     lpreds = [(k, p.preds[k]) for k in range(p.nlp)]
     rpreds = [(k, p.preds[k]) for k in range(p.nlp, p.npreds)]
-    aggs = [p.aggs[i] for i in range(p.naggs)]
+    aggs = aggs_of(p)
     grouped = p.group_col >= 0
     fl = bool(p.key_is_float)
     lk, rk = p.lkey, p.rkey
@@ -1657,8 +1723,7 @@ def join_index_agg_shape(p: NL.JoinParams, compacts=None, vec: int = 0, jw: int 
     cols = tuple(sorted(_col_specs(p, compacts).items()))
     preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
                    p.preds[k].group) for k in range(p.npreds))
-    aggs = tuple((p.aggs[i].kind, p.aggs[i].nterms, tuple(p.aggs[i].col[:p.aggs[i].nterms]))
-                 for i in range(p.naggs))
+    aggs = aggs_shape(p)
     return ("join_index_agg", cols, preds, p.nlp, aggs, p.group_col, JI_ITEMS, vec, BLOCK, jw,
             jlog, JI_COMPACT, WAVE_SYNC, bool(stage and vec), bool(bitmap), VEC_PREFETCH)
 
@@ -2004,7 +2069,7 @@ def gen_join_index_agg(p: NL.JoinParams, compacts=None, vec: int = 0, jw: int = 
     split = 8
     lpreds = [(k, p.preds[k]) for k in range(p.nlp)]
     rpreds = [(k, p.preds[k]) for k in range(p.nlp, p.npreds)]
-    aggs = [p.aggs[i] for i in range(p.naggs)]
+    aggs = aggs_of(p)
     grouped = p.group_col >= 0
     first = _pred_slots(lpreds)
     second = [s for s in _pred_slots(rpreds) if s not in first]
@@ -2358,7 +2423,7 @@ def join_index_agg(p: NL.JoinParams, rstart, rlen, jx, compacts=None, nrows: int
          "num_groups": p.num_groups, "group_base": p.group_base,
          "rbm": bm.data_ptr() if bm is not None else 0}
     _fill_common(v, p.cols, [(k_, p.preds[k_]) for k_ in range(p.npreds)],
-                 [p.aggs[i] for i in range(p.naggs)], compacts)
+                 aggs_of(p), compacts)
     k.launch(grid, v, NL.stream_ptr(), GA * 32 if p.group_col >= 0 else 0)
     return _final(parts, grid, GA, rstart.device)
 

@@ -17,8 +17,7 @@ def merge_join_shape(p: NL.JoinParams, compacts=None, hk=None) -> tuple:
     cols = tuple(sorted(J._col_specs(p, compacts).items()))
     preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
                    p.preds[k].group) for k in range(p.npreds))
-    aggs = tuple((p.aggs[i].kind, p.aggs[i].nterms, tuple(p.aggs[i].col[:p.aggs[i].nterms]))
-                 for i in range(p.naggs))
+    aggs = J.aggs_shape(p)
     return ("merge_join_agg", cols, preds, p.nlp, aggs, p.group_col, p.lkey, p.rkey,
             p.key_is_float, J.MJ_ITEMS, J.MJ_LDS_KEYS, J.MJ_STEPS, J.BLOCK, J.WAVE_SYNC,
             _key32_frame(p, compacts) is not None, J.MJ_STAGE_UNROLL, J.MJ_DBUF, J.MJ_PREFETCH,
@@ -233,7 +232,7 @@ def gen_merge_join_agg(p: NL.JoinParams, compacts=None, hk=None) -> J.Kernel:
     rpreds = [(k, p.preds[k]) for k in range(p.nlp, p.npreds)]
     ronly = [(k, q) for k, q in rpreds if all(x >= split for x in _slots_of(q))]
     mixed = [(k, q) for k, q in rpreds if (k, q) not in ronly]
-    aggs = [p.aggs[i] for i in range(p.naggs)]
+    aggs = J.aggs_of(p)
     grouped = p.group_col >= 0
     assert not (grouped and hk is not None)
     hslots = hk.slots if hk is not None else []
@@ -816,7 +815,7 @@ def merge_join_agg(p: NL.JoinParams, rstart, rlen, rbucket, roff, compacts=None,
              "spans": spans.data_ptr(), "R": rstart.numel(), "nrows": nrows, "rdup": int(rdup),
              "psum": 0, "pcnt": 0, "pmin": 0, "pmax": 0, "TR": tr.data_ptr() if tr is not None else 0}
         J._fill_common(v, p.cols, [(k_, p.preds[k_]) for k_ in range(p.npreds)],
-                     [p.aggs[i] for i in range(p.naggs)], compacts)
+                     J.aggs_of(p), compacts)
         frame = _key32_frame(p, compacts)
         if frame is not None:
             v["KLO"], v["KSP"], v["KOF"] = frame
@@ -864,7 +863,7 @@ class MergeJoinLauncher:
         v.update({"psum": parts[0].data_ptr(), "pcnt": parts[1].data_ptr(),
                   "pmin": parts[2].data_ptr(), "pmax": parts[3].data_ptr()})
         J.fill_preds_aggs(v, [(k_, p.preds[k_]) for k_ in range(p.npreds)],
-                        [p.aggs[i] for i in range(p.naggs)], self.compacts)
+                        J.aggs_of(p), self.compacts)
         self.k.launch(self.grid, v, NL.stream_ptr(), self.shmem)
         return J._final(parts, self.grid, self.GA, self.dev)
 
@@ -877,6 +876,10 @@ def _with_runs(p: NL.JoinParams, compacts):
     from .encoding import GroupedCompact, key_runs
     ni = _mj_items(True)
     if not (J.MJ_RUNS and ni and 64 % ni == 0) or _key32_frame(p, compacts) is None:
+        return compacts, None
+    if J.has_guards(p):
+        # the run-keyed forms (and the two-phase kernels over them: bit-parallel phase 2, the
+        # 12-bit pack) have no place for a per-aggregate guard: the generic merge join runs
         return compacts, None
     lk = p.lkey
     c = compacts.get(lk)
@@ -924,7 +927,7 @@ def _with_key16(p: NL.JoinParams, compacts):
     if p.cols[lk].valid:
         return compacts
     used = set(J._pred_slots([(k, p.preds[k]) for k in range(p.npreds)])) | \
-        set(J._agg_slots([p.aggs[i] for i in range(p.naggs)])) | {p.group_col}
+        set(J._agg_slots(J.aggs_of(p))) | {p.group_col}
     if lk in used:
         return compacts
     g = grouped16(compacts[lk])
@@ -1004,7 +1007,7 @@ def join_agg_values(p: NL.JoinParams, tile_prefix, spans, parts,
          "pmin": parts[2].data_ptr(), "pmax": parts[3].data_ptr(),
          "num_groups": p.num_groups, "group_base": p.group_base}
     J._fill_common(v, p.cols, [(k, p.preds[k]) for k in range(p.npreds)],
-                 [p.aggs[i] for i in range(p.naggs)], compacts)
+                 J.aggs_of(p), compacts)
     return v
 
 

@@ -106,7 +106,9 @@ def tag_width(p: NL.JoinParams) -> int:
 
 
 def applies(p: NL.JoinParams) -> bool:
-    if not MJ_2P:
+    if not MJ_2P or J.has_guards(p):
+        # (the two phases carry one pass bit per row: a guarded aggregate takes the generic
+        # merge join, whose aggregate phase sees the guard's columns)
         return False
     for i in range(p.naggs):
         a = p.aggs[i]
@@ -1077,7 +1079,7 @@ def gen_run_scan(p: NL.JoinParams, compacts, W: int, NI: int) -> J.Kernel:
     args, lk = _scan_args(p), p.lkey
     cols = J._col_specs(p, compacts)
     lpreds = _lpreds(p)
-    aggs = [p.aggs[i] for i in range(p.naggs)]
+    aggs = J.aggs_of(p)
     grouped = _scan_grouped(p)
     rgroup = grouped and p.group_col >= SPLIT
     pslots = J._pred_slots(lpreds)
@@ -1148,7 +1150,7 @@ def gen_run_scan(p: NL.JoinParams, compacts, W: int, NI: int) -> J.Kernel:
 
 def _tail_slots(p: NL.JoinParams) -> list:
     grouped = _scan_grouped(p)
-    aggs = [p.aggs[i] for i in range(p.naggs)]
+    aggs = J.aggs_of(p)
     return list(dict.fromkeys(J._agg_slots(aggs) + ([p.group_col] if grouped else [])))
 
 
@@ -1369,7 +1371,7 @@ def _bits_tail(p: NL.JoinParams, hk, tk) -> list:
     """The slots the walk reads per passing row."""
     # top-K mode segments the walk by key run (lrn_) and loads the key columns only where a
     # group is emitted (jit_hash._hash_accumulate ``seg``): they are not part of the per-row tail
-    aggs = [p.aggs[i] for i in range(p.naggs)]
+    aggs = J.aggs_of(p)
     return list(dict.fromkeys(J._agg_slots(aggs) + ([p.group_col] if _scan_grouped(p) else []) +
                               (list(hk.slots) if hk is not None and tk is None else [])))
 
@@ -1416,7 +1418,7 @@ class _BitsScan:
         self.p, self.hk, self.tk, self.lk = p, hk, tk, p.lkey
         self.args = args = _scan_args(p, f.pair)
         self.cols = cols = J._col_specs(p, compacts)
-        self.lpreds, self.aggs = _lpreds(p), [p.aggs[i] for i in range(p.naggs)]
+        self.lpreds, self.aggs = _lpreds(p), J.aggs_of(p)
         self.pslots, self.tail = J._pred_slots(self.lpreds), _bits_tail(p, hk, tk)
         self.approx = J._sum_only_slots(self.lpreds, self.aggs,
                                         p.group_col if f.grouped else -1, cols) - \
@@ -2266,7 +2268,7 @@ class TwoPhaseLauncher:
         hit = self.blocks.get(key) if key is not None else None
         if hit is None:
             preds = [(k_, p.preds[k_]) for k_ in range(p.npreds)]
-            aggs = [p.aggs[i] for i in range(p.naggs)]
+            aggs = J.aggs_of(p)
             if self.tpl is None:
                 vs0 = dict(self.vs)
                 vs0.update({"psum": 0, "pcnt": 0, "pmin": 0, "pmax": 0})
@@ -2391,7 +2393,7 @@ class TwoPhaseLauncher:
             J.fill_preds_aggs(vt, preds, [], self.compacts)
             vs = dict(self.vs)
             vs.update({"psum": 0, "pcnt": 0, "pmin": 0, "pmax": 0})
-            J.fill_preds_aggs(vs, preds, [p.aggs[i] for i in range(p.naggs)], self.compacts)
+            J.fill_preds_aggs(vs, preds, J.aggs_of(p), self.compacts)
             vs.update(htab.kernel_values())
             vs.update((hk or self.hk).values())   # this query's key domain
             if self.tk is not None:
@@ -2559,7 +2561,7 @@ def semi_runs_agg(p: NL.JoinParams, rstart, rlen, compacts, runs, nrows: int, wo
     vs.update({"psum": parts[0].data_ptr(), "pcnt": parts[1].data_ptr(),
                "pmin": parts[2].data_ptr(), "pmax": parts[3].data_ptr()})
     J.fill_preds_aggs(vs, [(k_, p.preds[k_]) for k_ in range(p.npreds)],
-                      [p.aggs[i] for i in range(p.naggs)], compacts)
+                      J.aggs_of(p), compacts)
     ks.launch(grid, vs, st, GA * 32 if _scan_grouped(p) else 0)
     out = J._final(parts, grid, GA, dev)
     for t in (tags, tp64, pk, *p12):   # used by the queued kernels: keep until they ran

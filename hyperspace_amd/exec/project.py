@@ -19,6 +19,7 @@ Semantics (Spark non-ANSI, and the host oracle ``exec/arrow_eval.py``):
 """
 from __future__ import annotations
 
+import datetime
 from typing import Dict, List, Tuple
 
 import pyarrow as pa
@@ -49,10 +50,27 @@ def _kind(t: pa.DataType) -> str:
     raise Unsupported(f"computed projection over {t}")
 
 
+def _is_date(e: E.Expression) -> bool:
+    try:
+        return pa.types.is_date32(e.data_type)
+    except ValueError:
+        return False
+
+
+def _date_compare(e: E.BinaryComparison) -> bool:
+    """Date against date, or against a string literal (which the analyzer reads as a date)."""
+    def text(x):
+        return isinstance(x, E.Literal) and isinstance(x.value, str)
+    l, r = e.left, e.right
+    return (_is_date(l) and (_is_date(r) or text(r))) or (text(l) and _is_date(r))
+
+
 def _out_storage(t: pa.DataType):
     import torch
     if pa.types.is_boolean(t):
         return torch.uint8, "unsigned char"
+    if pa.types.is_date32(t):
+        return torch.int32, "int"
     if pa.types.is_integer(t):
         bw = t.bit_width
         return ({8: torch.int8, 16: torch.int16, 32: torch.int32, 64: torch.int64}[bw],
@@ -73,18 +91,20 @@ class _Gen:
         self.values: Dict[str, object] = {}
         self.shape: List[object] = []
         self.n = 0
+        self.in_case = 0            # depth of CaseWhen nodes around the node being emitted
 
     def _var(self) -> str:
         self.n += 1
         return f"t{self.n}"
 
-    def attr(self, a: E.Attribute) -> Tuple[str, str, str]:
+    def attr(self, a: E.Attribute, dates: bool = False) -> Tuple[str, str, str]:
         c = self.cols.get(a.expr_id)
         if c is None:
             raise Unsupported(f"attribute {a.sql()} not on device")
         if c.dictionary is not None:
             raise Unsupported("computed projection over a string column")
-        k = _kind(c.atype)
+        # a date is its day number where a CASE selects or compares dates (``dates``)
+        k = "i" if dates and pa.types.is_date32(c.atype) else _kind(c.atype)
         s = self.slot.get(a.expr_id)
         if s is None:
             s = self.slot[a.expr_id] = len(self.slot)
@@ -100,13 +120,20 @@ class _Gen:
                           else f"const bool {ok} = true;")
         return v, ok, k
 
-    def lit(self, e: E.Literal) -> Tuple[str, str, str]:
+    def lit(self, e: E.Literal, dates: bool = False) -> Tuple[str, str, str]:
         v, ok = self._var(), self._var()
         if e.value is None:
             self.shape.append(("null",))
             self.lines.append(f"const long long {v} = 0; const bool {ok} = false;")
             return v, ok, "i"
         val = e.value
+        if dates and isinstance(val, str):
+            try:
+                val = datetime.date.fromisoformat(val[:10])
+            except ValueError:
+                raise Unsupported(f"literal {val!r} compared with a date") from None
+        if dates and isinstance(val, datetime.date) and not isinstance(val, datetime.datetime):
+            val = (val - datetime.date(1970, 1, 1)).days
         if isinstance(val, bool):
             k = "b"
         elif isinstance(val, int):
@@ -129,6 +156,53 @@ class _Gen:
         self.lines.append(f"const bool {ok} = true;")
         return v, ok, k
 
+    def operand(self, e: E.Expression, dates: bool) -> Tuple[str, str, str]:
+        """``emit`` with date columns and date literals as day numbers when ``dates``."""
+        while isinstance(e, E.Alias):
+            e = e.child
+        if isinstance(e, E.Attribute):
+            return self.attr(e, dates)
+        if isinstance(e, E.Literal):
+            return self.lit(e, dates)
+        return self.emit(e)
+
+    def case_when(self, e: E.CaseWhen) -> Tuple[str, str, str]:
+        """Nested selects over the (value, valid) pairs of the branches: the first branch whose
+        condition is valid and true gives both; every operand is computed, nothing branches."""
+        rt = e.data_type
+        if pa.types.is_string(rt) or pa.types.is_large_string(rt):
+            raise Unsupported("string-valued CASE in a computed projection")
+        dates = pa.types.is_date32(rt)
+        rk = "i" if dates else _kind(rt)
+        ct = {"i": "long long", "f": "double", "b": "bool"}[rk]
+        self.shape.append(("case", len(e.branches), e.else_value is not None, rk))
+
+        def value(x):
+            v, ok, k = self.operand(x, dates)
+            null = isinstance(x, E.Literal) and x.value is None
+            if not null and k != rk and not (k == "i" and rk == "f"):
+                raise Unsupported(f"CASE value {x.sql()} in a {rt} result")
+            return f"({ct}){v}", ok
+        self.in_case += 1
+        try:
+            arms = []
+            for c, x in e.branches:
+                cv, cok, ck = self.emit(c)
+                if ck != "b" and not (isinstance(c, E.Literal) and c.value is None):
+                    raise Unsupported("CASE condition that is not a boolean")
+                arms.append((f"({cok} && {cv})", *value(x)))
+            tail_v, tail_ok = value(e.else_value) if e.else_value is not None else \
+                (f"({ct})0", "false")
+        finally:
+            self.in_case -= 1
+        v, ok = self._var(), self._var()
+        ve, oke = tail_v, tail_ok
+        for g, bv, bok in reversed(arms):
+            ve, oke = f"({g} ? {bv} : {ve})", f"({g} ? {bok} : {oke})"
+        self.lines.append(f"const {ct} {v} = {ve};")
+        self.lines.append(f"const bool {ok} = {oke};")
+        return v, ok, rk
+
     def emit(self, e: E.Expression) -> Tuple[str, str, str]:
         if isinstance(e, E.Alias):
             return self.emit(e.child)
@@ -137,6 +211,15 @@ class _Gen:
         if isinstance(e, E.Literal):
             return self.lit(e)
         self.shape.append(type(e).__name__)
+        if isinstance(e, E.CaseWhen):
+            return self.case_when(e)
+        if self.in_case and type(e) in _CMP and _date_compare(e):
+            # inside a CASE (a WHERE conjunct on dates alone never comes here): day numbers
+            (a, av, ak), (b, bv, bk) = self.operand(e.left, True), self.operand(e.right, True)
+            v, ok = self._var(), self._var()
+            self.lines.append(f"const bool {ok} = {av} && {bv};")
+            self.lines.append(f"const bool {v} = (long long){a} {_CMP[type(e)]} (long long){b};")
+            return v, ok, "b"
         if type(e) in _ARITH or isinstance(e, (E.Divide, E.Remainder)) or type(e) in _CMP:
             (a, av, ak), (b, bv, bk) = self.emit(e.left), self.emit(e.right)
             if "b" in (ak, bk):

@@ -115,6 +115,10 @@ SIDE_STREAM_PRIORITY_DEFAULT = "normal"
 # hipGraph per lowering (graphs.TwoPhaseGraph); needs hipGraph.enabled
 JOIN_GRAPH_ENABLED = "spark.hyperspace.mi.joinGraph.enabled"
 JOIN_GRAPH_ENABLED_DEFAULT = "true"
+# conditional aggregates agg(CASE WHEN p THEN v [ELSE c] END) run as a guard inside the fused
+# scan / join aggregate kernels; false: the CASE is computed as a hidden column first
+COND_AGG_FUSED = "spark.hyperspace.mi.condAgg.fused"
+COND_AGG_FUSED_DEFAULT = "true"
 # plan-cache hits of a fused aggregate with a known literal vector replay the prepared
 # lowering directly (exec/gpu.py _AggProgram), skipping the executor's plan walk
 PREPARED_SUBMIT_ENABLED = "spark.hyperspace.mi.preparedSubmit.enabled"

@@ -523,6 +523,154 @@ class Cast(Expression):
 
 
 # ---------------------------------------------------------------------------------------------
+# Conditional
+# ---------------------------------------------------------------------------------------------
+def _plain_type(t: pa.DataType) -> pa.DataType:
+    return t.value_type if pa.types.is_dictionary(t) else t
+
+
+def _case_family(t: pa.DataType) -> str:
+    if pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_decimal(t):
+        return "numeric"
+    if pa.types.is_string(t) or pa.types.is_large_string(t):
+        return "string"
+    if pa.types.is_date32(t) or pa.types.is_date64(t):
+        return "date"
+    if pa.types.is_boolean(t):
+        return "boolean"
+    return str(t)
+
+
+def common_case_type(a: pa.DataType, b: pa.DataType, what="CASE") -> pa.DataType:
+    """The type two branch values of a CASE share: integers widen to the widest integer, an
+    integer with a floating or decimal value is a double (the rule of the host engine's
+    ``_numeric_align``), strings go with strings, dates with dates, booleans with booleans; a
+    NULL literal takes the other side's type.  Anything else is an analysis error that names
+    both types (``what``: the expression's text, or a function that builds it - only then)."""
+    a, b = _plain_type(a), _plain_type(b)
+    if pa.types.is_null(a):
+        return b
+    if pa.types.is_null(b) or a == b:
+        return a
+    fa, fb = _case_family(a), _case_family(b)
+    if fa == fb == "numeric":
+        if pa.types.is_integer(a) and pa.types.is_integer(b):
+            return a if a.bit_width >= b.bit_width else b
+        return pa.float64()
+    if fa == fb and fa in ("string", "date"):
+        return pa.string() if fa == "string" else a
+    from ..exceptions import HyperspaceException
+    what = what() if callable(what) else what
+    raise HyperspaceException(
+        f"cannot resolve '{what}' due to data type mismatch: THEN and ELSE expressions should "
+        f"all be same type or coercible to a common type, got {a} and {b}")
+
+
+class CaseWhen(Expression):
+    """``CASE WHEN c1 THEN v1 [WHEN c2 THEN v2 ...] [ELSE e] END`` with Spark's semantics: the
+    first branch whose condition is TRUE wins (a NULL condition is not taken); without an ELSE
+    the result of a row no branch takes is NULL.  The children are the conditions and values in
+    order, then the ELSE value if there is one - so every literal in it is an ordinary
+    ``Literal`` child (which the plan cache parameterises) and the node has no other field."""
+
+    def __init__(self, branches, else_value: Expression = None):
+        branches = [(c, v) for c, v in branches]
+        if not branches:
+            raise ValueError("CASE needs at least one WHEN branch")
+        flat = [x for b in branches for x in b]
+        self.children = tuple(flat) + ((else_value,) if else_value is not None else ())
+        # resolution rebuilds the node over resolved children (with_children): then the
+        # branch types are known, and values without a common type are an analysis error
+        try:
+            self.data_type
+        except ValueError:      # an unresolved attribute below: checked once it is resolved
+            pass
+        for c in self.children[:len(branches) * 2:2]:
+            try:
+                t = c.data_type
+            except ValueError:
+                continue
+            if not (pa.types.is_boolean(t) or pa.types.is_null(t)):
+                from ..exceptions import HyperspaceException
+                raise HyperspaceException(
+                    f"cannot resolve '{self.sql()}' due to data type mismatch: WHEN expressions "
+                    f"should all be boolean type, but {c.sql()} is {t}")
+
+    @property
+    def branches(self) -> list:
+        n = len(self.children) // 2
+        return [(self.children[2 * i], self.children[2 * i + 1]) for i in range(n)]
+
+    @property
+    def else_value(self):
+        return self.children[-1] if len(self.children) % 2 else None
+
+    @property
+    def values(self) -> list:
+        """The branch values, then the ELSE value if there is one."""
+        out = [v for _, v in self.branches]
+        if self.else_value is not None:
+            out.append(self.else_value)
+        return out
+
+    def with_children(self, children):
+        children = tuple(children)
+        n = len(children) // 2
+        return CaseWhen([(children[2 * i], children[2 * i + 1]) for i in range(n)],
+                        children[-1] if len(children) % 2 else None)
+
+    @property
+    def data_type(self):
+        vals = self.values
+        t = vals[0].data_type
+        for v in vals[1:]:
+            t = common_case_type(t, v.data_type, self.sql)
+        return _plain_type(t)
+
+    @property
+    def nullable(self):
+        return self.else_value is None or any(v.nullable for v in self.values)
+
+    def canonical_key(self):
+        return ("CaseWhen", len(self.children)) + tuple(c.canonical_key() for c in self.children)
+
+    def sql(self):
+        parts = ["CASE"]
+        for c, v in self.branches:
+            cs = c.sql()
+            if not (cs.startswith("(") and cs.endswith(")")):
+                cs = f"({cs})"
+            parts.append(f"WHEN {cs} THEN {v.sql()}")
+        if self.else_value is not None:
+            parts.append(f"ELSE {self.else_value.sql()}")
+        parts.append("END")
+        return " ".join(parts)
+
+
+def contains_case(e: Expression) -> bool:
+    return any(isinstance(x, CaseWhen) for x in e.iter_tree())
+
+
+def references_outside_case(e: Expression) -> List["Attribute"]:
+    """``e.references()`` without the attributes that only occur inside a ``CaseWhen``: a
+    predicate over a CASE says nothing about the nullness of the columns the CASE reads
+    (``coalesce(x, 0) > 1`` is true for a NULL ``x``)."""
+    out: list = []
+
+    def walk(x):
+        if isinstance(x, CaseWhen):
+            return
+        if isinstance(x, Attribute):
+            if all(a.expr_id != x.expr_id for a in out):
+                out.append(x)
+            return
+        for c in x.children:
+            walk(c)
+    walk(e)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Aggregates
 # ---------------------------------------------------------------------------------------------
 class AggregateFunction(Expression):

@@ -99,7 +99,8 @@ def _null_intolerant_attrs(cond: E.Expression) -> List[E.Attribute]:
     out = []
     for c in E.split_conjuncts(cond):
         if isinstance(c, (E.BinaryComparison, E.In, E.InSet, E.Like)):
-            for a in c.references():
+            # not through a CASE: ``coalesce(x, 0) > 1`` is true for a NULL x
+            for a in E.references_outside_case(c):
                 out.append(a)
         elif isinstance(c, E.IsNotNull) and isinstance(c.child, E.Attribute):
             out.append(c.child)

@@ -2,7 +2,10 @@
 
 Grammar (precedence low->high): OR, AND, NOT, comparison / IN / BETWEEN / IS [NOT] NULL,
 additive, multiplicative, unary minus, primary (literal, column, function call with an optional
-``OVER ([PARTITION BY e, ...] [ORDER BY e [ASC|DESC], ...])``, parenthesised).
+``OVER ([PARTITION BY e, ...] [ORDER BY e [ASC|DESC], ...])``, parenthesised,
+``CASE [x] WHEN c THEN v ... [ELSE e] END``).  ``if(c, a, b)``, ``coalesce(a, b, ...)`` and
+``nullif(a, b)`` build the same ``CaseWhen``; CASE / WHEN / THEN / ELSE / END are recognised by
+position, so columns of those names keep parsing.
 Produces expressions with ``UnresolvedAttribute`` leaves; the DataFrame resolves them.
 """
 from __future__ import annotations
@@ -216,10 +219,55 @@ class _Parser:
             self.expect("op", ")")
             return e
         if kind == "id":
+            if text.upper() == "CASE" and self._case_ahead():
+                # CASE is no reserved word: what follows decides, and a text that does not
+                # parse as a CASE expression is read as before (a column or function ``case``)
+                save, searched = self.i, self.word("WHEN")
+                try:
+                    return self.case_expr()
+                except SyntaxError:
+                    if searched:
+                        raise
+                    self.i = save
             if self.peek() == ("op", "("):
                 return self.over(self.call(text))
             return E.UnresolvedAttribute(text)
         raise SyntaxError(f"unexpected token {text!r}")
+
+    # -- CASE [x] WHEN c THEN v ... [ELSE e] END ------------------------------------------------
+    def _case_ahead(self) -> bool:
+        """Whether the token after the word CASE can start an operand or a WHEN."""
+        t = self.peek()
+        return t[0] in ("id", "num", "str") or t == ("op", "(") or \
+            (t[0] == "kw" and t[1] in ("NOT", "NULL", "TRUE", "FALSE", "DATE", "TIMESTAMP"))
+
+    def case_expr(self):
+        """After the word CASE.  The words WHEN / THEN / ELSE / END are recognised where the
+        grammar expects them only, so columns of those names keep parsing."""
+        operand = None
+        if not (self.word("WHEN") and self._starts_operand(1)):
+            operand = self.or_expr()
+        branches = []
+        while self.accept_word("WHEN"):
+            cond = self.or_expr()
+            if operand is not None:
+                cond = E.EqualTo(operand, cond)
+            if not self.accept_word("THEN"):
+                raise SyntaxError(f"expected THEN in CASE, got {self.peek()[1]!r}")
+            branches.append((cond, self.or_expr()))
+        if not branches:
+            raise SyntaxError(f"expected WHEN in CASE, got {self.peek()[1]!r}")
+        else_value = None
+        if self.word("ELSE") and self._starts_operand(1):
+            self.take()
+            else_value = self.or_expr()
+        if not self.accept_word("END"):
+            raise SyntaxError(f"expected END of CASE, got {self.peek()[1]!r}")
+        return E.CaseWhen(branches, else_value)
+
+    def _starts_operand(self, k: int) -> bool:
+        t = self.peek(k)
+        return t[0] in ("id", "num", "str", "kw") or t in (("op", "("), ("op", "-"), ("op", "!"))
 
     # -- fn(args) [OVER (...)] ------------------------------------------------------------------
     def word(self, text: str, k: int = 0) -> bool:
@@ -318,6 +366,21 @@ def make_function(name: str, args, distinct: bool = False):
              "mean": E.Avg}
     if n in table:
         return table[n](args[0] if args else None)
+    # conditional sugar: all three build a CaseWhen
+    if n == "if":
+        if len(args) != 3:
+            raise SyntaxError("if() takes three arguments: if(condition, then, else)")
+        return E.CaseWhen([(args[0], args[1])], args[2])
+    if n == "coalesce":
+        if not args:
+            raise SyntaxError("coalesce() takes at least one argument")
+        if len(args) == 1:
+            return args[0]
+        return E.CaseWhen([(E.IsNotNull(a), a) for a in args[:-1]], args[-1])
+    if n == "nullif":
+        if len(args) != 2:
+            raise SyntaxError("nullif() takes two arguments")
+        return E.CaseWhen([(E.EqualTo(args[0], args[1]), E.Literal(None))], args[0])
     ranking = {"row_number": E.RowNumber, "rank": E.Rank, "dense_rank": E.DenseRank}
     if n in ranking:
         if args:

@@ -127,6 +127,10 @@ class HyperspaceConf:
         return _b(conf.get(C.CODEGEN_ENABLED, C.CODEGEN_ENABLED_DEFAULT))
 
     @staticmethod
+    def cond_agg_fused(conf) -> bool:
+        return _b(conf.get(C.COND_AGG_FUSED, C.COND_AGG_FUSED_DEFAULT))
+
+    @staticmethod
     def fd_group_enabled(conf) -> bool:
         """GROUP BY (join key, right columns) over a unique right key groups by the key and
         looks the right columns up for the result groups (exec/gpu.py ``_fd_grouping``)."""
