@@ -50,6 +50,10 @@ against the same query with Hyperspace disabled (the reference's correctness ora
   (``--zorder-sf``, default 10): device and host ``createIndex``, zone-map build and prune pass,
   and 5 % range filters on either or both columns with the index, with pruning off, and with
   Hyperspace disabled (one session each, alternating).
+* ``date_fns`` — date functions (``--date-sf``, default 10): the ``year(l_shipdate)`` projection
+  against a same-byte arithmetic one, a Q8-style query grouped by ``extract(year FROM ...)``
+  against one grouped by a stored column, and ``WHERE year(l_shipdate) = 1994`` with the range
+  rewrite on and off; alternating runs, medians.
 * ``case_when`` — conditional aggregates over the bench's lineitem / orders index pair
   (``--case-sf``, default 10): a Q12-style grouped join, a Q14-style ratio and an ungrouped
   Q6-style query, each as fused guards, as a hidden computed column, with the guard in WHERE
@@ -1403,12 +1407,109 @@ def config_zorder(args):
     return out
 
 
+def config_date_fns(args):
+    """Date functions over the lineitem / orders index pair of the bench (TPC-H SF ``--date-sf``),
+    every query cross-checked against the host engine; alternating runs in one process, medians
+    of ``--date-runs``:
+
+    1. projection cost: ``select(year(l_shipdate))`` against the same-byte arithmetic projection
+       ``select(l_linenumber + 1)`` over the same rows (4 B + validity read, 5 B written each);
+    2. the Q8 shape - ``sum(CASE WHEN year(o_orderdate) = 1995 ...)`` grouped by
+       ``extract(year FROM o_orderdate)`` over the join - against the same query grouped by a
+       stored int column with as many groups (``l_linenumber``: 7 values, like the 7 order
+       years): the price of the hidden-column route;
+    3. ``WHERE year(l_shipdate) = 1994`` with ``datePartRange.enabled`` true against false."""
+    from hyperspace_amd import Hyperspace, IndexConfig
+    sf = args.date_sf
+    data, _ = _tpch(args, sf)
+    root = os.path.join(args.data_dir, f"cfg_date_fns_sf{sf:g}")
+    shutil.rmtree(root, ignore_errors=True)
+    s = _session(root, args.device, args.buckets)
+    hs = Hyperspace(s)
+    li = s.read.parquet(os.path.join(data, "lineitem"))
+    od = s.read.parquet(os.path.join(data, "orders"))
+    for df, cfg in ((li, IndexConfig("li_shipdate", ["l_shipdate"],
+                                     ["l_discount", "l_quantity", "l_extendedprice"])),
+                    (li, IndexConfig("li_orderkey", ["l_orderkey"],
+                                     ["l_extendedprice", "l_discount", "l_shipdate",
+                                      "l_linenumber"])),
+                    (od, IndexConfig("ord_orderkey", ["o_orderkey"],
+                                     ["o_orderdate", "o_shippriority"]))):
+        _build(hs, df, cfg, args.device)
+    Hyperspace.enable(s)
+    li.createOrReplaceTempView("lineitem")
+    od.createOrReplaceTempView("orders")
+    join = "FROM lineitem JOIN orders ON l_orderkey = o_orderkey"
+    # a projection is timed through an aggregate over it that reads the computed column, so
+    # that no result rows cross to the host: the projection pass is the difference in kind
+    pairs = {
+        "projection": (
+            "SELECT sum(y) s, count(*) n FROM (SELECT year(l_shipdate) y FROM lineitem "
+            "WHERE l_orderkey >= 0)",
+            "SELECT sum(y) s, count(*) n FROM (SELECT l_linenumber + 1 y FROM lineitem "
+            "WHERE l_orderkey >= 0)", {}),
+        "q8_grouped": (
+            f"SELECT extract(year FROM o_orderdate) g, sum(CASE WHEN year(o_orderdate) = 1995 "
+            f"THEN l_extendedprice ELSE 0 END) v, sum(l_extendedprice) t, count(*) n {join} "
+            f"GROUP BY extract(year FROM o_orderdate)",
+            f"SELECT l_linenumber g, sum(CASE WHEN o_orderdate >= DATE '1995-01-01' AND "
+            f"o_orderdate < DATE '1996-01-01' THEN l_extendedprice ELSE 0 END) v, "
+            f"sum(l_extendedprice) t, count(*) n {join} GROUP BY l_linenumber", {}),
+        "year_filter": (
+            "SELECT sum(l_extendedprice * l_discount) r, count(*) n FROM lineitem "
+            "WHERE year(l_shipdate) = 1994",
+            "SELECT sum(l_extendedprice * l_discount) r, count(*) n FROM lineitem "
+            "WHERE year(l_shipdate) = 1994",
+            {"spark.hyperspace.mi.datePartRange.enabled": ("true", "false")}),
+    }
+    be = s.backend()
+    out = {"config": "date_fns", "device": args.device, "sf": sf, "runs": args.date_runs,
+           "notes": {"projection": "a = year(l_shipdate), b = l_linenumber + 1; each timed as "
+                                   "sum / count over the projected column, not a plain select",
+                     "q8_grouped": "a grouped by extract(year FROM o_orderdate) with the CASE "
+                                   "over year(), b grouped by the stored l_linenumber (7 groups "
+                                   "each) with the CASE over a date range",
+                     "year_filter": "a = datePartRange.enabled true, b = false"},
+           "queries": {}}
+
+    def med(ts):
+        return sorted(ts)[len(ts) // 2]
+    for name, (a, b, conf) in pairs.items():
+        def use(i):
+            for k, v in conf.items():
+                s.conf.set(k, v[i])
+        info = []
+        for i, text in enumerate((a, b)):
+            use(i)
+            rows = _rows(s.sql(text))
+            path, why = getattr(be, "last_path", None), getattr(be, "fallback_reason", None)
+            s.conf.set("spark.hyperspace.mi.execution.device", "cpu")
+            ref = _rows(s.sql(text))
+            s.conf.set("spark.hyperspace.mi.execution.device", args.device)
+            info.append((rows, path, why, _close(rows, ref)))
+        ta, tb = [], []
+        for _ in range(max(5, args.date_runs)):        # alternating, one run each
+            use(0)
+            ta.append(_median_ms(lambda: s.sql(a).collect(), 1, args.device))
+            use(1)
+            tb.append(_median_ms(lambda: s.sql(b).collect(), 1, args.device))
+        use(0)
+        out["queries"][name] = {
+            "a_ms": med(ta), "b_ms": med(tb), "ratio": round(med(ta) / med(tb), 3),
+            "a_runs_ms": [round(x, 3) for x in ta], "b_runs_ms": [round(x, 3) for x in tb],
+            "a_path": info[0][1], "b_path": info[1][1],
+            "fallback_reason": info[0][2] or info[1][2],
+            "rows": len(info[0][0]), "match": info[0][3] and info[1][3]}
+    out["match"] = all(r["match"] for r in out["queries"].values())
+    return out
+
+
 CONFIGS = {"csv10k": config_csv10k, "sf10_filter": config_sf10_filter, "hybrid": config_hybrid,
            "q3_3way": config_q3_3way, "tpcds_3way": config_tpcds_3way,
            "streamed": config_streamed, "like": config_like, "case_when": config_case_when,
            "count_distinct": config_count_distinct, "window": config_window,
            "broadcast_join": config_broadcast_join, "data_skipping": config_data_skipping,
-           "zorder": config_zorder}
+           "zorder": config_zorder, "date_fns": config_date_fns}
 
 
 def main():
@@ -1428,6 +1529,10 @@ def main():
                     help="case_when: TPC-H scale factor")
     ap.add_argument("--case-runs", type=int, default=7,
                     help="case_when: alternating timed runs per route (medians reported)")
+    ap.add_argument("--date-sf", type=float, default=10.0,
+                    help="date_fns: TPC-H scale factor")
+    ap.add_argument("--date-runs", type=int, default=7,
+                    help="date_fns: alternating timed runs per query pair (at least 5; medians)")
     ap.add_argument("--probe-sweep", action="store_true",
                     help="broadcast_join: time the hash-join probe kernel alone, per rows per lane")
     ap.add_argument("--ds-runs", type=int, default=5,

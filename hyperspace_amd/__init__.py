@@ -12,12 +12,16 @@ from .index.dataskipping import BloomFilterSketch, DataSkippingIndexConfig, MinM
 from .index.zorder import ZOrderCoveringIndexConfig
 from .session import Session
 from .plan.column import (col, lit, sum_, count, countDistinct, count_distinct, min_, max_,
-                          avg, row_number, rank, dense_rank, when, Window, WindowSpec)
+                          avg, row_number, rank, dense_rank, when, Window, WindowSpec,
+                          year, quarter, month, dayofmonth, dayofyear, dayofweek, weekday,
+                          weekofyear, date_add, date_sub, datediff, add_months, last_day, trunc)
 
 __all__ = ["Hyperspace", "IndexConfig", "DataSkippingIndexConfig", "MinMaxSketch",
            "BloomFilterSketch", "ZOrderCoveringIndexConfig", "Session",
            "HyperspaceException", "NoChangesException",
            "col", "lit", "sum_", "count", "countDistinct", "count_distinct", "min_", "max_",
-           "avg", "row_number", "rank", "dense_rank", "when", "Window", "WindowSpec", "get_context"]
+           "avg", "row_number", "rank", "dense_rank", "when", "Window", "WindowSpec", "get_context",
+           "year", "quarter", "month", "dayofmonth", "dayofyear", "dayofweek", "weekday",
+           "weekofyear", "date_add", "date_sub", "datediff", "add_months", "last_day", "trunc"]
 
 __version__ = "0.1.0"

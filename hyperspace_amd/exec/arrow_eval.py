@@ -149,6 +149,8 @@ def eval_expr(e: E.Expression, t: pa.Table):
                 continue
             out = pc.if_else(pc.fill_null(cond, False), value(v), out)
         return out
+    if isinstance(e, E.DateFunction):
+        return _date_function(e, t)
     if isinstance(e, E.Cast):
         v = eval_expr(e.child, t)
         if _is_num(v.type) and _is_num(e.dtype):
@@ -158,6 +160,101 @@ def eval_expr(e: E.Expression, t: pa.Table):
             return pc.cast(v, e.dtype, safe=False)
         return pc.cast(v, e.dtype)
     raise NotImplementedError(f"cannot evaluate {type(e).__name__}")
+
+
+def _flat(v):
+    return v.combine_chunks() if isinstance(v, pa.ChunkedArray) else v
+
+
+def _date_arg(x: E.Expression, t: pa.Table):
+    """A date argument as a date32 array: a timestamp is its UTC date (floor of the day)."""
+    v = _flat(eval_expr(x, t))
+    if pa.types.is_null(v.type):
+        return pa.nulls(len(v), pa.date32())
+    if pa.types.is_timestamp(v.type):
+        per_day = {"s": 86400, "ms": 86400 * 10 ** 3, "us": 86400 * 10 ** 6,
+                   "ns": 86400 * 10 ** 9}[v.type.unit]
+        ticks = np.asarray(pc.fill_null(v.cast(pa.int64()), 0).to_numpy(zero_copy_only=False))
+        days = np.floor_divide(ticks, per_day).astype(np.int32)
+        return pa.array(days, pa.int32(), mask=_null_mask(v)).cast(pa.date32())
+    return v if pa.types.is_date32(v.type) else pc.cast(v, pa.date32())
+
+
+def _null_mask(*arrays) -> np.ndarray:
+    bad = np.zeros(len(arrays[0]), dtype=bool)
+    for a in arrays:
+        if a.null_count:
+            bad |= np.asarray(pc.is_null(a).to_numpy(zero_copy_only=False))
+    return bad
+
+
+def _days(v) -> np.ndarray:
+    """int32 day numbers of a date32 array (NULLs as 0)."""
+    return np.asarray(pc.fill_null(v.cast(pa.int32()), 0).to_numpy(zero_copy_only=False))
+
+
+def _int_arg(x: E.Expression, t: pa.Table):
+    v = _flat(eval_expr(x, t))
+    if pa.types.is_null(v.type):
+        return pa.nulls(len(v), pa.int32())
+    return pc.cast(v, pa.int32())
+
+
+def _month_start(m: np.ndarray) -> np.ndarray:
+    """Day numbers (int64) of the first days of the ``datetime64[M]`` months ``m``."""
+    return m.astype("datetime64[D]").astype(np.int64)
+
+
+def _date_function(e: E.DateFunction, t: pa.Table):
+    """The date functions: the parts through ``pyarrow.compute``, day arithmetic on int32 day
+    numbers, month arithmetic through numpy ``datetime64[M]`` (pyarrow has no add_months)."""
+    d = _date_arg(e.children[0], t)
+    part = {E.Year: pc.year, E.Quarter: pc.quarter, E.Month: pc.month, E.DayOfMonth: pc.day,
+            E.DayOfYear: pc.day_of_year, E.WeekOfYear: pc.iso_week}.get(type(e))
+    if part is not None:
+        return pc.cast(part(d), pa.int32())
+    if isinstance(e, E.WeekDay):
+        return pc.cast(pc.day_of_week(d), pa.int32())               # Monday = 0
+    if isinstance(e, E.DayOfWeek):
+        wd = pc.cast(pc.day_of_week(d, count_from_zero=False, week_start=7), pa.int32())
+        return wd                                                   # Sunday = 1
+    dn = _days(d)
+    if isinstance(e, (E.DateAdd, E.DateSub, E.AddMonths)):
+        n = _int_arg(e.children[1], t)
+        bad = _null_mask(d, n)
+        nv = np.asarray(pc.fill_null(n, 0).to_numpy(zero_copy_only=False)).astype(np.int32)
+        if not isinstance(e, E.AddMonths):
+            with np.errstate(over="ignore"):
+                out = dn + nv if isinstance(e, E.DateAdd) else dn - nv
+            return pa.array(out.astype(np.int32), pa.int32(), mask=bad).cast(pa.date32())
+        m = dn.astype("datetime64[D]").astype("datetime64[M]")
+        dom = dn.astype(np.int64) - _month_start(m)                 # day of month - 1
+        m2 = m + nv.astype(np.int64)
+        first = _month_start(m2)
+        out = first + np.minimum(dom, _month_start(m2 + 1) - first - 1)
+        return pa.array(out.astype(np.int32), pa.int32(), mask=bad).cast(pa.date32())
+    if isinstance(e, E.DateDiff):
+        s = _date_arg(e.children[1], t)
+        out = dn.astype(np.int64) - _days(s).astype(np.int64)
+        return pa.array(out.astype(np.int32), pa.int32(), mask=_null_mask(d, s))
+    bad = _null_mask(d)
+    m = dn.astype("datetime64[D]").astype("datetime64[M]")
+    if isinstance(e, E.LastDay):
+        out = _month_start(m + 1) - 1
+    else:
+        level = e.level
+        if level is None:
+            return pa.nulls(len(d), pa.date32())
+        if level == "week":
+            out = dn.astype(np.int64) - np.mod(dn.astype(np.int64) + 3, 7)   # 1970-01-01: Thursday
+        elif level == "month":
+            out = _month_start(m)
+        elif level == "quarter":
+            mi = m.astype(np.int64)                                  # months since 1970-01
+            out = _month_start((mi - np.mod(mi, 3)).astype("datetime64[M]"))
+        else:
+            out = m.astype("datetime64[Y]").astype("datetime64[D]").astype(np.int64)
+    return pa.array(out.astype(np.int32), pa.int32(), mask=bad).cast(pa.date32())
 
 
 def _remainder(a, b, n: int, dtype=None):

@@ -205,11 +205,12 @@ def _warm_torch_kernels(device) -> None:
 
 
 def _needs_eval(c: E.Expression) -> bool:
-    """A predicate over computed values (arithmetic, or a cast that changes a column's values):
-    the scan kernels' predicate compiler takes column / literal comparisons (it looks through
-    value-preserving casts only), so such a conjunct is evaluated as a computed column."""
+    """A predicate over computed values (arithmetic, a CASE, a date function, or a cast that
+    changes a column's values): the scan kernels' predicate compiler takes column / literal
+    comparisons (it looks through value-preserving casts only), so such a conjunct is evaluated
+    as a computed column."""
     for x in c.iter_tree():
-        if isinstance(x, (E.BinaryArithmetic, E.CaseWhen)):
+        if isinstance(x, (E.BinaryArithmetic, E.CaseWhen, E.DateFunction)):
             return True
         if isinstance(x, E.Cast) and not isinstance(x.child, E.Literal) and \
                 not _lossless_cast(x.child.data_type, x.dtype):

@@ -16,6 +16,15 @@ Semantics (Spark non-ANSI, and the host oracle ``exec/arrow_eval.py``):
 * casts between numeric types truncate toward zero (integer targets) and wrap;
 * comparisons give booleans; AND / OR / NOT follow three-valued (Kleene) logic;
 * NULL in, NULL out for everything else.
+
+Date functions (``year(d)``, ``date_add(d, n)``, ``add_months``, ``trunc``, ...) read and produce
+dates as int32 day numbers.  Their calendar arithmetic (``DATE_PRELUDE``) is the
+days-from-0000-03-01 form in 32-bit unsigned registers: that count is non-negative for every day
+of 0001-01-01 ... 9999-12-31, so no era branch is needed, every division is by a constant (a
+multiply-high on gfx950, which has no integer divide) and nothing is ever 64 bits wide.  Outside
+that range the result is unspecified but still plain integer arithmetic.  The prelude is appended
+only to kernels that use it, and it is plain C++ (no HIP builtin), so a host compiler can check
+it over every day of the range.
 """
 from __future__ import annotations
 
@@ -37,6 +46,84 @@ _CTYPE = {NL.I8: "signed char", NL.I16: "short", NL.I32: "int", NL.I64: "long lo
 _CMP = {E.EqualTo: "==", E.NotEqual: "!=", E.LessThan: "<", E.LessThanOrEqual: "<=",
         E.GreaterThan: ">", E.GreaterThanOrEqual: ">="}
 _ARITH = {E.Add: "+", E.Subtract: "-", E.Multiply: "*"}
+
+
+DATE_PRELUDE_MARK = "// -- date functions --"
+DATE_PRELUDE = DATE_PRELUDE_MARK + r"""
+// Proleptic Gregorian calendar over int32 day numbers (days since 1970-01-01), exact for
+// 0001-01-01 ... 9999-12-31.  z = days + 719468 counts from 0000-03-01 and is >= 306 there.
+struct HsCivil { unsigned y, m, d; };
+__device__ inline HsCivil hs_civil(int days) {
+  const unsigned z = (unsigned)days + 719468u;
+  const unsigned era = z / 146097u;
+  const unsigned doe = z - era * 146097u;
+  const unsigned yoe = (doe - doe / 1460u + doe / 36524u - doe / 146096u) / 365u;
+  const unsigned doy = doe - (365u * yoe + yoe / 4u - yoe / 100u);
+  const unsigned mp = (5u * doy + 2u) / 153u;
+  HsCivil c;
+  c.d = doy - (153u * mp + 2u) / 5u + 1u;
+  c.m = mp < 10u ? mp + 3u : mp - 9u;
+  c.y = yoe + era * 400u + (c.m <= 2u ? 1u : 0u);
+  return c;
+}
+__device__ inline int hs_days(unsigned y, unsigned m, unsigned d) {
+  y -= m <= 2u ? 1u : 0u;
+  const unsigned era = y / 400u;
+  const unsigned yoe = y - era * 400u;
+  const unsigned doy = (153u * (m > 2u ? m - 3u : m + 9u) + 2u) / 5u + d - 1u;
+  const unsigned doe = yoe * 365u + yoe / 4u - yoe / 100u + doy;
+  return (int)(era * 146097u + doe - 719468u);
+}
+// Monday = 0 ... Sunday = 6 (0000-03-01 is a Wednesday)
+__device__ inline unsigned hs_weekday(int days) { return ((unsigned)days + 719470u) % 7u; }
+__device__ inline int hs_year(int days) { return (int)hs_civil(days).y; }
+__device__ inline int hs_quarter(int days) { return (int)((hs_civil(days).m + 2u) / 3u); }
+__device__ inline int hs_month(int days) { return (int)hs_civil(days).m; }
+__device__ inline int hs_dayofmonth(int days) { return (int)hs_civil(days).d; }
+__device__ inline int hs_dayofyear(int days) {
+  return (int)((unsigned)days - (unsigned)hs_days(hs_civil(days).y, 1u, 1u)) + 1;
+}
+// 1 = Sunday ... 7 = Saturday
+__device__ inline int hs_dayofweek(int days) { return (int)(((unsigned)days + 719471u) % 7u) + 1; }
+// ISO-8601: the week of the year that holds this week's Thursday
+__device__ inline int hs_weekofyear(int days) {
+  const int thu = (int)((unsigned)days - hs_weekday(days) + 3u);
+  const unsigned into = (unsigned)thu - (unsigned)hs_days(hs_civil(thu).y, 1u, 1u);
+  return (int)(into / 7u) + 1;
+}
+__device__ inline int hs_month_first(unsigned y, unsigned m) { return hs_days(y, m, 1u); }
+__device__ inline int hs_next_month_first(unsigned y, unsigned m) {
+  return m == 12u ? hs_days(y + 1u, 1u, 1u) : hs_days(y, m + 1u, 1u);
+}
+__device__ inline int hs_last_day(int days) {
+  const HsCivil c = hs_civil(days);
+  return (int)((unsigned)hs_next_month_first(c.y, c.m) - 1u);
+}
+// Spark 3: the day of month is kept, clamped to the target month's length
+__device__ inline int hs_add_months(int days, int n) {
+  const HsCivil c = hs_civil(days);
+  const unsigned total = c.y * 12u + (c.m - 1u) + (unsigned)n;
+  const unsigned y = total / 12u;
+  const unsigned m = total - y * 12u + 1u;
+  const unsigned first = (unsigned)hs_month_first(y, m);
+  const unsigned len = (unsigned)hs_next_month_first(y, m) - first;
+  return (int)(first + (c.d < len ? c.d : len) - 1u);
+}
+__device__ inline int hs_trunc_year(int days) { return hs_days(hs_civil(days).y, 1u, 1u); }
+__device__ inline int hs_trunc_quarter(int days) {
+  const HsCivil c = hs_civil(days);
+  return hs_days(c.y, (c.m - 1u) / 3u * 3u + 1u, 1u);
+}
+__device__ inline int hs_trunc_month(int days) {
+  return (int)((unsigned)days - hs_civil(days).d + 1u);
+}
+__device__ inline int hs_trunc_week(int days) { return (int)((unsigned)days - hs_weekday(days)); }
+"""
+
+_DATE_PART = {E.Year: "hs_year", E.Quarter: "hs_quarter", E.Month: "hs_month",
+              E.DayOfMonth: "hs_dayofmonth", E.DayOfYear: "hs_dayofyear",
+              E.DayOfWeek: "hs_dayofweek", E.WeekOfYear: "hs_weekofyear",
+              E.LastDay: "hs_last_day"}
 
 
 def _kind(t: pa.DataType) -> str:
@@ -92,6 +179,8 @@ class _Gen:
         self.shape: List[object] = []
         self.n = 0
         self.in_case = 0            # depth of CaseWhen nodes around the node being emitted
+        self.uses_dates = False     # a date function was emitted: the kernel needs DATE_PRELUDE
+        self.date_exprs = False     # the output expression being emitted holds a date function
 
     def _var(self) -> str:
         self.n += 1
@@ -203,6 +292,71 @@ class _Gen:
         self.lines.append(f"const bool {ok} = {oke};")
         return v, ok, rk
 
+    def date_function(self, e: E.DateFunction) -> Tuple[str, str, str]:
+        """A date function over day numbers: every argument is narrowed to ``int`` once, the
+        calendar arithmetic of ``DATE_PRELUDE`` runs in 32 bits, and the result widens back to
+        the kernel's ``long long`` value convention.  Integer arguments (``n`` of date_add /
+        add_months) are ordinary operands: a literal is a kernel argument."""
+        self.uses_dates = True
+        args = []
+        for i, x in enumerate(e.children):
+            if i in e.DATES:
+                t = x.data_type
+                if pa.types.is_timestamp(t):
+                    raise Unsupported(f"timestamp argument of {e.name}()")
+                if not (pa.types.is_date32(t) or pa.types.is_null(t)):
+                    raise Unsupported(f"{t} argument of {e.name}()")
+            v, ok, k = self.operand(x, True)
+            if k != "i":
+                raise Unsupported(f"argument {x.sql()} of {e.name}()")
+            args.append((f"(int){v}", ok))
+        v, ok = self._var(), self._var()
+        valid = " && ".join(o for _, o in args)
+        a = args[0][0]
+        if type(e) in _DATE_PART:
+            expr = f"{_DATE_PART[type(e)]}({a})"
+        elif isinstance(e, E.WeekDay):
+            expr = f"(int)hs_weekday({a})"
+        elif isinstance(e, E.DateAdd):
+            expr = f"(int)((unsigned){a} + (unsigned){args[1][0]})"
+        elif isinstance(e, (E.DateSub, E.DateDiff)):
+            expr = f"(int)((unsigned){a} - (unsigned){args[1][0]})"
+        elif isinstance(e, E.AddMonths):
+            expr = f"hs_add_months({a}, {args[1][0]})"
+        elif isinstance(e, E.TruncDate):
+            level = e.level
+            self.shape.append(("trunc", level))
+            if level is None:
+                expr, valid = "0", "false"
+            else:
+                expr = f"hs_trunc_{level}({a})"
+        else:
+            raise Unsupported(f"computed projection of {type(e).__name__}")
+        self.lines.append(f"const bool {ok} = {valid};")
+        self.lines.append(f"const long long {v} = (long long)({expr});")
+        return v, ok, "i"
+
+    def in_list(self, e: E.In) -> Tuple[str, str, str]:
+        """``x IN (literals)`` over an integral value: TRUE on a match, else NULL when ``x`` or
+        a list entry is NULL, else FALSE."""
+        a, av, ak = self.emit(e.value)
+        if ak != "i" or not all(isinstance(x, E.Literal) for x in e.values):
+            raise Unsupported("IN over a value that is not integral, or a list of non-literals")
+        hits, nulls = [], False
+        for x in e.values:
+            if x.value is None:
+                nulls = True
+                continue
+            b, _, bk = self.lit(x)
+            if bk != "i":
+                raise Unsupported("IN list entry that is not an integer")
+            hits.append(f"{a} == {b}")
+        self.shape.append(("in", len(hits), nulls))
+        v, ok = self._var(), self._var()
+        self.lines.append(f"const bool {v} = {av} && ({' || '.join(hits) if hits else 'false'});")
+        self.lines.append(f"const bool {ok} = {av} && ({v} || {'false' if nulls else 'true'});")
+        return v, ok, "b"
+
     def emit(self, e: E.Expression) -> Tuple[str, str, str]:
         if isinstance(e, E.Alias):
             return self.emit(e.child)
@@ -213,8 +367,11 @@ class _Gen:
         self.shape.append(type(e).__name__)
         if isinstance(e, E.CaseWhen):
             return self.case_when(e)
-        if self.in_case and type(e) in _CMP and _date_compare(e):
-            # inside a CASE (a WHERE conjunct on dates alone never comes here): day numbers
+        if isinstance(e, E.DateFunction):
+            return self.date_function(e)
+        if (self.in_case or self.date_exprs) and type(e) in _CMP and _date_compare(e):
+            # inside a CASE, or in an expression that holds a date function (a WHERE conjunct
+            # on dates alone never comes here): day numbers
             (a, av, ak), (b, bv, bk) = self.operand(e.left, True), self.operand(e.right, True)
             v, ok = self._var(), self._var()
             self.lines.append(f"const bool {ok} = {av} && {bv};")
@@ -271,6 +428,11 @@ class _Gen:
                                   f"({bv} && {b});")
                 self.lines.append(f"const bool {v} = ({av} && {a}) || ({bv} && {b});")
             return v, ok, "b"
+        if isinstance(e, E.In):
+            return self.in_list(e)
+        if isinstance(e, E.InSet):
+            # OptimizeIn's form of a long literal list
+            return self.in_list(E.In(e.value, [E.Literal(x) for x in sorted(e.hset, key=repr)]))
         if isinstance(e, E.Not):
             a, av, ak = self.emit(e.child)
             if ak != "b":
@@ -331,6 +493,7 @@ def build(exprs: List[E.Expression], cols: Dict[int, DeviceColumn], n: int, devi
         t = e.data_type
         if pa.types.is_integer(t) and e.data_type.bit_width > 64:
             raise Unsupported("wide integer result")
+        g.date_exprs = E.contains_date_function(e)
         v, ok, k = g.emit(e)
         tdt, ct = _out_storage(t)
         if (k == "b") != pa.types.is_boolean(t):
@@ -354,7 +517,7 @@ def build(exprs: List[E.Expression], cols: Dict[int, DeviceColumn], n: int, devi
     shape = ("project", tuple(map(str, g.shape)), tuple(s for _, s, _ in g.args.slots))
 
     def make():
-        src = (jit._PRELUDE + g.args.struct_src() +
+        src = (jit._PRELUDE + (DATE_PRELUDE if g.uses_dates else "") + g.args.struct_src() +
                f'extern "C" __global__ __launch_bounds__({BLOCK}) void hs_jit_project(Args a) {{\n'
                + "\n".join(body) + "\n}\n")
         return jit.Kernel(src, "hs_jit_project", g.args, 0, BLOCK)

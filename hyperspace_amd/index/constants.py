@@ -119,6 +119,10 @@ JOIN_GRAPH_ENABLED_DEFAULT = "true"
 # scan / join aggregate kernels; false: the CASE is computed as a hidden column first
 COND_AGG_FUSED = "spark.hyperspace.mi.condAgg.fused"
 COND_AGG_FUSED_DEFAULT = "true"
+# the optimizer rewrites year(date column) <cmp> literal into a range on the column, so an index
+# on it serves the filter (plan/optimizer.py date_part_range)
+DATE_PART_RANGE_ENABLED = "spark.hyperspace.mi.datePartRange.enabled"
+DATE_PART_RANGE_ENABLED_DEFAULT = "true"
 # plan-cache hits of a fused aggregate with a known literal vector replay the prepared
 # lowering directly (exec/gpu.py _AggProgram), skipping the executor's plan walk
 PREPARED_SUBMIT_ENABLED = "spark.hyperspace.mi.preparedSubmit.enabled"

@@ -671,6 +671,251 @@ def references_outside_case(e: Expression) -> List["Attribute"]:
 
 
 # ---------------------------------------------------------------------------------------------
+# Date functions
+# ---------------------------------------------------------------------------------------------
+_EPOCH = datetime.date(1970, 1, 1)
+
+
+def _as_date(v):
+    """The date a literal value stands for where a date is expected: a date, a timestamp (its
+    UTC date) or a string that reads as one; None when it is none of these."""
+    if isinstance(v, datetime.datetime):
+        if v.tzinfo is not None:
+            v = v.astimezone(datetime.timezone.utc)
+        return v.date()
+    if isinstance(v, datetime.date):
+        return v
+    if isinstance(v, str):
+        try:
+            return datetime.date.fromisoformat(v.strip()[:10])
+        except ValueError:
+            return None
+    return None
+
+
+class DateFunction(Expression):
+    """A scalar function over dates with Spark 3's typing and NULL rules (NULL in, NULL out).
+    ``DATES`` / ``INTS`` name the argument positions that take a date and an integer.  A date
+    argument is a ``date32`` expression, a timestamp expression (taken as its UTC date: session
+    time zones are not modelled) or a string literal that reads as a date, which becomes a date
+    literal here, as the analyzer reads ``l_shipdate >= '1994-01-01'``.  The calendar is the
+    proleptic Gregorian one; the contract covers 0001-01-01 ... 9999-12-31 for inputs and results.
+
+    The nodes hold their children only (``TruncDate``: and ``fmt``), so every literal argument
+    is an ordinary ``Literal`` child that the plan cache parameterises.  Build them through
+    ``date_function``, which folds a call over literals."""
+    name = "?"
+    DATES: tuple = (0,)
+    INTS: tuple = ()
+    RESULT = "int"
+
+    def __init__(self, *children):
+        if len(children) != len(self.DATES) + len(self.INTS):
+            raise TypeError(f"{self.name}() takes {len(self.DATES) + len(self.INTS)} arguments")
+        self.children = tuple(self._checked(i, c) for i, c in enumerate(children))
+
+    def _checked(self, i: int, c: Expression) -> Expression:
+        """Argument ``i`` once its type is known (resolution rebuilds the node over resolved
+        children): a string literal in a date position as a date literal; a type the function
+        does not take is an analysis error."""
+        try:
+            t = c.data_type
+        except ValueError:          # an unresolved attribute below: checked once it is resolved
+            return c
+        if pa.types.is_null(t):
+            return c
+        if i in self.DATES:
+            if isinstance(c, Literal) and isinstance(c.value, str):
+                d = _as_date(c.value)
+                return Literal(d, pa.date32())      # (not a date: NULL, as in Spark)
+            if pa.types.is_date32(t) or pa.types.is_timestamp(t):
+                return c
+            want = "a date"
+        else:
+            if pa.types.is_signed_integer(t) and t.bit_width <= 32:
+                return c
+            want = "an int"
+        from ..exceptions import HyperspaceException
+        raise HyperspaceException(
+            f"cannot resolve '{self.name}(...)' due to data type mismatch: argument {i + 1} "
+            f"({c.sql()}) of {self.name}() requires {want}, not {t}")
+
+    def with_children(self, children):
+        return type(self)(*children)
+
+    @property
+    def data_type(self):
+        return pa.date32() if self.RESULT == "date" else pa.int32()
+
+    def sql(self):
+        return f"{self.name}({', '.join(c.sql() for c in self.children)})"
+
+    # the value for plain Python arguments (dates as datetime.date): folding and documentation
+    @staticmethod
+    def compute(*args):
+        raise NotImplementedError
+
+
+def _month_len(y: int, m: int) -> int:
+    import calendar
+    return calendar.monthrange(y, m)[1]
+
+
+def _add_months(d: datetime.date, n: int) -> datetime.date:
+    y, m = divmod(d.year * 12 + d.month - 1 + n, 12)
+    return datetime.date(y, m + 1, min(d.day, _month_len(y, m + 1)))
+
+
+class Year(DateFunction):
+    name = "year"
+    compute = staticmethod(lambda d: d.year)
+
+
+class Quarter(DateFunction):
+    name = "quarter"
+    compute = staticmethod(lambda d: (d.month + 2) // 3)
+
+
+class Month(DateFunction):
+    name = "month"
+    compute = staticmethod(lambda d: d.month)
+
+
+class DayOfMonth(DateFunction):
+    name = "dayofmonth"
+    compute = staticmethod(lambda d: d.day)
+
+
+class DayOfYear(DateFunction):
+    name = "dayofyear"
+    compute = staticmethod(lambda d: d.timetuple().tm_yday)
+
+
+class DayOfWeek(DateFunction):
+    """1 = Sunday ... 7 = Saturday."""
+    name = "dayofweek"
+    compute = staticmethod(lambda d: (d.weekday() + 1) % 7 + 1)
+
+
+class WeekDay(DateFunction):
+    """0 = Monday ... 6 = Sunday."""
+    name = "weekday"
+    compute = staticmethod(lambda d: d.weekday())
+
+
+class WeekOfYear(DateFunction):
+    """The ISO-8601 week: weeks start on Monday, week 1 holds the year's first Thursday."""
+    name = "weekofyear"
+    compute = staticmethod(lambda d: d.isocalendar()[1])
+
+
+class DateAdd(DateFunction):
+    name, INTS, RESULT = "date_add", (1,), "date"
+    compute = staticmethod(lambda d, n: d + datetime.timedelta(days=n))
+
+
+class DateSub(DateFunction):
+    name, INTS, RESULT = "date_sub", (1,), "date"
+    compute = staticmethod(lambda d, n: d - datetime.timedelta(days=n))
+
+
+class DateDiff(DateFunction):
+    """``datediff(end, start)``: the days from ``start`` to ``end``."""
+    name, DATES = "datediff", (0, 1)
+    compute = staticmethod(lambda end, start: (end - start).days)
+
+
+class AddMonths(DateFunction):
+    """Spark 3: the day of month is kept and clamped to the target month's length; a month's
+    last day is not snapped to the target's last day."""
+    name, INTS, RESULT = "add_months", (1,), "date"
+    compute = staticmethod(_add_months)
+
+
+class LastDay(DateFunction):
+    name, RESULT = "last_day", "date"
+    compute = staticmethod(lambda d: d.replace(day=_month_len(d.year, d.month)))
+
+
+TRUNC_LEVELS = {"year": "year", "yyyy": "year", "yy": "year", "quarter": "quarter",
+                "month": "month", "mon": "month", "mm": "month", "week": "week"}
+
+
+def _trunc(d: datetime.date, level):
+    if level == "year":
+        return d.replace(month=1, day=1)
+    if level == "quarter":
+        return d.replace(month=(d.month - 1) // 3 * 3 + 1, day=1)
+    if level == "month":
+        return d.replace(day=1)
+    if level == "week":
+        return d - datetime.timedelta(days=d.weekday())
+    return None
+
+
+class TruncDate(DateFunction):
+    """``trunc(d, fmt)``: the first day of ``d``'s year / quarter / month, or the Monday of its
+    week; ``fmt`` (a plain field: a part of the plan's shape) is compared without case, and one
+    that names none of these gives NULL, as in Spark."""
+    name, RESULT = "trunc", "date"
+
+    def __init__(self, child, fmt: str):
+        if not isinstance(fmt, str):
+            raise TypeError(f"trunc() takes a string literal format, got {fmt!r}")
+        self.fmt = fmt
+        super().__init__(child)
+
+    @property
+    def level(self):
+        """'year' | 'quarter' | 'month' | 'week', or None for an unknown format."""
+        return TRUNC_LEVELS.get(self.fmt.lower())
+
+    def with_children(self, children):
+        return TruncDate(children[0], self.fmt)
+
+    @property
+    def nullable(self):
+        return self.level is None or self.children[0].nullable
+
+    def canonical_key(self):
+        return ("TruncDate", self.fmt.lower(), self.children[0].canonical_key())
+
+    def sql(self):
+        return f"trunc({self.children[0].sql()}, {self.fmt})"
+
+    def compute(self, d):
+        return _trunc(d, self.level)
+
+
+DATE_FUNCTIONS = {c.name: c for c in (Year, Quarter, Month, DayOfMonth, DayOfYear, DayOfWeek,
+                                      WeekDay, WeekOfYear, DateAdd, DateSub, DateDiff, AddMonths,
+                                      LastDay, TruncDate)}
+DATE_FUNCTIONS["day"] = DayOfMonth
+
+
+def date_function(name: str, *args) -> Expression:
+    """The date function ``name`` over ``args`` (``trunc``: the date and the format string).
+    A call whose arguments are all non-NULL literals is folded here, at construction, into its
+    ``Literal``: ``DATE '1998-12-01' - INTERVAL '90' DAY`` is a date literal before the plan is
+    fingerprinted, so the plan cache parameterises it and the index rules see a plain
+    column / literal comparison.  (A result outside 0001 ... 9999 is left unfolded.)"""
+    node = DATE_FUNCTIONS[name.lower()](*args)
+    if not all(isinstance(c, Literal) and c.value is not None for c in node.children):
+        return node
+    vals = [_as_date(c.value) if i in node.DATES else c.value
+            for i, c in enumerate(node.children)]
+    try:
+        out = node.compute(*vals)
+    except (OverflowError, ValueError):
+        return node
+    return Literal(out, node.data_type)
+
+
+def contains_date_function(e: Expression) -> bool:
+    return any(isinstance(x, DateFunction) for x in e.iter_tree())
+
+
+# ---------------------------------------------------------------------------------------------
 # Aggregates
 # ---------------------------------------------------------------------------------------------
 class AggregateFunction(Expression):

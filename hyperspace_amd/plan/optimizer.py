@@ -7,6 +7,7 @@ from __future__ import annotations
 
 from typing import List
 
+from ..utils.conf import HyperspaceConf
 from . import expressions as E
 from . import logical as L
 
@@ -258,6 +259,62 @@ def optimize_in(plan, threshold: int = IN_SET_THRESHOLD_DEFAULT):
     return plan.transform_up(fn)
 
 
+_YEAR_MIN, _YEAR_MAX = 1, 9998
+
+
+def date_part_range(plan):
+    """``year(c) <cmp> y`` in a Filter becomes a range on ``c``, so that FilterIndexRule, the
+    index range search and the fused scan serve the query and no computed pass runs:
+
+    * ``year(c) = y``  ->  ``c >= y-01-01 AND c < (y+1)-01-01``
+    * ``year(c) < y``  ->  ``c < y-01-01``;   ``year(c) <= y``  ->  ``c < (y+1)-01-01``
+    * ``year(c) > y``  ->  ``c >= (y+1)-01-01``;   ``year(c) >= y``  ->  ``c >= y-01-01``
+
+    and the flipped forms ``y <cmp> year(c)``.  ``c`` is a bare date32 attribute, ``y`` an integer
+    literal with 1 <= y <= 9998; anything else (``!=``, IN, other functions, other years) is left
+    alone.  Both sides are NULL exactly when ``c`` is, so the rewrite holds anywhere in the
+    predicate, under OR and NOT too.
+
+    The date literals made here do not come from the query, so the plan cache cannot
+    parameterise such a plan: its ``uncacheable`` counter rises and the query is planned each
+    time, which is correct by construction."""
+    import datetime
+    import pyarrow as pa
+
+    def jan1(y):
+        return E.Literal(datetime.date(y, 1, 1), pa.date32())
+
+    def efn(x):
+        if type(x) not in (E.EqualTo, E.LessThan, E.LessThanOrEqual, E.GreaterThan,
+                           E.GreaterThanOrEqual):
+            return None
+        cls, l, r = type(x), x.left, x.right
+        if isinstance(r, E.Year):
+            cls, l, r = E.FLIP[cls], r, l
+        if not (isinstance(l, E.Year) and isinstance(l.children[0], E.Attribute) and
+                pa.types.is_date32(l.children[0].data_type) and isinstance(r, E.Literal) and
+                isinstance(r.value, int) and not isinstance(r.value, bool) and
+                _YEAR_MIN <= r.value <= _YEAR_MAX):
+            return None
+        c, y = l.children[0], r.value
+        if cls is E.EqualTo:
+            return E.And(E.GreaterThanOrEqual(c, jan1(y)), E.LessThan(c, jan1(y + 1)))
+        if cls is E.LessThan:
+            return E.LessThan(c, jan1(y))
+        if cls is E.LessThanOrEqual:
+            return E.LessThan(c, jan1(y + 1))
+        if cls is E.GreaterThan:
+            return E.GreaterThanOrEqual(c, jan1(y + 1))
+        return E.GreaterThanOrEqual(c, jan1(y))
+
+    def fn(p):
+        if isinstance(p, L.Filter):
+            c2 = p.condition.transform_up(efn)
+            return None if c2 is p.condition else L.Filter(c2, p.child)
+        return None
+    return plan.transform_up(fn)
+
+
 def optimize_in_plan(plan):
     return optimize_in(plan)
 
@@ -269,6 +326,8 @@ class Optimizer:
     def base_batches(self, plan):
         from ..index import constants as C
         thr = int(self.session.conf.get(C.SQL_IN_SET_CONVERSION_THRESHOLD, "10"))
+        if HyperspaceConf.date_part_range_enabled(self.session.conf):
+            plan = date_part_range(plan)
         # fixed point by identity: every rule returns the very same tree when it changes nothing
         for _ in range(10):
             before = plan

@@ -5,7 +5,10 @@ additive, multiplicative, unary minus, primary (literal, column, function call w
 ``OVER ([PARTITION BY e, ...] [ORDER BY e [ASC|DESC], ...])``, parenthesised,
 ``CASE [x] WHEN c THEN v ... [ELSE e] END``).  ``if(c, a, b)``, ``coalesce(a, b, ...)`` and
 ``nullif(a, b)`` build the same ``CaseWhen``; CASE / WHEN / THEN / ELSE / END are recognised by
-position, so columns of those names keep parsing.
+position, so columns of those names keep parsing.  The date functions (``year(d)``,
+``date_add(d, n)``, ...), ``EXTRACT(field FROM e)`` and ``d + INTERVAL '<n>' DAY|MONTH|YEAR`` build
+``E.DateFunction`` nodes (folded when every argument is a literal); EXTRACT, FROM and INTERVAL are
+recognised by position too, and an interval is only an operand of a date's ``+`` / ``-``.
 Produces expressions with ``UnresolvedAttribute`` leaves; the DataFrame resolves them.
 """
 from __future__ import annotations
@@ -78,7 +81,9 @@ class _Parser:
         self.i = 0
 
     def peek(self, k=0):
-        return self.toks[self.i + k]
+        # a look-ahead past the end sees the end marker (the last token)
+        j = self.i + k
+        return self.toks[j] if j < len(self.toks) else self.toks[-1]
 
     def take(self):
         t = self.toks[self.i]
@@ -163,27 +168,50 @@ class _Parser:
         e = self.multiplicative()
         while True:
             if self.accept("op", "+"):
-                e = E.Add(e, self.multiplicative())
+                e = self._add(e, self.multiplicative(), False)
             elif self.accept("op", "-"):
-                e = E.Subtract(e, self.multiplicative())
+                e = self._add(e, self.multiplicative(), True)
             else:
+                if isinstance(e, _Interval):
+                    raise _interval_error()
                 return e
+
+    @staticmethod
+    def _add(l, r, minus: bool):
+        """``l + r`` / ``l - r``; an INTERVAL operand lowers to date_add / add_months of the
+        other operand (``d + i``, ``d - i``, ``i + d``)."""
+        li, ri = isinstance(l, _Interval), isinstance(r, _Interval)
+        if not (li or ri):
+            return E.Subtract(l, r) if minus else E.Add(l, r)
+        if (li and ri) or (li and minus):
+            raise _interval_error()
+        d, i = (r, l) if li else (l, r)
+        n = -i.n if minus else i.n
+        if i.unit == "DAY":
+            return E.date_function("date_add", d, E.Literal(n))
+        return E.date_function("add_months", d, E.Literal(n * (12 if i.unit == "YEAR" else 1)))
 
     def multiplicative(self):
         e = self.unary()
         while True:
             if self.accept("op", "*"):
-                e = E.Multiply(e, self.unary())
+                cls = E.Multiply
             elif self.accept("op", "/"):
-                e = E.Divide(e, self.unary())
+                cls = E.Divide
             elif self.accept("op", "%"):
-                e = E.Remainder(e, self.unary())
+                cls = E.Remainder
             else:
                 return e
+            r = self.unary()
+            if isinstance(e, _Interval) or isinstance(r, _Interval):
+                raise _interval_error()
+            e = cls(e, r)
 
     def unary(self):
         if self.accept("op", "-"):
             inner = self.unary()
+            if isinstance(inner, _Interval):
+                raise _interval_error()
             if isinstance(inner, E.Literal) and isinstance(inner.value, (int, float)):
                 return E.Literal(-inner.value)
             return E.Subtract(E.Literal(0), inner)
@@ -229,6 +257,13 @@ class _Parser:
                     if searched:
                         raise
                     self.i = save
+            if text.upper() == "INTERVAL":
+                iv = self._interval()
+                if iv is not None:
+                    return iv
+            if text.upper() == "EXTRACT" and self.peek() == ("op", "(") and \
+                    self.peek(1)[0] in ("id", "kw") and self.word("FROM", 2):
+                return self.extract()
             if self.peek() == ("op", "("):
                 return self.over(self.call(text))
             return E.UnresolvedAttribute(text)
@@ -264,6 +299,40 @@ class _Parser:
         if not self.accept_word("END"):
             raise SyntaxError(f"expected END of CASE, got {self.peek()[1]!r}")
         return E.CaseWhen(branches, else_value)
+
+    # -- EXTRACT(field FROM e), INTERVAL '<n>' unit -----------------------------------------------
+    def extract(self):
+        """After the word EXTRACT, at its parenthesis; FROM is a word of this position only."""
+        self.take()
+        field = self.take()[1]
+        self.take()
+        e = self.or_expr()
+        self.expect("op", ")")
+        fn = _EXTRACT_FIELDS.get(field.upper())
+        if fn is None:
+            raise SyntaxError(f"unknown EXTRACT field {field}: EXTRACT takes one of "
+                              f"{', '.join(_EXTRACT_FIELDS)}")
+        return E.date_function(fn, e)
+
+    def _interval(self):
+        """After the word INTERVAL: the interval marker when a quoted or numeric literal and a
+        unit word follow, else None (a column of that name)."""
+        k, neg = 0, False
+        if self.peek() == ("op", "-") and self.peek(1)[0] == "num":
+            k, neg = 1, True
+        kind, text = self.peek(k)
+        unit = self.peek(k + 1)
+        if kind not in ("str", "num") or unit[0] not in ("id", "kw") or unit[1] is None or \
+                unit[1].upper() not in _INTERVAL_UNITS:
+            return None
+        body = text[1:-1].strip() if kind == "str" else text
+        try:
+            n = int(body)
+        except ValueError:
+            raise SyntaxError(f"INTERVAL takes a whole number of days, months or years, "
+                              f"got {text}") from None
+        self.i += k + 2
+        return _Interval(-n if neg else n, _INTERVAL_UNITS[unit[1].upper()])
 
     def _starts_operand(self, k: int) -> bool:
         t = self.peek(k)
@@ -349,6 +418,37 @@ class _Parser:
         return make_function(text, args)
 
 
+_EXTRACT_FIELDS = {"YEAR": "year", "QUARTER": "quarter", "MONTH": "month", "WEEK": "weekofyear",
+                   "DAY": "dayofmonth", "DOW": "dayofweek", "DAYOFWEEK": "dayofweek",
+                   "DOY": "dayofyear"}
+_INTERVAL_UNITS = {"DAY": "DAY", "DAYS": "DAY", "MONTH": "MONTH", "MONTHS": "MONTH",
+                   "YEAR": "YEAR", "YEARS": "YEAR"}
+
+
+class _Interval(E.LeafExpression):
+    """Parser-private marker of ``INTERVAL '<n>' unit``: only ever an operand of the additive
+    rule, which lowers it; no interval type enters a plan."""
+
+    def __init__(self, n: int, unit: str):
+        self.n, self.unit = n, unit
+
+    def sql(self):
+        return f"INTERVAL '{self.n}' {self.unit}"
+
+
+def _interval_error():
+    return SyntaxError("an INTERVAL is only accepted as an operand of + or - whose other "
+                       "operand is a date: d + INTERVAL '1' MONTH, d - INTERVAL '90' DAY, "
+                       "INTERVAL '1' YEAR + d")
+
+
+_DATE_ARITY = {"date_add": ("two", "date_add(date, days)"),
+               "date_sub": ("two", "date_sub(date, days)"),
+               "datediff": ("two", "datediff(end, start)"),
+               "add_months": ("two", "add_months(date, months)"),
+               "trunc": ("two", "trunc(date, format)")}
+
+
 def make_function(name: str, args, distinct: bool = False):
     n = name.lower()
     if distinct:
@@ -386,6 +486,20 @@ def make_function(name: str, args, distinct: bool = False):
         if args:
             raise SyntaxError(f"{n}() takes no arguments")
         return ranking[n]()
+    if n in E.DATE_FUNCTIONS:
+        count, usage = _DATE_ARITY.get(n, ("one", f"{n}(date)"))
+        if len(args) != (2 if count == "two" else 1):
+            raise SyntaxError(f"{n}() takes {count} argument{'s' if count == 'two' else ''}: "
+                              f"{usage}")
+        if any(isinstance(a, _Interval) for a in args):
+            raise _interval_error()
+        if n == "trunc":
+            fmt = args[1]
+            if not (isinstance(fmt, E.Literal) and isinstance(fmt.value, str)):
+                raise SyntaxError("trunc() takes a string literal as its format: "
+                                  "trunc(date, 'month')")
+            return E.date_function(n, args[0], fmt.value)
+        return E.date_function(n, *args)
     raise SyntaxError(f"unknown function {name}")
 
 

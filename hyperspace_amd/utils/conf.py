@@ -127,6 +127,10 @@ class HyperspaceConf:
         return _b(conf.get(C.CODEGEN_ENABLED, C.CODEGEN_ENABLED_DEFAULT))
 
     @staticmethod
+    def date_part_range_enabled(conf) -> bool:
+        return _b(conf.get(C.DATE_PART_RANGE_ENABLED, C.DATE_PART_RANGE_ENABLED_DEFAULT))
+
+    @staticmethod
     def cond_agg_fused(conf) -> bool:
         return _b(conf.get(C.COND_AGG_FUSED, C.COND_AGG_FUSED_DEFAULT))
 
