@@ -289,224 +289,260 @@ def _tags_grouped(p: NL.JoinParams) -> bool:
     return p.group_col >= SPLIT and p.num_groups > 1
 
 
-def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
-                  mode: str = "", prune: tuple = (), k16: bool = False,
-                  pair: bool = False) -> J.Kernel:
-    """Phase 1, direct form: no tiles and no LDS.  Each wavefront owns a contiguous chunk of
-    64-run groups of the left run list (so it owns whole 2W-word stretches of the tag bitmap
-    and stores them without atomics).  Lane l of a group guesses the right row of its run: the
-    previous group's last match + 1 + l (or, at a range start, the range-relative position) -
-    exact for a foreign key whose every right key has left rows, the common case - and verifies
-    it with one compare of the 32-bit key images; a mismatch gallops from the guess to the
-    lower bound (exact for any sorted unique right keys).  The right predicate and group
-    columns are loaded at the guess together with the key, so a verified guess costs one round
-    trip; RT2_UNROLL groups are in flight per iteration.
+def _kernel(name: str, args: J.Args, body: List[str], lds: int = 0, tdefs=(),
+            attrs: str = "") -> J.Kernel:
+    """A generated kernel's translation unit: prelude, the ``Args`` struct as it stands now (so
+    after the last slot was added), file-scope typedefs, and ``body`` as the kernel function."""
+    src = (J._PRELUDE + args.struct_src() + "".join(t + "\n" for t in tdefs) +
+           f'extern "C" __global__ __launch_bounds__({J.BLOCK}){attrs} void {name}(Args a) {{\n' +
+           "\n".join(body) + "\n}\n")
+    return J.Kernel(src, name, args, lds)
 
-    Ranges (``RNG``, NRG x 4 int64, sorted by first run): [first run, end run) of each left row
-    range and the right bucket's rows [s0, s1).  (16-bit grouped run keys measured 0.59 vs
-    0.29 ms - more dependent loads per run - and a per-tile LDS form 0.79 ms: both removed.)
+
+# Which phase-1 kernel is generated, resolved once (``_tags_form``): its name; the run /
+# right-row index type IX; tag bits W with MASK and L, the lanes whose 4 tags share one 32-bit word
+# in the four-run form; runs per lane ``wide`` (``tags2_wide``); U, the 64-run groups per iteration
+# or 256-run blocks per pipeline stage; whether it records the match (``rec``), reads a recorded
+# match (``match``) or per-run column copies (``copy``), compares 16-bit key halves (``lo16``) or
+# prepares them (``prep``); ``k16`` / ``pair``; whether the tags carry a right-side group code
+# (``rgroup``) and the right key is stored grouped (``rkg``); the right columns read at a matched
+# row; and per pre-filter conjunct (bound array slot, literal slot, comparison).
+_TagsForm = collections.namedtuple(
+    "_TagsForm", "name IX W MASK L wide U rec match copy lo16 prep k16 pair rgroup rkg "
+                 "stage_slots bounds")
+
+
+def _tags_form(p: NL.JoinParams, compacts, W: int, ix32: bool, mode: str, prune: tuple,
+               k16: bool, pair: bool) -> _TagsForm:
+    """The form of ``gen_run_tags2``'s arguments under the bound tunables, and every check that
+    the combination exists.  The only place that looks at ``mode``.
 
     ``ix32``: run and right-row indices fit int32 (the lowering checks the table sizes), so the
     index arithmetic, range clamps and gallop run in 32-bit registers and the column loads
     address through a scalar base plus a 32-bit lane offset - the 64-bit index math was most of
-    the kernel's VALU instructions (``profiles/pmc_query_kernels_sf100_r6.txt``).
-
-    ``mode``: "rec" also stores each run's matched right row (or -1) into ``MOUT``; "match"
-    reads that record (``MATCH``, one int32 per run, -1 padded to whole 64-run groups) instead of
-    the left run keys, the right key images and the range table - it depends only on the
-    lowering's ranges and the key columns, not on the literals (``record_matches``).
-
-    Four runs per lane (``tags2_wide``; modes "" and "rec"): the chunk is counted in 256-run
-    blocks, lane l owning runs 256 b + 4 l .. + 3.  A block whose runs all lie in one range and
-    below NRUNS, and whose 256 guessed right rows lie in [s0, s1), is *fast*: one 16-byte load
-    of the lane's 4 left keys, one element-aligned 4-element load of the right key and of each
-    staged right column at the guess, four compares, and a miss gallops per run as above.  The
-    guess of the stage after the current one assumes every run matches (current base + its
-    runs), so its loads are issued before the current stage is resolved - two register sets,
-    the loop unrolled by two so neither is copied; the resolved base (last match + 1) replaces
-    the assumption for the stage after that.  Every other block (a range edge, the table tail,
-    a guess outside the bucket) takes the 64-run code below, one group at a time.
-
-    ``prune`` (``prune_plan``; mode ""): per listed left conjunct the run's bound - ``RMX<slot>``
-    or ``RMN<slot>``, one uint16 per run (code + 32768, ``run_bounds``) - is loaded with the run
-    key (the four-run form: one 8-byte load per lane) and the tag is cleared when the bound
-    fails the conjunct's code range [CL<k>, CH<k>].
-
-    ``k16`` (``tags2_k16``; the four-run form, mode ""): a fast stage reads both key columns as
-    uint16 offsets (``LO16`` per run, ``RO16`` per right row: one 8-byte load each per lane and
-    block) plus the bases of their 32-element groups (``LG16`` / ``RG16``: one dword for the
-    lane's four runs, two for its four right rows, which can straddle one group edge; the group
-    index comes from the run / guessed row, so nothing depends on a load) and rebuilds
-    code = base + offset for the eight keys - 8.25 instead of 12 B per run with one bound.
-    Compare, key frame, miss path and tags are the 32-bit form's.  A stage in which any lane
-    loaded a ``WIDE_GROUP`` base (a ballot after the loads) leaves the pipeline and takes the
-    64-run code on the 32-bit arrays, as the gallop always does.
-
-    ``pair`` (``tags2_pair``; the k16 form with 1-bit tags): two queries of the shape are tagged
-    in one pass.  Loads, guess, key compare, gallop and the wide-group fall-back run once per
-    run; the right predicates and the bound tests run once per literal set (the second set's
-    slots carry ``PAIR_SFX``) and every tag word is stored twice, the second query's into
-    ``tags_b``.  Each bitmap is what the single kernel writes for that literal set."""
+    the kernel's VALU instructions (``profiles/pmc_query_kernels_sf100_r6.txt``)."""
     assert not prune or mode == ""
     assert not k16 or tags2_k16(p, compacts, ix32, mode)
     assert not pair or tags2_pair(p, compacts, W, ix32, mode, k16)
-    IX = "int" if ix32 else "i64"  # noqa: N806 — run / right-row index type
+    recorded, lo16 = mode in ("match", "copy"), mode in ("lo16", "lo16prep")
+    assert ix32 or recorded or not (mode == "rec" or lo16)
     wide = tags2_wide(p, compacts, ix32, mode)
-    args = J.Args()
-    if mode in ("match", "copy"):
-        return _gen_tags2_match(p, compacts, W, mode == "copy")
-    lk, rk = p.lkey, p.rkey
-    args.add("p", f"RK{lk}", "const int*")
-    args.add("p", "RNG", "const long long*")
-    args.add("p", "tags", "unsigned*")
-    if pair:
-        args.add("p", "tags_b", "unsigned*")
-    for n in ("NRG", "NRUNS", "KLO", "KSP", "KOF"):
-        args.add("q", n, "long long")
-    cols = J._col_specs(p, compacts)
-    rpreds = _rpreds(p)
-    rgroup = _tags_grouped(p)
+    # four-run form: 256-run blocks per pipeline stage (RT2_UNROLL counts blocks there), at most
+    # two - 84 VGPRs at W = 1, six waves per SIMD; a third block's register sets would spill
+    U = max(1, min(2, RT2_UNROLL) if wide == 4 else RT2_UNROLL)  # noqa: N806
     stage_slots = _stage_slots(p)
-    U = max(1, RT2_UNROLL)  # noqa: N806
-    WV = J.BLOCK // 64  # noqa: N806
-    MASK = (1 << W) - 1  # noqa: N806
-    if mode == "rec":
-        assert ix32
-        args.add("p", "MOUT", "int*")
-    # the pre-filter's bound arrays and its tests on the loaded bounds (bm<i>_<u>: conjunct i's
-    # bound of run u; hs_c20 keeps the sum in int32)
-    bounds, btests = [], []
-    for i, (k, sl, mx) in enumerate(prune):
-        bounds.append(args.add("p", f"RMX{sl}" if mx else f"RMN{sl}", "const unsigned short*"))
-        lit = args.add("q", f"CL{k}" if mx else f"CH{k}", "long long")
-        btests.append(f"bm{i}_@U@ {'>=' if mx else '<='} hs_c20({lit}) + 32768")
-    if k16:
-        for n in ("LO16", "RO16"):
-            args.add("p", n, "const unsigned short*")
-        for n in ("LG16", "RG16"):
-            args.add("p", n, "const int*")
-    lo16 = mode in ("lo16", "lo16prep")
-    if lo16:
-        assert ix32
-        cst = "" if mode == "lo16prep" else "const "
-        args.add("p", "LL", f"{cst}unsigned short*")
-        args.add("p", "RL", f"{cst}unsigned short*")
-    g = J._Gen(args, cols, SPLIT, ("row_", "row_"), frozenset(), True)
-    rv = J._valid_expr(g, rk, "row_")
-    if rgroup:
-        gb = args.add("q", "group_base", "long long")
-        ng = args.add("q", "num_groups", "long long")
-    renc = cols[rk][2]
-    if renc and len(renc) > 2 and renc[2] == 64:
-        # grouped 16-bit right key: code = gbase[row >> 6] + offset, or the 32-bit code of a
-        # wide group (both loads unconditional: the wide one hits row 0 otherwise)
-        assert rk not in stage_slots
-        base = args.add("q", f"B{rk}", "long long")
-        gp = args.add("p", f"G{rk}", "const int*")
-        wp = args.add("p", f"W{rk}", "const int*")
-        cp = g.ptr(rk)
-        rval = (f"({{ const int gb_ = {gp}[row_ >> 6]; const bool wd_ = gb_ == (int)0x80000000; "
-                f"const int w_ = {wp}[wd_ ? row_ : 0]; const unsigned short o_ = {cp}[row_]; "
-                f"{base} + (wd_ ? (i64)w_ : (i64)gb_ + (i64)o_); }})")
-        # the guess's image without the dependent wide-group load: 0 (below every left image,
-        # so never a false match) for a wide group; a miss re-reads the exact image
-        fval = (f"({{ const int gb_ = {gp}[row_ >> 6]; const unsigned short o_ = {cp}[row_]; "
-                f"gb_ == (int)0x80000000 ? (i64)-1 : {base} + (i64)gb_ + (i64)o_; }})")
-    else:
-        rval = fval = g.value(rk, "row_")
+    enc = J._col_specs(p, compacts)[p.rkey][2]
+    rkg = not recorded and bool(enc and len(enc) > 2 and enc[2] == 64)
+    assert not rkg or p.rkey not in stage_slots
+    bounds = tuple((f"RMX{sl}" if mx else f"RMN{sl}", f"CL{k}" if mx else f"CH{k}",
+                    ">=" if mx else "<=") for k, sl, mx in prune)
+    return _TagsForm("hs_jit_key_lo16" if mode == "lo16prep" else "hs_jit_run_tags2",
+                     "int" if ix32 else "i64", W, (1 << W) - 1, 8 // W, wide, U, mode == "rec",
+                     mode == "match", mode == "copy", lo16, mode == "lo16prep", bool(k16),
+                     bool(pair), _tags_grouped(p), rkg, stage_slots, bounds)
 
-    def image(val: str, wide0: bool) -> str:
-        guard = "(__v_ == (i64)-1) || " if wide0 else ""
-        return (f"({rv} ? 0u : ({{ const i64 __v_ = (i64)({val}); const i64 d_ = __v_ - a.KLO; "
-                f"({guard}d_ < 0) ? 0u : (d_ > a.KSP ? 0xFFFFFFFFu : (unsigned)(d_ + 1)); }}))")
-    img = image(rval, False)
-    imgf = image(fval, fval is not rval)
 
-    def lit_b(expr: str) -> str:
-        """``expr`` over the pair's second literal set: every literal slot it names gets a
-        twin (same kind and type) with ``PAIR_SFX``."""
-        def twin(m):
-            kind, name, ct = args.slots[args._index[m.group(1)]]
-            return args.add(kind, name + PAIR_SFX, ct)
-        return _LIT_SLOT.sub(twin, expr)
+class _Tags2:
+    """The builder behind ``gen_run_tags2``: one method per stage of the kernel, each returning
+    its source lines, over the form ``f``, the argument struct and the column descriptions.
 
-    def tag_expr(gen: J._Gen, it, ok: str) -> str:
-        cond = J._rename(gen.cnf(rpreds), stage_slots, it)
-        if not rgroup:
-            return f"(({ok}) && {cond} ? 1u : 0u)"
-        gx = J._rename(f"x{p.group_col}", stage_slots, it)
-        return (f"({{ const i64 gl_ = (i64){gx} - {gb}; (({ok}) && {cond} && gl_ >= 0 && "
-                f"gl_ < {ng}) ? (unsigned)(gl_ + 1) : 0u; }})")
+    The verifying kernel has no tiles and no LDS.  Each wavefront owns a contiguous chunk of
+    64-run groups of the left run list (so it owns whole 2W-word stretches of the tag bitmap and
+    stores them without atomics).  Ranges (``RNG``, NRG x 4 int64, sorted by first run):
+    [first run, end run) of each left row range and the right bucket's rows [s0, s1).  (16-bit
+    grouped run keys measured 0.59 vs 0.29 ms - more dependent loads per run - and a per-tile
+    LDS form 0.79 ms: both removed.)
 
-    if mode == "lo16prep":
-        # the low 16 bits of every left run key image and right key image (``lo16_keys``)
-        args.add("q", "NRIGHT", "long long")
-        body = [f"  auto IMG = [&]({IX} row_) -> unsigned {{ return {img}; }};",
-                f"  const i64 t_ = (i64)blockIdx.x * {J.BLOCK} + threadIdx.x, "
+    Stages add slots to ``args`` as they emit, and the slot order is the ``Args`` struct layout -
+    part of the source text - so the order of the driver's calls is fixed: ``header`` (every
+    slot that does not depend on a column's encoding), ``images`` (the right key's validity
+    pointer, group_base / num_groups, the key's pointers and base, ``NRIGHT``), then the loop
+    top to bottom - ``group`` / ``load`` / ``recorded_loads`` add the staged columns' pointers and
+    bases (the copy form its ``S<slot>`` / ``SV<slot>``) at their first load, ``tag_expr`` the
+    right predicates' literal slots, and ``lit_b`` a ``PAIR_SFX`` twin of every literal slot
+    where the second set first names it, so straight after the first tag expression's own."""
+
+    def __init__(self, p: NL.JoinParams, compacts, W: int, ix32: bool, mode: str, prune: tuple,
+                 k16: bool, pair: bool):
+        self.f = _tags_form(p, compacts, W, ix32, mode, prune, k16, pair)
+        self.p, self.lk, self.rk = p, p.lkey, p.rkey
+        self.args = J.Args()
+        self.cols = J._col_specs(p, compacts)
+        self.rpreds = _rpreds(p)
+        self.WV = J.BLOCK // 64
+
+    def gen(self, row: str) -> J._Gen:
+        return J._Gen(self.args, self.cols, SPLIT, (row, row), frozenset(), True)
+
+    def header(self) -> None:
+        """The argument slots that precede the columns'."""
+        f, add = self.f, self.args.add
+        if f.match or f.copy:
+            add("p", *(("HIT", "const u64*") if f.copy else ("MATCH", "const int*")))
+            add("p", "tags", "unsigned*")
+            add("q", "NRUNS", "long long")
+            self.group_args()
+            return
+        add("p", f"RK{self.lk}", "const int*")
+        add("p", "RNG", "const long long*")
+        add("p", "tags", "unsigned*")
+        if f.pair:
+            add("p", "tags" + PAIR_SFX, "unsigned*")
+        for n in ("NRG", "NRUNS", "KLO", "KSP", "KOF"):
+            add("q", n, "long long")
+        if f.rec:
+            add("p", "MOUT", "int*")
+        for arr, lit, _ in f.bounds:
+            add("p", arr, "const unsigned short*")
+            add("q", lit, "long long")
+        if f.k16:
+            for n in ("LO16", "RO16"):
+                add("p", n, "const unsigned short*")
+            for n in ("LG16", "RG16"):
+                add("p", n, "const int*")
+        if f.lo16:
+            cst = "" if f.prep else "const "
+            add("p", "LL", f"{cst}unsigned short*")
+            add("p", "RL", f"{cst}unsigned short*")
+
+    def group_args(self) -> None:
+        if self.f.rgroup:
+            self.args.add("q", "group_base", "long long")
+            self.args.add("q", "num_groups", "long long")
+
+    def images(self) -> List[str]:
+        """The lambdas from a right row to its 32-bit key image (the left images are run key +
+        KOF): ``IMG``, exact; ``IMGF``, the guess's, and ``IMGV`` (four-run form), from a loaded
+        element.  Adds the right key's slots and, between its validity pointer and the rest,
+        group_base / num_groups."""
+        f, args, rk = self.f, self.args, self.rk
+        g = self.gen("row_")
+        rv = J._valid_expr(g, rk, "row_")
+        self.group_args()
+        if f.rkg:
+            # grouped 16-bit right key: code = gbase[row >> 6] + offset, or the 32-bit code of a
+            # wide group (both loads unconditional: the wide one hits row 0 otherwise)
+            base = args.add("q", f"B{rk}", "long long")
+            gp = args.add("p", f"G{rk}", "const int*")
+            wp = args.add("p", f"W{rk}", "const int*")
+            cp = g.ptr(rk)
+            rval = (f"({{ const int gb_ = {gp}[row_ >> 6]; const bool wd_ = gb_ == (int)0x80000000; "
+                    f"const int w_ = {wp}[wd_ ? row_ : 0]; const unsigned short o_ = {cp}[row_]; "
+                    f"{base} + (wd_ ? (i64)w_ : (i64)gb_ + (i64)o_); }})")
+            # the guess's image without the dependent wide-group load: 0 (below every left image,
+            # so never a false match) for a wide group; a miss re-reads the exact image
+            fval = (f"({{ const int gb_ = {gp}[row_ >> 6]; const unsigned short o_ = {cp}[row_]; "
+                    f"gb_ == (int)0x80000000 ? (i64)-1 : {base} + (i64)gb_ + (i64)o_; }})")
+        else:
+            rval = fval = g.value(rk, "row_")
+
+        def image(val: str, wide0: bool) -> str:
+            guard = "(__v_ == (i64)-1) || " if wide0 else ""
+            return (f"({rv} ? 0u : ({{ const i64 __v_ = (i64)({val}); const i64 d_ = __v_ - a.KLO; "
+                    f"({guard}d_ < 0) ? 0u : (d_ > a.KSP ? 0xFFFFFFFFu : (unsigned)(d_ + 1)); }}))")
+        b = [f"  auto IMG = [&]({f.IX} row_) -> unsigned {{ return {image(rval, False)}; }};"]
+        if f.prep:
+            args.add("q", "NRIGHT", "long long")
+            return b
+        b.append(f"  auto IMGF = [&]({f.IX} row_) -> unsigned "
+                 f"{{ return {image(fval, fval is not rval)}; }};")
+        if f.wide == 4:
+            b.append(f"  auto IMGV = [&]({g.raw_type(rk)} w_) -> unsigned "
+                     f"{{ return {image(g.decode(rk, 'w_'), False)}; }};")
+        return b
+
+    def prep_body(self) -> List[str]:
+        """The low 16 bits of every left run key image and right key image (``lo16_keys``)."""
+        return [f"  const i64 t_ = (i64)blockIdx.x * {J.BLOCK} + threadIdx.x, "
                 f"n_ = (i64)gridDim.x * {J.BLOCK};",
                 f"  for (i64 i = t_; i < a.NRUNS; i += n_) "
-                f"a.LL[i] = (unsigned short)((unsigned)a.RK{lk}[i] + (unsigned)a.KOF);",
+                f"a.LL[i] = (unsigned short)((unsigned)a.RK{self.lk}[i] + (unsigned)a.KOF);",
                 "  for (i64 i = t_; i < a.NRIGHT; i += n_) a.RL[i] = (unsigned short)IMG((int)i);"]
-        src = (J._PRELUDE + args.struct_src() +
-               f'extern "C" __global__ __launch_bounds__({J.BLOCK}) void hs_jit_key_lo16(Args a) '
-               "{\n" + "\n".join(body) + "\n}\n")
-        return J.Kernel(src, "hs_jit_key_lo16", args)
 
-    b: List[str] = [
-        f"  auto IMG = [&]({IX} row_) -> unsigned {{ return {img}; }};",
-        f"  auto IMGF = [&]({IX} row_) -> unsigned {{ return {imgf}; }};",
-        "  const int lane = (int)(threadIdx.x & 63);",
-        "  const i64 G = (a.NRUNS + 63) >> 6;",
-        f"  const i64 nwv = (i64)gridDim.x * {WV};",
-        # wavefront-uniform (scalar registers, scalar loads of the range table)
-        f"  const i64 wv = (i64)blockIdx.x * {WV} + "
-        "(i64)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
-        "  const i64 per = (G + nwv - 1) / nwv;",
-        "  const i64 gbeg = wv * per;",
-        "  const i64 gend = G < gbeg + per ? G : gbeg + per;",
-        "  if (gbeg >= gend || a.NRG <= 0) return;",
-        "  const i64* RG = a.RNG;",
-        "  int rg = 0;",
-        "  { int lo = 0, hi = (int)a.NRG; const i64 r0 = gbeg << 6;",
-        "    while (hi - lo > 1) { const int m = (lo + hi) >> 1; "
-        "if (RG[4 * m] <= r0) lo = m; else hi = m; }",
-        "    rg = lo; }",
-        f"  {IX} lr0 = ({IX})RG[4 * rg], lr1 = ({IX})RG[4 * rg + 1], s0 = ({IX})RG[4 * rg + 2], "
-        f"s1 = ({IX})RG[4 * rg + 3];",
-        "  i64 nxt0 = rg + 1 < a.NRG ? RG[4 * (rg + 1)] : 0x7fffffffffffffffll;",
-        f"  {IX} gbase = -1;   // right row of the next group's first run (-1: range-relative)",
-        f"  for (i64 gi = gbeg; gi < gend; gi += {U}) {{",
-        "    while (nxt0 <= (gi << 6)) {",
-        f"      ++rg; lr0 = ({IX})RG[4 * rg]; lr1 = ({IX})RG[4 * rg + 1]; s0 = ({IX})RG[4 * rg + 2];",
-        f"      s1 = ({IX})RG[4 * rg + 3]; gbase = -1;",
-        "      nxt0 = rg + 1 < a.NRG ? RG[4 * (rg + 1)] : 0x7fffffffffffffffll; }",
-        # wavefront-uniform: every run of this iteration's groups belongs to range rg (or none)
-        f"    if (((gi + {U}) << 6) <= nxt0) {{"]
-    ind = "      "
+    def prologue(self) -> List[str]:
+        """A wavefront's chunk [gbeg, gend) of 64-run groups - in the four-run form [bbeg, bend)
+        of 256-run blocks, in int, whole stages per wavefront so only a chunk's last stage can
+        be cut by its end - all wavefront-uniform (scalar registers, scalar loads of the range
+        table)."""
+        f = self.f
+        blocks = f.wide == 4
+        T, N, x = ("int", "NB", "b") if blocks else ("i64", "G", "g")  # noqa: N806
+        cast = "" if blocks else "(i64)"
+        per = f"(({N} + nwv - 1) / nwv + {f.U - 1}) / {f.U} * {f.U}" if blocks else \
+            f"({N} + nwv - 1) / nwv"
+        return ["  const int lane = (int)(threadIdx.x & 63);",
+                "  const i64 G = (a.NRUNS + 63) >> 6;"] + \
+            (["  const int NR = (int)a.NRUNS, NB = (int)((a.NRUNS + 255) >> 8);"]
+             if blocks else []) + [
+                f"  const {T} nwv = ({T})gridDim.x * {self.WV};",
+                f"  const {T} wv = ({T})blockIdx.x * {self.WV} + "
+                f"{cast}__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
+                f"  const {T} per = {per};",
+                f"  const {T} {x}beg = wv * per;",
+                f"  const {T} {x}end = {N} < {x}beg + per ? {N} : {x}beg + per;"] + \
+            ([] if f.match or f.copy else [f"  if ({x}beg >= {x}end || a.NRG <= 0) return;"]) + \
+            (["  const i64 gend = G < ((i64)bend << 2) ? G : ((i64)bend << 2);"] if blocks else [])
 
-    def group(u: int, fast: bool, ind: str) -> None:
-        """Loads and guess of group u: unconditional (clamped) loads in the fast form, so all
-        U groups' loads are in flight together (a load under a per-lane condition makes the
-        compiler wait for it before the branches merge)."""
-        b.extend([f"{ind}const {IX} r{u} = ({IX})(((gi + {u}) << 6) + lane);",
-                  f"{ind}const bool in{u} = gi + {u} < gend;"])
+    def seek(self) -> List[str]:
+        """The range of the chunk's first run (a binary search of the range table) and the guess
+        base."""
+        IX, blocks = self.f.IX, self.f.wide == 4  # noqa: N806
+        return ["  const i64* RG = a.RNG;",
+                "  int rg = 0;",
+                "  { int lo = 0, hi = (int)a.NRG; const i64 r0 = " +
+                ("(i64)bbeg << 8" if blocks else "gbeg << 6") + ";",
+                "    while (hi - lo > 1) { const int m = (lo + hi) >> 1; "
+                "if (RG[4 * m] <= r0) lo = m; else hi = m; }",
+                "    rg = lo; }",
+                f"  {IX} lr0 = ({IX})RG[4 * rg], lr1 = ({IX})RG[4 * rg + 1], "
+                f"s0 = ({IX})RG[4 * rg + 2], s1 = ({IX})RG[4 * rg + 3];",
+                "  i64 nxt0 = rg + 1 < a.NRG ? RG[4 * (rg + 1)] : 0x7fffffffffffffffll;",
+                f"  {IX} gbase = -1;   // right row of the next {'stage' if blocks else 'group'}'s "
+                f"first run (-1: range-relative)"]
+
+    def advance(self, at: str, ind: str, inline: bool = False) -> List[str]:
+        """Step to the range that holds run ``at``."""
+        IX = self.f.IX  # noqa: N806
+        b = [f"{ind}while (nxt0 <= {at}) {{",
+             f"{ind}  ++rg; lr0 = ({IX})RG[4 * rg]; lr1 = ({IX})RG[4 * rg + 1]; "
+             f"s0 = ({IX})RG[4 * rg + 2];",
+             f"{ind}  s1 = ({IX})RG[4 * rg + 3]; gbase = -1;",
+             f"{ind}  nxt0 = rg + 1 < a.NRG ? RG[4 * (rg + 1)] : 0x7fffffffffffffffll;"]
+        if inline:
+            b[-1] += " }"
+            return b
+        return b + [f"{ind}}}"]
+
+    def group(self, u: int, fast: bool, ind: str) -> List[str]:
+        """Loads and guess of 64-run group ``gi + u``.  Lane l guesses the right row of its run:
+        the previous group's last match + 1 + l (or, at a range start, the range-relative
+        position) - exact for a foreign key whose every right key has left rows, the common
+        case.  The right predicate and group columns are loaded at the guess together with the
+        key, so a verified guess costs one round trip.  ``fast`` (every run of the iteration
+        lies in range rg): unconditional (clamped) loads, so all U groups' loads are in flight
+        together (a load under a per-lane condition makes the compiler wait for it before the
+        branches merge).  ``prune_plan``'s bound of the run - ``RMX<slot>`` or ``RMN<slot>``,
+        one uint16 per run (code + 32768, ``run_bounds``) - is loaded with the run key."""
+        f, lk, IX = self.f, self.lk, self.f.IX  # noqa: N806
+        b = [f"{ind}const {IX} r{u} = ({IX})(((gi + {u}) << 6) + lane);",
+             f"{ind}const bool in{u} = gi + {u} < gend;"]
         if fast:
             b.append(f"{ind}const {IX} l0_{u} = lr0, l1_{u} = lr1, a0_{u} = s0, a1_{u} = s1; "
                      f"const bool own{u} = true;")
         else:
             b.extend([f"{ind}{IX} l0_{u} = lr0, l1_{u} = lr1, a0_{u} = s0, a1_{u} = s1; "
-                  f"bool own{u} = true;",
-                  f"{ind}if (r{u} >= nxt0) {{ own{u} = false; int q_ = rg;",
-                  f"{ind}  while (q_ + 1 < (int)a.NRG && RG[4 * (q_ + 1)] <= r{u}) ++q_;",
-                  f"{ind}  l0_{u} = ({IX})RG[4 * q_]; l1_{u} = ({IX})RG[4 * q_ + 1]; "
-                  f"a0_{u} = ({IX})RG[4 * q_ + 2]; a1_{u} = ({IX})RG[4 * q_ + 3]; }}"])
+                      f"bool own{u} = true;",
+                      f"{ind}if (r{u} >= nxt0) {{ own{u} = false; int q_ = rg;",
+                      f"{ind}  while (q_ + 1 < (int)a.NRG && RG[4 * (q_ + 1)] <= r{u}) ++q_;",
+                      f"{ind}  l0_{u} = ({IX})RG[4 * q_]; l1_{u} = ({IX})RG[4 * q_ + 1]; "
+                      f"a0_{u} = ({IX})RG[4 * q_ + 2]; a1_{u} = ({IX})RG[4 * q_ + 3]; }}"])
         b.extend([f"{ind}const bool act{u} = in{u} && r{u} < a.NRUNS && r{u} >= l0_{u} && "
-              f"r{u} < l1_{u} && a1_{u} > a0_{u};",
-              f"{ind}{IX} j{u} = (own{u} && gbase >= 0) ? gbase + {u * 64} + lane : "
-              f"a0_{u} + (r{u} - l0_{u});",
-              f"{ind}j{u} = act{u} ? (j{u} < a0_{u} ? a0_{u} : (j{u} >= a1_{u} ? a1_{u} - 1 : j{u}))"
-              f" : 0;"])
-        if lo16 and fast:
+                  f"r{u} < l1_{u} && a1_{u} > a0_{u};",
+                  f"{ind}{IX} j{u} = (own{u} && gbase >= 0) ? gbase + {u * 64} + lane : "
+                  f"a0_{u} + (r{u} - l0_{u});",
+                  f"{ind}j{u} = act{u} ? (j{u} < a0_{u} ? a0_{u} : (j{u} >= a1_{u} ? a1_{u} - 1 : j{u}))"
+                  f" : 0;"])
+        if f.lo16 and fast:
             # 16-bit key halves per lane; the full images of the group's two end pairs (lanes
             # 0 / 1 load them for lane 0 / lane 63) decide in ``resolve`` whether halves suffice
             b.extend([f"{ind}const unsigned key{u} = (unsigned)a.LL[act{u} ? r{u} : 0];",
@@ -521,14 +557,47 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
             b.extend([f"{ind}const unsigned key{u} = (unsigned)a.RK{lk}[act{u} ? r{u} : 0] + "
                       f"(unsigned)a.KOF;",
                       f"{ind}const unsigned k{u} = IMGF(j{u});"])
-        for i, bp in enumerate(bounds):
-            b.append(f"{ind}const int bm{i}_{u} = (int){bp}[act{u} ? r{u} : 0];")
-        gu = J._Gen(args, cols, SPLIT, (f"j{u}", f"j{u}"), frozenset(), True)
-        for sl in stage_slots:
+        for i, (arr, _, _) in enumerate(f.bounds):
+            b.append(f"{ind}const int bm{i}_{u} = (int)a.{arr}[act{u} ? r{u} : 0];")
+        gu = self.gen(f"j{u}")
+        for sl in f.stage_slots:
             J._uload(gu, sl, f"g{u}", b, ind)
+        return b
 
-    def resolve(u, ind: str, lo: bool = False, stores: bool = True) -> None:
-        gu = J._Gen(args, cols, SPLIT, (f"j{u}", f"j{u}"), frozenset(), True)
+    def lit_b(self, expr: str) -> str:
+        """``expr`` over the pair's second literal set: every literal slot it names gets a twin
+        (same kind and type) with ``PAIR_SFX``, added where first met."""
+        def twin(m):
+            kind, name, ct = self.args.slots[self.args._index[m.group(1)]]
+            return self.args.add(kind, name + PAIR_SFX, ct)
+        return _LIT_SLOT.sub(twin, expr)
+
+    def tag_expr(self, gen: J._Gen, it: str, x) -> str:
+        """The tag of run ``x`` from ``hit<x>`` and the right columns loaded as item ``it``: 0 =
+        no (passing) right row, else 1 or the right-side group code + 1.  Adds the right
+        predicates' literal slots.  (The forms over a record spell the same test with other
+        parentheses.)"""
+        f = self.f
+        cond = J._rename(gen.cnf(self.rpreds), f.stage_slots, it)
+        recorded = f.match or f.copy
+        ok = f"hit{x}" if recorded else f"(hit{x})"
+        if not f.rgroup:
+            return f"({ok} && {cond}) ? 1u : 0u" if recorded else f"({ok} && {cond} ? 1u : 0u)"
+        gx = J._rename(f"x{self.p.group_col}", f.stage_slots, it)
+        return (f"({{ const i64 gl_ = (i64){gx} - a.group_base; ({ok} && {cond} && gl_ >= 0 && "
+                f"gl_ < a.num_groups) ? (unsigned)(gl_ + 1) : 0u; }})")
+
+    def resolve(self, x, ind: str, lo: bool = False) -> List[str]:
+        """Verifies the guess of run ``x`` with one compare of the 32-bit key images and leaves
+        ``hit<x>``, the matched row ``m<x>`` and the tag ``tg<x>`` (pair: ``tgb<x>`` for the
+        second literal set - loads, guess, compare and gallop run once per run, the right
+        predicates and bound tests once per set); a mismatch gallops from the guess to the lower
+        bound (exact for any sorted unique right keys) and reloads the staged columns there.
+        The tag is cleared when a loaded bound fails its conjunct's code range [CL<k>, CH<k>]
+        (hs_c20 keeps the sum in int32).  ``lo``: the group's keys are 16-bit halves."""
+        f, lk, IX = self.f, self.lk, self.f.IX  # noqa: N806
+        u, b = x, []
+        gu = self.gen(f"j{u}")
         # (a checked group's keys are low halves: a miss gallops with the full left key)
         kfull = f"(unsigned)a.RK{lk}[r{u}] + (unsigned)a.KOF" if lo else f"key{u}"
         if lo:
@@ -545,10 +614,10 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
         else:
             b.append(f"{ind}bool hit{u} = act{u} && k{u} == key{u};")
         b.extend([f"{ind}{IX} m{u} = j{u};",
-                  f"{ind}unsigned tg{u} = {tag_expr(gu, f'g{u}', f'hit{u}')};"] +
-                 ([f"{ind}unsigned tgb{u} = {lit_b(tag_expr(gu, f'g{u}', f'hit{u}'))};"]
-                  if pair else []) + [
-                  f"{ind}if (act{u} && !hit{u}) {{",
+                  f"{ind}unsigned tg{u} = {self.tag_expr(gu, f'g{u}', u)};"])
+        if f.pair:
+            b.append(f"{ind}unsigned tgb{u} = {self.lit_b(self.tag_expr(gu, f'g{u}', u))};")
+        b.extend([f"{ind}if (act{u} && !hit{u}) {{",
                   # gallop from the guess to the lower bound of key in [a0, a1)
                   f"{ind}  const unsigned key_ = {kfull}; {IX} lo_, hi_;",
                   f"{ind}  const unsigned kj_ = IMG(j{u});",
@@ -569,24 +638,28 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
                   f"{ind}  m{u} = lo_;",
                   f"{ind}  hit{u} = lo_ < a1_{u} && IMG(lo_) == key_;",
                   f"{ind}  const {IX} jm{u} = hit{u} ? lo_ : 0;"])
-        gm = J._Gen(args, cols, SPLIT, (f"jm{u}", f"jm{u}"), frozenset(), True)
-        for sl in stage_slots:
+        gm = self.gen(f"jm{u}")
+        for sl in f.stage_slots:
             J._uload(gm, sl, f"h{u}", b, ind + "  ")
-        b.append(f"{ind}  tg{u} = {tag_expr(gm, f'h{u}', f'hit{u}')};")
-        if pair:
-            b.append(f"{ind}  tgb{u} = {lit_b(tag_expr(gm, f'h{u}', f'hit{u}'))};")
+        b.append(f"{ind}  tg{u} = {self.tag_expr(gm, f'h{u}', u)};")
+        if f.pair:
+            b.append(f"{ind}  tgb{u} = {self.lit_b(self.tag_expr(gm, f'h{u}', u))};")
         b.append(f"{ind}}}")
-        if btests:
+        if f.bounds:
             # a run whose bound fails a left conjunct holds no passing row
-            ok = " && ".join(f"({t.replace('@U@', str(u))})" for t in btests)
+            ok = " && ".join(f"(bm{i}_{u} {cmp} hs_c20(a.{lit}) + 32768)"
+                             for i, (_, lit, cmp) in enumerate(f.bounds))
             b.append(f"{ind}tg{u} = ({ok}) ? tg{u} : 0u;")
-            if pair:
-                b.append(f"{ind}tgb{u} = ({lit_b(ok)}) ? tgb{u} : 0u;")
-        if not stores:
-            return
-        # the group's 2W tag words: whole words, plain stores
+            if f.pair:
+                b.append(f"{ind}tgb{u} = ({self.lit_b(ok)}) ? tgb{u} : 0u;")
+        return b
+
+    def stores(self, u: int, ind: str) -> List[str]:
+        """The 2W tag words of 64-run group ``gi + u`` from the lanes' tags ``tg<u>`` (pair: and
+        ``tgb<u>`` into ``tags_b``): whole words, plain stores; and the recorded match."""
+        f, W, b = self.f, self.f.W, []  # noqa: N806
         if W == 1:
-            for tg, tags in (("tg", "tags"), ("tgb", "tags_b"))[:2 if pair else 1]:
+            for tg, tags in (("tg", "tags"), ("tgb", "tags" + PAIR_SFX))[:2 if f.pair else 1]:
                 b.extend([f"{ind}{{ const u64 bal_ = __ballot({tg}{u} != 0u);",
                           f"{ind}  if (in{u} && lane < 2) a.{tags}[((gi + {u}) << 1) + lane] = "
                           f"(unsigned)(bal_ >> (32 * lane)); }}"])
@@ -595,95 +668,95 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
             b.extend([f"{ind}{{ unsigned wd_ = 0u;",
                       f"{ind}  for (int i_ = 0; i_ < {per_w}; ++i_) {{",
                       f"{ind}    const int src_ = ((lane * {per_w}) + i_) & 63;",
-                      f"{ind}    wd_ |= (((unsigned)__shfl((int)tg{u}, src_, 64)) & {MASK}u) << "
+                      f"{ind}    wd_ |= (((unsigned)__shfl((int)tg{u}, src_, 64)) & {f.MASK}u) << "
                       f"(unsigned)(i_ * {W}); }}",
                       f"{ind}  if (in{u} && lane < {2 * W}) a.tags[(gi + {u}) * {2 * W} + lane] = "
                       f"wd_; }}"])
-        if mode == "rec":
+        if f.rec:
             b.append(f"{ind}if (in{u} && r{u} < a.NRUNS) a.MOUT[r{u}] = hit{u} ? (int)m{u} : -1;")
+        return b
 
-    def iteration(fast: bool, ind: str) -> None:
+    def iteration(self, fast: bool, ind: str) -> List[str]:
+        """U groups: all loads, then the resolves and stores, then the next iteration's guess."""
+        U, IX, b = self.f.U, self.f.IX, []  # noqa: N806
         for u in range(U):
-            group(u, fast, ind)
+            b += self.group(u, fast, ind)
         for u in range(U):
-            resolve(u, ind, lo16 and fast)
+            b += self.resolve(u, ind, self.f.lo16 and fast) + self.stores(u, ind)
         # next iteration's guess: the last group's last lane, when it matched in this range
-        b.extend([f"{ind}{{ const {IX} nx_ = __shfl((hit{U - 1} && own{U - 1}) ? m{U - 1} + 1 : "
-                  f"({IX})-1, 63, 64);",
-                  f"{ind}  gbase = nx_; }}"])
+        return b + [f"{ind}{{ const {IX} nx_ = __shfl((hit{U - 1} && own{U - 1}) ? m{U - 1} + 1 : "
+                    f"({IX})-1, 63, 64);",
+                    f"{ind}  gbase = nx_; }}"]
 
-    if wide == 4:
-        del b[:]
-        return _gen_tags2_wide(p, args, cols, b, group, resolve,
-                               image(g.decode(rk, "w_"), False), img, imgf, W, mode, bounds,
-                               k16, pair)
-    iteration(True, ind)
-    b.append("    } else {   // a range starts inside this iteration's groups")
-    iteration(False, ind)
-    b += ["    }", "  }"]
-    src = (J._PRELUDE + args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({J.BLOCK}) void hs_jit_run_tags2(Args a) {{\n' +
-           "\n".join(b) + "\n}\n")
-    return J.Kernel(src, "hs_jit_run_tags2", args)
+    def group_loop(self) -> List[str]:
+        """The one-run-per-lane kernel's loop: RT2_UNROLL groups in flight per iteration."""
+        U = self.f.U  # noqa: N806
+        return [f"  for (i64 gi = gbeg; gi < gend; gi += {U}) {{"] + \
+            self.advance("(gi << 6)", "    ", True) + [
+            # wavefront-uniform: every run of this iteration's groups belongs to range rg (or none)
+            f"    if (((gi + {U}) << 6) <= nxt0) {{"] + self.iteration(True, "      ") + [
+            "    } else {   // a range starts inside this iteration's groups"] + \
+            self.iteration(False, "      ") + ["    }", "  }"]
 
-
-def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, resolve,
-                    imgv: str, img: str, imgf: str, W: int, mode: str,
-                    bounds=(), k16: bool = False, pair: bool = False) -> J.Kernel:
-    """The four-runs-per-lane body of ``gen_run_tags2`` (its docstring; 32-bit indices).
-    ``group`` / ``resolve`` are that generator's 64-run emitters (appending to ``b``): the slow
-    blocks run them one group at a time, and a fast block's runs resolve through the same miss
-    path, one instance per run.  ``bounds``: the pre-filter's per-run bound arrays (uint16), a
-    lane's four loaded with one 8-byte load beside its run keys.  ``k16``: the keys come as
-    16-bit offsets plus group bases (``gen_run_tags2``).  ``pair``: ``resolve`` also leaves
-    the second literal set's tag ``tgb<x>``; its words go to ``tags_b``."""
-    lk, rk = p.lkey, p.rkey
-    # 256-run blocks per pipeline stage (RT2_UNROLL counts blocks here): at most two - 84 VGPRs
-    # at W = 1, six waves per SIMD; a third block's register sets would spill
-    U = max(1, min(2, RT2_UNROLL))  # noqa: N806
-    WV = J.BLOCK // 64  # noqa: N806
-    MASK = (1 << W) - 1  # noqa: N806
-    L = 8 // W  # noqa: N806 — lanes whose 4 tags share one 32-bit word
-    R = 256 * U  # noqa: N806 — runs per stage
-    stage_slots = _stage_slots(p)
-    g = J._Gen(args, cols, SPLIT, ("row_", "row_"), frozenset(), True)
-    rkt = g.raw_type(rk)
-    # 4 consecutive elements at an element-aligned address (the guess is arbitrary): one load
-    tdefs = ["typedef int hs_i4 __attribute__((ext_vector_type(4)));"] + \
-        (["typedef unsigned short hs_us4 __attribute__((ext_vector_type(4)));"] if bounds or k16
-         else []) + (["typedef unsigned short hs_ro4 __attribute__((ext_vector_type(4), "
-                      "aligned(2)));"] if k16 else []) + [
-             f"typedef {rkt} hs_rk4 __attribute__((ext_vector_type(4), "
-             f"aligned({J._SIZEOF[rkt]})));"]
-    for sl in stage_slots:
-        t = g.raw_type(sl)
-        tdefs.append(f"typedef {t} hs_c{sl}x4 __attribute__((ext_vector_type(4), "
+    def vec_types(self) -> List[str]:
+        """4 consecutive elements at an element-aligned address (the guess is arbitrary): one
+        load."""
+        f, g = self.f, self.gen("row_")
+        rkt = g.raw_type(self.rk)
+        b = ["typedef int hs_i4 __attribute__((ext_vector_type(4)));"] + \
+            (["typedef unsigned short hs_us4 __attribute__((ext_vector_type(4)));"]
+             if f.bounds or f.k16 else []) + \
+            (["typedef unsigned short hs_ro4 __attribute__((ext_vector_type(4), aligned(2)));"]
+             if f.k16 else []) + [
+                f"typedef {rkt} hs_rk4 __attribute__((ext_vector_type(4), "
+                f"aligned({J._SIZEOF[rkt]})));"]
+        for sl in f.stage_slots:
+            t = g.raw_type(sl)
+            b.append(f"typedef {t} hs_c{sl}x4 __attribute__((ext_vector_type(4), "
                      f"aligned({J._SIZEOF[t]})));")
-    sets = ("A", "B")
+        return b
 
-    def adv(ind: str) -> List[str]:
-        return [f"{ind}++rg; lr0 = (int)RG[4 * rg]; lr1 = (int)RG[4 * rg + 1]; "
-                f"s0 = (int)RG[4 * rg + 2];",
-                f"{ind}s1 = (int)RG[4 * rg + 3]; gbase = -1;",
-                f"{ind}nxt0 = rg + 1 < a.NRG ? RG[4 * (rg + 1)] : 0x7fffffffffffffffll;"]
+    def stage_regs(self) -> List[str]:
+        """The two register sets (A / B) of the pipeline, and ``slow_``."""
+        f, b = self.f, []
+        for s in ("A", "B"):
+            b.append(f"  int pb{s} = 0; " + " ".join(
+                (f"hs_us4 L{s}{u} = {{}}; hs_ro4 R{s}{u} = {{}}; int LG{s}{u} = 0, RG{s}{u} = 0, "
+                 f"RH{s}{u} = 0;" if f.k16 else f"hs_v4u L{s}{u} = {{}}; hs_rk4 R{s}{u} = {{}};") +
+                "".join(f" hs_us4 M{i}{s}{u} = {{}};" for i in range(len(f.bounds))) +
+                "".join(f" hs_c{sl}x4 C{sl}{s}{u} = {{}};" for sl in f.stage_slots)
+                for u in range(f.U)))
+        if f.k16:
+            # blocks still to take the 64-run code after a stage met a wide group
+            b.append("  int slow_ = 0;")
+        return b
 
-    def fast(blk: str, off: int, ind: str) -> None:
+    def fast(self, blk: str, off: int, ind: str) -> List[str]:
         """``f_``: the stage of blocks blk .. blk + U - 1 is fast at guess base ``base_`` (the
         resolved base + ``off``, or range-relative) - all wavefront-uniform, tested before any
         address is formed."""
-        b.extend([f"{ind}const int rb_ = ({blk}) << 8;",
-                  f"{ind}const int base_ = gbase >= 0 ? gbase + {off} : s0 + (rb_ - lr0);",
-                  f"{ind}const bool f_ = {'slow_ == 0 && ' if k16 else ''}({blk}) + {U} <= bend && "
-                  f"rb_ >= lr0 && "
-                  f"rb_ + {R} <= lr1 && rb_ + {R} <= NR && (i64)rb_ + {R} <= nxt0 && "
-                  f"base_ >= s0 && base_ + {R} <= s1;"])
+        U, R = self.f.U, 256 * self.f.U  # noqa: N806
+        return [f"{ind}const int rb_ = ({blk}) << 8;",
+                f"{ind}const int base_ = gbase >= 0 ? gbase + {off} : s0 + (rb_ - lr0);",
+                f"{ind}const bool f_ = {'slow_ == 0 && ' if self.f.k16 else ''}({blk}) + {U} <= bend && "
+                f"rb_ >= lr0 && "
+                f"rb_ + {R} <= lr1 && rb_ + {R} <= NR && (i64)rb_ + {R} <= nxt0 && "
+                f"base_ >= s0 && base_ + {R} <= s1;"]
 
-    def load(s: str, run0: str, base: str, ind: str) -> None:
+    def load(self, s: str, run0: str, base: str, ind: str) -> List[str]:
         """Set ``s`` <- the stage whose first run is ``run0`` (a multiple of 256), guessed at
-        right row ``base``; the caller has tested both (``fast``)."""
-        b.append(f"{ind}pb{s} = {base};")
-        for u in range(U):
-            if k16:
+        right row ``base``; the caller has tested both (``fast``).  Per block one 16-byte load
+        of the lane's 4 left keys, one element-aligned 4-element load of the right key and of
+        each staged right column at the guess, and one 8-byte load of its runs' bounds.
+
+        ``k16``: both key columns come as uint16 offsets (``LO16`` per run, ``RO16`` per right
+        row: one 8-byte load each per lane and block) plus the bases of their 32-element groups
+        (``LG16`` / ``RG16``: one dword for the lane's four runs, two for its four right rows,
+        which can straddle one group edge; the group index comes from the run / guessed row, so
+        nothing depends on a load) - 8.25 instead of 12 B per run with one bound."""
+        f, g, b = self.f, self.gen("row_"), [f"{ind}pb{s} = {base};"]
+        for u in range(f.U):
+            if f.k16:
                 lr_, rr_ = f"({run0} + {256 * u} + 4 * lane)", f"({base} + {256 * u} + 4 * lane)"
                 b.extend([f"{ind}L{s}{u} = *(const hs_us4*)(a.LO16 + {lr_});",
                           f"{ind}R{s}{u} = *(const hs_ro4*)(a.RO16 + {rr_});",
@@ -691,30 +764,34 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
                           f"{ind}RG{s}{u} = a.RG16[{rr_} >> 5]; "
                           f"RH{s}{u} = a.RG16[({rr_} + 3) >> 5];"])
             else:
-                b.extend([f"{ind}L{s}{u} = *(const hs_v4u*)(a.RK{lk} + ({run0} + {256 * u} + "
+                b.extend([f"{ind}L{s}{u} = *(const hs_v4u*)(a.RK{self.lk} + ({run0} + {256 * u} + "
                           f"4 * lane));",
-                          f"{ind}R{s}{u} = *(const hs_rk4*)({g.ptr(rk)} + ({base} + {256 * u} + "
+                          f"{ind}R{s}{u} = *(const hs_rk4*)({g.ptr(self.rk)} + ({base} + {256 * u} + "
                           f"4 * lane));"])
-            for i, bp in enumerate(bounds):
-                b.append(f"{ind}M{i}{s}{u} = *(const hs_us4*)({bp} + ({run0} + {256 * u} + "
+            for i, (arr, _, _) in enumerate(f.bounds):
+                b.append(f"{ind}M{i}{s}{u} = *(const hs_us4*)(a.{arr} + ({run0} + {256 * u} + "
                          f"4 * lane));")
-            for sl in stage_slots:
+            for sl in f.stage_slots:
                 b.append(f"{ind}C{sl}{s}{u} = *(const hs_c{sl}x4*)({g.ptr(sl)} + "
                          f"({base} + {256 * u} + 4 * lane));")
+        return b
 
-    def resolve_stage(s: str, ind: str) -> None:
+    def resolve_stage(self, s: str, ind: str) -> List[str]:
         """Tags (and matches) of the stage in register set ``s``: blocks nb .. nb + U - 1,
-        loaded at guess base pb<s>; leaves the resolved next base in ``gbase``."""
-        b.append(f"{ind}int nx_ = -1;")
-        for u in range(U):
-            b.append(f"{ind}{{ unsigned pk_ = 0u;" + (" unsigned pkb_ = 0u;" if pair else "") +
-                     (" hs_i4 mo_;" if mode == "rec" else ""))
+        loaded at guess base pb<s>; four compares per lane and block, a miss gallops per run
+        through ``resolve``; leaves the resolved next base in ``gbase``.  Compare, key frame,
+        miss path and tags are the same with ``k16``, which rebuilds code = base + offset."""
+        f, W, L, g = self.f, self.f.W, self.f.L, self.gen("row_")  # noqa: N806
+        b = [f"{ind}int nx_ = -1;"]
+        for u in range(f.U):
+            b.append(f"{ind}{{ unsigned pk_ = 0u;" + (" unsigned pkb_ = 0u;" if f.pair else "") +
+                     (" hs_i4 mo_;" if f.rec else ""))
             i2 = ind + "  "
             for k in range(4):
                 x = f"{s}{u}_{k}"
                 b.extend([f"{i2}{{ const int j{x} = pb{s} + {256 * u + k} + 4 * lane;",
                           f"{i2}const int a0_{x} = s0, a1_{x} = s1; const bool act{x} = true;"])
-                if k16:
+                if f.k16:
                     # code = group base + offset (exact); right row k is in the group of the
                     # lane's first row or, past a group edge, of its last
                     b.extend([f"{i2}const unsigned key{x} = (unsigned)LG{s}{u} + "
@@ -725,21 +802,21 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
                 else:
                     b.extend([f"{i2}const unsigned key{x} = L{s}{u}[{k}] + (unsigned)a.KOF;",
                               f"{i2}const unsigned k{x} = IMGV(R{s}{u}[{k}]);"])
-                for i in range(len(bounds)):
+                for i in range(len(f.bounds)):
                     b.append(f"{i2}const int bm{i}_{x} = (int)M{i}{s}{u}[{k}];")
-                for sl in stage_slots:
+                for sl in f.stage_slots:
                     J._uload_raw(g, sl, f"g{x}", f"C{sl}{s}{u}[{k}]", "1", b, i2)
-                resolve(x, i2, False, False)
-                b.append(f"{i2}pk_ |= (tg{x} & {MASK}u) << {k * W};")
-                if pair:
-                    b.append(f"{i2}pkb_ |= (tgb{x} & {MASK}u) << {k * W};")
-                if mode == "rec":
+                b += self.resolve(x, i2)
+                b.append(f"{i2}pk_ |= (tg{x} & {f.MASK}u) << {k * W};")
+                if f.pair:
+                    b.append(f"{i2}pkb_ |= (tgb{x} & {f.MASK}u) << {k * W};")
+                if f.rec:
                     b.append(f"{i2}mo_[{k}] = hit{x} ? m{x} : -1;")
-                if u == U - 1 and k == 3:
+                if u == f.U - 1 and k == 3:
                     b.append(f"{i2}nx_ = hit{x} ? m{x} + 1 : -1;")
                 b.append(f"{i2}}}")
             # the lanes of one tag word hold disjoint bit fields: OR across them, one stores
-            for pk, tags in (("pk_", "tags"), ("pkb_", "tags_b"))[:2 if pair else 1]:
+            for pk, tags in (("pk_", "tags"), ("pkb_", "tags" + PAIR_SFX))[:2 if f.pair else 1]:
                 if L > 1:
                     b.append(f"{i2}{pk} <<= (unsigned)({4 * W} * (lane & {L - 1}));")
                 o = 1
@@ -748,107 +825,142 @@ def _gen_tags2_wide(p: NL.JoinParams, args: J.Args, cols, b: List[str], group, r
                     o <<= 1
                 b.append(f"{i2}if ((lane & {L - 1}) == 0) a.{tags}[(nb + {u}) * {8 * W} + "
                          f"(lane >> {L.bit_length() - 1})] = {pk};")
-            if mode == "rec":
+            if f.rec:
                 b.append(f"{i2}*(hs_i4*)(a.MOUT + (((nb + {u}) << 8) + 4 * lane)) = mo_;")
             b.append(f"{ind}}}")
-        b.append(f"{ind}gbase = __builtin_amdgcn_readlane(nx_, 63);")
+        return b + [f"{ind}gbase = __builtin_amdgcn_readlane(nx_, 63);"]
 
-    b.extend([
-        f"  auto IMG = [&](int row_) -> unsigned {{ return {img}; }};",
-        f"  auto IMGF = [&](int row_) -> unsigned {{ return {imgf}; }};",
-        f"  auto IMGV = [&]({rkt} w_) -> unsigned {{ return {imgv}; }};",
-        "  const int lane = (int)(threadIdx.x & 63);",
-        "  const i64 G = (a.NRUNS + 63) >> 6;",
-        "  const int NR = (int)a.NRUNS, NB = (int)((a.NRUNS + 255) >> 8);",
-        f"  const int nwv = (int)gridDim.x * {WV};",
-        f"  const int wv = (int)blockIdx.x * {WV} + "
-        "__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
-        # whole stages per wavefront, so only a chunk's last stage can be cut by its end
-        f"  const int per = ((NB + nwv - 1) / nwv + {U - 1}) / {U} * {U};",
-        "  const int bbeg = wv * per;",
-        "  const int bend = NB < bbeg + per ? NB : bbeg + per;",
-        "  if (bbeg >= bend || a.NRG <= 0) return;",
-        "  const i64 gend = G < ((i64)bend << 2) ? G : ((i64)bend << 2);",
-        "  const i64* RG = a.RNG;",
-        "  int rg = 0;",
-        "  { int lo = 0, hi = (int)a.NRG; const i64 r0 = (i64)bbeg << 8;",
-        "    while (hi - lo > 1) { const int m = (lo + hi) >> 1; "
-        "if (RG[4 * m] <= r0) lo = m; else hi = m; }",
-        "    rg = lo; }",
-        "  int lr0 = (int)RG[4 * rg], lr1 = (int)RG[4 * rg + 1], s0 = (int)RG[4 * rg + 2], "
-        "s1 = (int)RG[4 * rg + 3];",
-        "  i64 nxt0 = rg + 1 < a.NRG ? RG[4 * (rg + 1)] : 0x7fffffffffffffffll;",
-        "  int gbase = -1;   // right row of the next stage's first run (-1: range-relative)"])
-    for s in sets:
-        b.append(f"  int pb{s} = 0; " + " ".join(
-            (f"hs_us4 L{s}{u} = {{}}; hs_ro4 R{s}{u} = {{}}; int LG{s}{u} = 0, RG{s}{u} = 0, "
-             f"RH{s}{u} = 0;" if k16 else f"hs_v4u L{s}{u} = {{}}; hs_rk4 R{s}{u} = {{}};") +
-            "".join(f" hs_us4 M{i}{s}{u} = {{}};" for i in range(len(bounds))) +
-            "".join(f" hs_c{sl}x4 C{sl}{s}{u} = {{}};" for sl in stage_slots)
-            for u in range(U)))
-    if k16:
-        # blocks still to take the 64-run code after a stage met a wide group
-        b.append("  int slow_ = 0;")
-    b.extend(["  int nb = bbeg;",
-              "  while (nb < bend) {",
-              "    while (nxt0 <= ((i64)nb << 8)) {"] + adv("      ") + ["    }"])
-    fast("nb", 0, "    ")
-    b.extend(["    if (!f_) {   // slow block: its 64-run groups one at a time",
-              "#pragma unroll 1",
-              "      for (i64 gi = (i64)nb << 2; gi < (((i64)nb + 1) << 2) && gi < gend; ++gi) {",
-              "        while (nxt0 <= (gi << 6)) {"] + adv("          ") + ["        }"])
-    group(0, False, "        ")
-    resolve(0, "        ")
-    b.extend(["        gbase = __builtin_amdgcn_readlane((hit0 && own0) ? m0 + 1 : -1, 63);",
-              "      }"] + (["      slow_ -= slow_ > 0 ? 1 : 0;"] if k16 else []) + [
-              "      ++nb; continue;",
-              "    }"])
-    load("A", "rb_", "base_", "    ")
-    b.append("    for (;;) {")
-    for s, t in (("A", "B"), ("B", "A")):
-        # set s holds the stage at nb: issue the next stage's loads into set t, then resolve s.
-        # The loads are unconditional (under a branch the compiler would wait for them where
-        # the paths merge): when the next stage is not fast they re-read this stage's
-        # addresses, which passed the test, and the loop ends after this stage
-        b.append("      {")
-        fast(f"nb + {U}", R, "        ")
-        b.append(f"        const int nr_ = f_ ? rb_ : (nb << 8), nj_ = f_ ? base_ : pb{s};")
-        load(t, "nr_", "nj_", "        ")
-        if k16:
-            # a wide group among this stage's loaded bases (wavefront-uniform): its blocks take
-            # the 64-run code on the 32-bit arrays (nb and gbase still name this stage)
-            wd = " || ".join(f"{r}{s}{u} == (int)0x80000000" for u in range(U)
-                             for r in ("LG", "RG", "RH"))
-            b.append(f"        if (__ballot({wd}) != 0ull) {{ slow_ = {U}; "
-                     "__builtin_amdgcn_s_waitcnt(0x0F70); break; }")
-        resolve_stage(s, "        ")
-        # (leaving the loop: drain the re-read, or the compiler's wait counts, which merge
-        # every path into the loop head, would wait for it in every iteration: vmcnt(0))
-        b.extend([f"        nb += {U};",
+    def slow_block(self) -> List[str]:
+        """Block nb through the 64-run ``group`` / ``resolve``, one group at a time, on the
+        32-bit arrays."""
+        return ["    if (!f_) {   // slow block: its 64-run groups one at a time",
+                "#pragma unroll 1",
+                "      for (i64 gi = (i64)nb << 2; gi < (((i64)nb + 1) << 2) && gi < gend; ++gi) {"] + \
+            self.advance("(gi << 6)", "        ") + self.group(0, False, "        ") + \
+            self.resolve(0, "        ") + self.stores(0, "        ") + [
+                "        gbase = __builtin_amdgcn_readlane((hit0 && own0) ? m0 + 1 : -1, 63);",
+                "      }"] + (["      slow_ -= slow_ > 0 ? 1 : 0;"] if self.f.k16 else []) + [
+                "      ++nb; continue;",
+                "    }"]
+
+    def pipeline(self) -> List[str]:
+        """The fast stages from nb on.  The guess of the stage after the current one assumes
+        every run matches (current base + its runs), so its loads are issued before the current
+        stage is resolved - two register sets, the loop unrolled by two so neither is copied;
+        the resolved base (last match + 1) replaces the assumption for the stage after that."""
+        f, U, R = self.f, self.f.U, 256 * self.f.U  # noqa: N806
+        b = self.load("A", "rb_", "base_", "    ") + ["    for (;;) {"]
+        for s, t in (("A", "B"), ("B", "A")):
+            # set s holds the stage at nb: issue the next stage's loads into set t, then resolve s.
+            # The loads are unconditional (under a branch the compiler would wait for them where
+            # the paths merge): when the next stage is not fast they re-read this stage's
+            # addresses, which passed the test, and the loop ends after this stage
+            b += ["      {"] + self.fast(f"nb + {U}", R, "        ") + [
+                f"        const int nr_ = f_ ? rb_ : (nb << 8), nj_ = f_ ? base_ : pb{s};"] + \
+                self.load(t, "nr_", "nj_", "        ")
+            if f.k16:
+                # a wide group (``WIDE_GROUP``) among this stage's loaded bases (a ballot after the
+                # loads; wavefront-uniform): its blocks take the 64-run code on the 32-bit arrays,
+                # as the gallop always does (nb and gbase still name this stage)
+                wd = " || ".join(f"{r}{s}{u} == (int)0x80000000" for u in range(U)
+                                 for r in ("LG", "RG", "RH"))
+                b.append(f"        if (__ballot({wd}) != 0ull) {{ slow_ = {U}; "
+                         "__builtin_amdgcn_s_waitcnt(0x0F70); break; }")
+            b += self.resolve_stage(s, "        ")
+            # (leaving the loop: drain the re-read, or the compiler's wait counts, which merge
+            # every path into the loop head, would wait for it in every iteration: vmcnt(0))
+            b += [f"        nb += {U};",
                   "        if (!f_) { __builtin_amdgcn_s_waitcnt(0x0F70); break; }",
-                  "      }"])
-    b.extend(["    }", "  }"])
-    src = (J._PRELUDE + args.struct_src() + "\n".join(tdefs) + "\n" +
-           f'extern "C" __global__ __launch_bounds__({J.BLOCK}) void hs_jit_run_tags2(Args a) {{\n' +
-           "\n".join(b) + "\n}\n")
-    return J.Kernel(src, "hs_jit_run_tags2", args)
+                  "      }"]
+        return b + ["    }"]
+
+    def block_loop(self) -> List[str]:
+        """The four-runs-per-lane kernel's loop (``tags2_wide``): the chunk is counted in 256-run
+        blocks, lane l owning runs 256 b + 4 l .. + 3.  A block whose runs all lie in one range
+        and below NRUNS, and whose 256 guessed right rows lie in [s0, s1), is *fast*; every other
+        block (a range edge, the table tail, a guess outside the bucket) is a ``slow_block``."""
+        return self.stage_regs() + ["  int nb = bbeg;", "  while (nb < bend) {"] + \
+            self.advance("((i64)nb << 8)", "    ") + self.fast("nb", 0, "    ") + \
+            self.slow_block() + self.pipeline() + ["  }"]
+
+    def recorded_loop(self) -> List[str]:
+        """Phase 1 over a recorded match (``match``): per run one int32 load of its right row
+        (-1: no match, or the run is outside the lowering's ranges), then the right predicate /
+        group columns at that row.  No key images, no range table, no gallop: the record already
+        resolved them (``record_matches``: it depends only on the lowering's ranges and the key
+        columns, not on the literals), so the phase reads 4 bytes per run plus the staged right
+        columns (monotone rows: coalesced).
+
+        ``copy``: the right columns were gathered into run order at the record (``S<slot>`` /
+        ``SV<slot>``, ``gen_match_gather``; added here at the first group's loads) and the match
+        is one bit per run (``HIT``, one 64-bit word per 64-run group, read once per wavefront):
+        the phase reads the stored codes of its predicate columns per run and nothing at right
+        rows."""
+        f, args, cols, ind = self.f, self.args, self.cols, "    "
+        b = [f"  for (i64 gi = gbeg; gi < gend; gi += {f.U}) {{"]
+        for u in range(f.U):
+            # the record is padded to whole groups: an in-range group's 64 lanes all read it
+            b.append(f"{ind}const bool in{u} = gi + {u} < gend;")
+            if f.copy:
+                b.extend([f"{ind}const int r{u} = in{u} ? (int)(((gi + {u}) << 6) + lane) : lane;",
+                          f"{ind}const u64 hb{u} = a.HIT[in{u} ? gi + {u} : 0];"])
+                for sl in f.stage_slots:
+                    t = self.gen("r_").raw_type(sl)
+                    sp = args.add("p", f"S{sl}", f"const {t}*")
+                    b.append(f"{ind}const {t} w{sl}_g{u} = {sp}[r{u}];")
+                    if cols[sl][1]:
+                        vp = args.add("p", f"SV{sl}", "const unsigned char*")
+                        b.append(f"{ind}const unsigned char u{sl}_g{u} = {vp}[r{u}];")
+            else:
+                b.append(f"{ind}const int mt{u} = a.MATCH[in{u} ? (((gi + {u}) << 6) + lane) : lane];")
+        for u in range(f.U):
+            if f.copy:
+                b.append(f"{ind}const bool hit{u} = in{u} && ((hb{u} >> lane) & 1ull);")
+                gu = self.gen(f"r{u}")
+                for sl in f.stage_slots:
+                    J._uload_raw(gu, sl, f"g{u}", f"w{sl}_g{u}", f"u{sl}_g{u}", b, ind)
+                continue
+            b.extend([f"{ind}const bool hit{u} = in{u} && mt{u} >= 0;",
+                      f"{ind}const int j{u} = hit{u} ? mt{u} : 0;"])
+            gu = self.gen(f"j{u}")
+            for sl in f.stage_slots:
+                J._uload(gu, sl, f"g{u}", b, ind)
+        for u in range(f.U):
+            b.append(f"{ind}const unsigned tg{u} = {self.tag_expr(self.gen(f'j{u}'), f'g{u}', u)};")
+            b += self.stores(u, ind)
+        return b + ["  }"]
 
 
-def _tag_stores(b: List[str], u: int, W: int, ind: str) -> None:
-    """The 2W tag words of 64-run group ``gi + u`` from the lanes' tags ``tg<u>``: whole words,
-    plain stores."""
-    if W == 1:
-        b.extend([f"{ind}{{ const u64 bal_ = __ballot(tg{u} != 0u);",
-                  f"{ind}  if (in{u} && lane < 2) a.tags[((gi + {u}) << 1) + lane] = "
-                  f"(unsigned)(bal_ >> (32 * lane)); }}"])
-        return
-    per_w = 32 // W
-    b.extend([f"{ind}{{ unsigned wd_ = 0u;",
-              f"{ind}  for (int i_ = 0; i_ < {per_w}; ++i_) {{",
-              f"{ind}    const int src_ = ((lane * {per_w}) + i_) & 63;",
-              f"{ind}    wd_ |= (((unsigned)__shfl((int)tg{u}, src_, 64)) & {(1 << W) - 1}u) << "
-              f"(unsigned)(i_ * {W}); }}",
-              f"{ind}  if (in{u} && lane < {2 * W}) a.tags[(gi + {u}) * {2 * W} + lane] = wd_; }}"])
+def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
+                  mode: str = "", prune: tuple = (), k16: bool = False,
+                  pair: bool = False) -> J.Kernel:
+    """Phase 1, direct form (``_Tags2``).  The forms (``_tags_form``) and their stages:
+
+    * mode "" / "rec" (also stores each run's matched right row, or -1, into ``MOUT``) / "lo16",
+      one run per lane: ``group_loop`` - per iteration U ``group`` loads, then ``resolve`` and
+      ``stores`` per group;
+    * the same modes, four runs per lane (``tags2_wide``): ``block_loop`` - ``fast`` test, then
+      ``slow_block`` or the ``pipeline`` of ``load`` and ``resolve_stage``; with ``prune``
+      (``prune_plan``) bounds, ``k16`` (``tags2_k16``) key offsets and for a ``pair``
+      (``tags2_pair``: every tag word stored twice, the second query's into ``tags_b``; each
+      bitmap is what the single kernel writes for that literal set);
+    * "match" / "copy": ``recorded_loop`` over ``MATCH`` (one int32 per run, -1 padded to whole
+      64-run groups) or ``HIT`` and the column copies, instead of the run keys, the key images
+      and the range table;
+    * "lo16prep" (kernel ``hs_jit_key_lo16``): ``prep_body``.
+
+    The driver is the kernel top to bottom; its order is also the order in which argument slots
+    are added (``_Tags2``), so it is part of the sources' text."""
+    s = _Tags2(p, compacts, W, ix32, mode, prune, k16, pair)
+    s.header()
+    if s.f.match or s.f.copy:
+        b = s.prologue() + s.recorded_loop()
+    elif s.f.prep:
+        b = s.images() + s.prep_body()
+    else:
+        b = s.images() + s.prologue() + s.seek() + \
+            (s.block_loop() if s.f.wide == 4 else s.group_loop())
+    return _kernel(s.f.name, s.args, b, tdefs=s.vec_types() if s.f.wide == 4 else ())
 
 
 def copy_ok(p: NL.JoinParams, compacts) -> bool:
@@ -860,88 +972,6 @@ def copy_ok(p: NL.JoinParams, compacts) -> bool:
         if enc and len(enc) > 2 and enc[2] == 64:
             return False
     return True
-
-
-def _gen_tags2_match(p: NL.JoinParams, compacts, W: int, copy: bool = False) -> J.Kernel:
-    """Phase 1 over a recorded match (``gen_run_tags2`` mode "match"): per run one int32 load
-    of its right row (-1: no match, or the run is outside the lowering's ranges), then the right
-    predicate / group columns at that row.  No key images, no range table, no gallop: the
-    record already resolved them (``record_matches``), so the phase reads 4 bytes per run plus
-    the staged right columns (monotone rows: coalesced).
-
-    ``copy`` (mode "copy"): the right columns were gathered into run order at the record
-    (``S<slot>`` / ``SV<slot>``, ``gen_match_gather``) and the match is one bit per run
-    (``HIT``, one 64-bit word per 64-run group, read once per wavefront): the phase reads the
-    stored codes of its predicate columns per run and nothing at right rows."""
-    args = J.Args()
-    if copy:
-        args.add("p", "HIT", "const u64*")
-    else:
-        args.add("p", "MATCH", "const int*")
-    args.add("p", "tags", "unsigned*")
-    args.add("q", "NRUNS", "long long")
-    cols = J._col_specs(p, compacts)
-    rpreds = _rpreds(p)
-    rgroup = _tags_grouped(p)
-    stage_slots = _stage_slots(p)
-    if rgroup:
-        gb = args.add("q", "group_base", "long long")
-        ng = args.add("q", "num_groups", "long long")
-    U = max(1, RT2_UNROLL)  # noqa: N806
-    WV = J.BLOCK // 64  # noqa: N806
-    ind = "    "
-    b: List[str] = [
-        "  const int lane = (int)(threadIdx.x & 63);",
-        "  const i64 G = (a.NRUNS + 63) >> 6;",
-        f"  const i64 nwv = (i64)gridDim.x * {WV};",
-        f"  const i64 wv = (i64)blockIdx.x * {WV} + "
-        "(i64)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
-        "  const i64 per = (G + nwv - 1) / nwv;",
-        "  const i64 gbeg = wv * per;",
-        "  const i64 gend = G < gbeg + per ? G : gbeg + per;",
-        f"  for (i64 gi = gbeg; gi < gend; gi += {U}) {{"]
-    for u in range(U):
-        # the record is padded to whole groups: an in-range group's 64 lanes all read it
-        b.append(f"{ind}const bool in{u} = gi + {u} < gend;")
-        if copy:
-            b.extend([f"{ind}const int r{u} = in{u} ? (int)(((gi + {u}) << 6) + lane) : lane;",
-                      f"{ind}const u64 hb{u} = a.HIT[in{u} ? gi + {u} : 0];"])
-            for sl in stage_slots:
-                gt = J._Gen(args, cols, SPLIT, ("r_", "r_"), frozenset(), True)
-                sp = args.add("p", f"S{sl}", f"const {gt.raw_type(sl)}*")
-                b.append(f"{ind}const {gt.raw_type(sl)} w{sl}_g{u} = {sp}[r{u}];")
-                if cols[sl][1]:
-                    vp = args.add("p", f"SV{sl}", "const unsigned char*")
-                    b.append(f"{ind}const unsigned char u{sl}_g{u} = {vp}[r{u}];")
-        else:
-            b.append(f"{ind}const int mt{u} = a.MATCH[in{u} ? (((gi + {u}) << 6) + lane) : lane];")
-    for u in range(U):
-        if copy:
-            b.append(f"{ind}const bool hit{u} = in{u} && ((hb{u} >> lane) & 1ull);")
-            gu = J._Gen(args, cols, SPLIT, (f"r{u}", f"r{u}"), frozenset(), True)
-            for sl in stage_slots:
-                J._uload_raw(gu, sl, f"g{u}", f"w{sl}_g{u}", f"u{sl}_g{u}", b, ind)
-            continue
-        b.extend([f"{ind}const bool hit{u} = in{u} && mt{u} >= 0;",
-                  f"{ind}const int j{u} = hit{u} ? mt{u} : 0;"])
-        gu = J._Gen(args, cols, SPLIT, (f"j{u}", f"j{u}"), frozenset(), True)
-        for sl in stage_slots:
-            J._uload(gu, sl, f"g{u}", b, ind)
-    for u in range(U):
-        gu = J._Gen(args, cols, SPLIT, (f"j{u}", f"j{u}"), frozenset(), True)
-        cond = J._rename(gu.cnf(rpreds), stage_slots, f"g{u}")
-        if rgroup:
-            gx = J._rename(f"x{p.group_col}", stage_slots, f"g{u}")
-            b.append(f"{ind}const unsigned tg{u} = ({{ const i64 gl_ = (i64){gx} - {gb}; "
-                     f"(hit{u} && {cond} && gl_ >= 0 && gl_ < {ng}) ? (unsigned)(gl_ + 1) : 0u; }});")
-        else:
-            b.append(f"{ind}const unsigned tg{u} = (hit{u} && {cond}) ? 1u : 0u;")
-        _tag_stores(b, u, W, ind)
-    b.append("  }")
-    src = (J._PRELUDE + args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({J.BLOCK}) void hs_jit_run_tags2(Args a) {{\n' +
-           "\n".join(b) + "\n}\n")
-    return J.Kernel(src, "hs_jit_run_tags2", args)
 
 
 def record_matches(p: NL.JoinParams, compacts, W: int, vt: dict, nruns: int, grid: int, dev):
@@ -979,10 +1009,7 @@ def gen_match_gather(p: NL.JoinParams, compacts) -> J.Kernel:
             vp = args.add("p", f"SV{sl}", "unsigned char*")
             b.append(f"    {vp}[i] = {g.vptr(sl)}[j_];")
     b.append("  }")
-    src = (J._PRELUDE + args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({J.BLOCK}) void hs_jit_match_gather(Args a) '
-           "{\n" + "\n".join(b) + "\n}\n")
-    return J.Kernel(src, "hs_jit_match_gather", args)
+    return _kernel("hs_jit_match_gather", args, b)
 
 
 def copy_matches(p: NL.JoinParams, compacts, m, vt: dict, dev) -> tuple:
@@ -1136,11 +1163,8 @@ def gen_run_scan(p: NL.JoinParams, compacts, W: int, NI: int) -> J.Kernel:
            "  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;"]
     if rgroup:
         pre.append(f"  __shared__ int cj_s[{Wv}][{64 * NI}];")
-    src = (J._PRELUDE + args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({BLOCK}) void hs_jit_run_scan(Args a) {{\n' +
-           "\n".join(pre + b) + "\n}\n")
-    lds = (len(aggs) * p.num_groups * 32) if grouped else 0
-    return J.Kernel(src, "hs_jit_run_scan", args, lds)
+    return _kernel("hs_jit_run_scan", args, pre + b,
+                   (len(aggs) * p.num_groups * 32) if grouped else 0)
 
 
 # phase 2 for 1-bit tags: masks 64 rows at a time (gen_run_sparse_scan; RS_BITS), aggregate
@@ -2156,11 +2180,8 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     # accumulators and mask; the union path alone fits six (73) - so five stays)
     waves = RS_WAVES or (5 if s.f.pair else 0)
     occ = f" __attribute__((amdgpu_waves_per_eu({waves}, {waves})))" if waves else ""
-    src = (J._PRELUDE + s.args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({J.BLOCK}){occ} void {s.f.name}(Args a) '
-           f'{{\n' + "\n".join(b) + "\n}\n")
-    lds = (len(s.aggs) * p.num_groups * 32) if s.f.grouped else 0
-    return J.Kernel(src, s.f.name, s.args, lds)
+    return _kernel(s.f.name, s.args, b, (len(s.aggs) * p.num_groups * 32) if s.f.grouped else 0,
+                   attrs=occ)
 
 
 class TwoPhaseLauncher:

@@ -18,25 +18,15 @@ Cases, by group (one test case each):
   (left-grouped, a float predicate, a plain predicate column, a nullable one) under ``EXTRA_CFGS``.
 * ``scan/q3g3``: one ``gen_run_scan`` source (the argument header it shares).
 
-Per case the kernel name, sha1 of the source, sha1 of ``repr(args.slots)`` and ``lds_bytes`` - or
-``!<exception type>`` if generation raises, or null where the form does not apply under the
-setting.  A group's cases are a list in the order ``cases(group)`` yields them (the base groups:
-``itertools.product`` over ``SWEEP``, last setting fastest), each an index into the distinct
-sources, which are stored once; each of those also keeps one
-character per line after the prelude (6 bits of the line's sha1), from which a mismatch names its
-first differing line (a changed line goes unnoticed there with probability 1/64; the sha1 of the
-whole source decides equality).
+The record per case and the file form: ``source_manifest.py``.  A group's cases come in the
+order ``cases(group)`` yields them (the base groups: ``itertools.product`` over ``SWEEP``, last
+setting fastest).
 """
-import argparse
 import functools
-import hashlib
 import itertools
-import json
-import os
-import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import source_manifest as S
+from source_manifest import cfg_key
 
 SWEEP = (("rs_keep", (True, False)), ("rs_lut", (True, False)), ("rs_pipe", (0, 1, 2)),
          ("rs_lds", (False, True)), ("rs_pk16", (True, False)), ("rs_pack12", (True, False)),
@@ -48,50 +38,13 @@ BASE_GROUPS = ("headline/stream", "headline/cand", "headline/cand2",
 EXTRA_GROUPS = ("extra/left_grouped", "extra/float_pred", "extra/plain_pred_col",
                 "extra/nullable_pred_col")
 GROUPS = BASE_GROUPS + EXTRA_GROUPS + ("scan/q3g3",)
-_B64 = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/"
-
-
-def cfg_key(cfg: dict) -> str:
-    return ",".join(f"{k}={int(v)}" for k, v in cfg.items()) or "default"
-
-
-def use_tree(root: str) -> None:
-    """Import ``hyperspace_amd`` and the tests' helpers from ``root``."""
-    for d in (os.path.join(root, "tests"), root):
-        if d in sys.path:
-            sys.path.remove(d)
-        sys.path.insert(0, d)
-
-
-def _gen_join_src():
-    """``scripts/dev/gen_join_src`` of the tree ``hyperspace_amd`` comes from."""
-    import hyperspace_amd
-    root = os.path.dirname(os.path.dirname(os.path.abspath(hyperspace_amd.__file__)))
-    sys.path.insert(0, os.path.join(root, "scripts", "dev"))
-    try:
-        import gen_join_src
-    finally:
-        sys.path.pop(0)
-    return gen_join_src
-
-
-def line_digest(src: str, prelude: str) -> str:
-    assert src.startswith(prelude)
-    return "".join(_B64[hashlib.sha1(x.encode()).digest()[0] & 63]
-                   for x in src[len(prelude):].split("\n"))
-
-
-def record(k, prelude: str) -> tuple:
-    return (k.name, hashlib.sha1(k.src.encode()).hexdigest(),
-            hashlib.sha1(repr(k.args.slots).encode()).hexdigest(), k.lds_bytes,
-            line_digest(k.src, prelude))
 
 
 def _extra_shape(group: str):
     """(params, compacts, objects to keep alive) of an ``extra/`` group."""
     import numpy as np
     import pyarrow as pa
-    G = _gen_join_src()
+    G = S.gen_join_src()
     from hyperspace_amd.exec.device_table import DeviceColumn
     from hyperspace_amd.exec.encoding import encode
     from hyperspace_amd.ops import _lib as NL
@@ -123,7 +76,7 @@ def cases(group: str):
     its ``kernel_config.use`` and returns None where the form does not apply."""
     import types
     import pyarrow as pa
-    G = _gen_join_src()
+    G = S.gen_join_src()
     from hyperspace_amd.exec import hash_agg as H
     from hyperspace_amd.exec import jit_runs, kernel_config
     from hyperspace_amd.ops import _lib as NL
@@ -191,53 +144,9 @@ def cases(group: str):
 
 
 def generate(group: str):
-    """Yield (configuration key, ``record`` tuple | "!ExceptionType" | None, kernel | None) of
-    ``group``."""
-    from hyperspace_amd.exec import jit
-    for key, run in cases(group):
-        try:
-            k = run()
-        except Exception as e:  # noqa: BLE001 — recorded: a case may raise on the parent too
-            yield key, "!" + type(e).__name__, None
-            continue
-        yield key, (None if k is None else record(k, jit._PRELUDE)), k
-
-
-def manifest() -> dict:
-    from hyperspace_amd.exec import jit
-    sources, index, out = [], {}, {}
-    for group in GROUPS:
-        got = out[group] = []
-        for _key, rec, _k in generate(group):
-            if isinstance(rec, tuple):
-                if rec not in index:
-                    index[rec] = len(sources)
-                    sources.append(list(rec))
-                rec = index[rec]
-            got.append(rec)
-    return {"prelude": hashlib.sha1(jit._PRELUDE.encode()).hexdigest(),
-            "sources": sources, "cases": out}
-
-
-def main() -> None:
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--root", default=ROOT)
-    ap.add_argument("--out", required=True)
-    a = ap.parse_args()
-    use_tree(os.path.abspath(a.root))
-    m = manifest()
-    with open(a.out, "w") as f:
-        # one distinct source / one group per line
-        dumps = lambda x: json.dumps(x, separators=(",", ":"))  # noqa: E731
-        f.write('{"prelude":' + dumps(m["prelude"]) + ',\n"sources":[\n' +
-                ",\n".join(dumps(s) for s in m["sources"]) + '],\n"cases":{\n' +
-                ",\n".join(dumps(g) + ":" + dumps(c) for g, c in m["cases"].items()) + "}}\n")
-    import hyperspace_amd
-    assert os.path.abspath(hyperspace_amd.__file__).startswith(os.path.abspath(a.root) + os.sep)
-    recs = [r for v in m["cases"].values() for r in v if r is not None]
-    n, bad = len(recs), sum(isinstance(r, str) for r in recs)
-    print(f"{n} cases, {len(m['sources'])} distinct sources, {bad} raised")
+    """``source_manifest.generate`` over ``group``."""
+    return S.generate(cases(group))
 
 
 if __name__ == "__main__":
-    main()
+    S.main(__doc__, GROUPS, cases)

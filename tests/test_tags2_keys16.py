@@ -304,7 +304,7 @@ def test_join_data_holds_the_cases():
 
 
 def _stage_walk(d, sub: bool, grid: int, U: int):
-    """Host model of the four-run kernel's walk over its 256-run blocks (``_gen_tags2_wide``
+    """Host model of the four-run kernel's walk over its 256-run blocks (``_Tags2.block_loop``
     with ``k16``) for the ranges of ``_ranges(d, sub)``: per wavefront the events
     ("fast", first run, guess base) - a stage of U blocks resolved from the 16-bit arrays -,
     ("wide", first run, left wide, right wide) - a loaded stage that met a wide group and left
