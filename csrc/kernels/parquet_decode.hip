@@ -131,9 +131,11 @@ enum : int { kErrCorrupt = 1, kErrDictRange = 2 };
 // Snappy raw-block decompression by one wavefront (input at byte offset `ib` of the 4-byte
 // aligned buffer `base`, `n` bytes; output `out`, `cap` bytes).
 //
-// Tag parsing is data-parallel.  Each batch looks at a 512-byte window of the input: every
-// lane speculatively decodes a tag at each of its 8 window offsets (length, source and the
-// offset of the following tag), then pointer-jumping tables over "next tag" (6 rounds) give
+// Tag parsing is data-parallel.  Each batch looks at an HS_SNAPPY_WIN-byte (128) window of the
+// input: every lane speculatively decodes a tag at each of its WIN / 64 (2) window offsets
+// (length, source and the offset of the following tag; a tag that cannot be real — header
+// past the window, literal past the input, copy offset 0 — is its own successor and ends the
+// batch), then pointer-jumping tables over "next tag" (6 rounds) give
 // every lane j the position of the j-th tag after the window start, so up to 64 real tags
 // are found in O(log) LDS steps instead of one dependent step per tag.  Then
 //   1. literal bytes are copied byte-parallel over the batch (a batch that is one long literal,
@@ -207,11 +209,18 @@ __device__ void snappy_wave(const uint8_t* __restrict__ base, int64_t ib, int n,
         l = 1 + (tag >> 2); src = -(h[1] | (h[2] << 8)); hl = 3;
       } else {
         l = 1 + (tag >> 2);
-        src = -(h[1] | (h[2] << 8) | (h[3] << 16) | ((int)h[4] << 24));
+        const int off = (int)(h[1] | (h[2] << 8) | (h[3] << 16) | ((uint32_t)h[4] << 24));
+        src = off > 0 ? -off : 0;             // bit 31 set: as corrupt as offset 0
         hl = 5;
       }
-      // a header must lie inside the window (and the input): otherwise the offset absorbs
-      ok = ok && i + hl <= WIN && ip + i + hl <= n;
+      // A header must lie inside the window (and the input): otherwise the offset absorbs.
+      // A copy's source is kept as -offset, so a real copy has a strictly negative source:
+      // offset 0 (and a copy-4 offset past INT_MAX) makes the tag "not ok", the batch stops
+      // before it and the next batch reports the corruption.  A literal must end inside the
+      // input, which also keeps `nx` below from overflowing on a length field near INT_MAX.
+      // (This form of the test costs nothing measurable; folding it differently cost 1-4 % of
+      // the inflate time.)
+      ok = ok && i + hl <= WIN && ip + i + hl <= n && (kind == 0 ? l <= n - src : src < 0);
       s_len[w][i] = l;
       s_srcw[w][i] = src;
       // a target beyond the window saturates at WIN (16 bits): only "< WIN" is ever tested,
@@ -252,8 +261,8 @@ __device__ void snappy_wave(const uint8_t* __restrict__ base, int64_t ib, int n,
     const int st = incl - l;
     const int total = __shfl(incl, cnt - 1, 64);
     const int nextpos = __shfl(mine ? s_skip[w][pos] : 0, cnt - 1, 64);
-    // a copy may not reach before the output start; literals must end inside the input
-    const bool bad = mine && (src < 0 ? (-src > op + st) : (src + l > n));
+    // a copy may not reach before the output start (literals were held to the input above)
+    const bool bad = mine && src < 0 && -src > op + st;
     if (__ballot(bad) != 0ull || op + total > cap) {
       if (lane == 0) atomicOr(status, kErrCorrupt);
       return;
@@ -783,6 +792,7 @@ int hs_pq_decode_pages(const uint8_t* raw, uint8_t* scratch, const HsPqPage* pag
 }
 
 int hs_pq_page_struct_size() { return (int)sizeof(HsPqPage); }
+int hs_pq_snappy_window() { return HS_SNAPPY_WIN; }
 
 // Expand value runs into `out` (elem_bytes 4 or 8).  dict_off < 0: the chunk has no dictionary
 // (then every run must be PLAIN).  Returns a HIP error code.

@@ -1388,3 +1388,11 @@ def zone_prune(maps, n: int, zone_rows: int, constraints):
                              hi, nc, NL.ptr(ws), NL.ptr(rstart), NL.ptr(rlen), NL.ptr(counts),
                              NL.stream_ptr()), "hs_zone_prune")
     return rstart[:nz], rlen[:nz], counts
+
+
+# ------------------------------------------------------------------------------------------------
+# Parquet page decode (csrc/kernels/parquet_decode.hip; driven from io/native_parquet.py)
+# ------------------------------------------------------------------------------------------------
+def pq_snappy_window() -> int:
+    """Input bytes one wavefront parses per Snappy batch."""
+    return int(NL.lib().hs_pq_snappy_window())
