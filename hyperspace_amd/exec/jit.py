@@ -20,6 +20,7 @@ Kernel arguments are one by-value struct whose fields are all 8 bytes wide, pack
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import re
@@ -459,6 +460,17 @@ __device__ __forceinline__ u64 hs_f32key(float f) {
 """
 
 
+def _kernel(name: str, args: Args, body: List[str], lds: int = 0, tdefs=(), attrs: str = "",
+            block: int = BLOCK, prelude: str = "") -> Kernel:
+    """A generated kernel's translation unit: the prelude (and the ``prelude`` of its own), the
+    ``Args`` struct as it stands now (so after the last slot was added), file-scope definitions
+    ``tdefs``, and ``body`` as the kernel function."""
+    src = (_PRELUDE + prelude + args.struct_src() + "".join(t + "\n" for t in tdefs) +
+           f'extern "C" __global__ __launch_bounds__({block}){attrs} void {name}(Args a) {{\n' +
+           "\n".join(body) + "\n}\n")
+    return Kernel(src, name, args, lds, block)
+
+
 def _ident(kind: int) -> str:
     return "__builtin_inf()" if kind == NL.AK_MIN else (
         "-__builtin_inf()" if kind == NL.AK_MAX else "0.0")
@@ -703,6 +715,19 @@ class _Gen:
         els = self.a.add("d", f"E{i}", "double")
         return f"(({g}) ? ({v}) : {els})", (f"(!({g}) || ({ok}))" if ok else "true")
 
+    def group_index(self, slot: int, it, pass_var: str, ind: str, names=None) -> List[str]:
+        """The group index of batch item ``it`` from its group key registers ``x<slot>_<it>`` /
+        ``n<slot>_<it>``: ``gl`` = key - group_base, ``pass_var`` narrowed to the rows whose key
+        is valid and in [0, num_groups), ``gi`` = the row's group (0 where it does not pass).
+        ``names``: (gl, gi) where they are not ``gl<it>`` / ``gi<it>``."""
+        gl, gi = names or (f"gl{it}", f"gi{it}")
+        base = self.a.add("q", "group_base", "long long")
+        ng = self.a.add("q", "num_groups", "long long")
+        ok = f"n{slot}_{it}" if self.cols[slot][1] else "true"
+        return [f"{ind}const i64 {gl} = (i64)x{slot}_{it} - {base};",
+                f"{ind}{pass_var} = {pass_var} && {ok} && {gl} >= 0 && {gl} < {ng};",
+                f"{ind}const int {gi} = {pass_var} ? (int){gl} : 0;"]
+
 
 def _sum_only_slots(preds, aggs, group_col: int = -1, cols=None) -> frozenset:
     """Slots whose decoded value is read only as a term of SUM / COUNT aggregates: it may carry
@@ -775,6 +800,13 @@ def aggs_of(p) -> list:
 
 def has_guards(p) -> bool:
     return any(p.aggs[i].pad for i in range(p.naggs))
+
+
+def _preds_shape(p, lo: int, hi: int) -> tuple:
+    """The part of a kernel's shape key that ``p.preds[lo:hi]`` make (their literals are kernel
+    arguments and stay out of it)."""
+    return tuple((q.kind, q.op, q.col, q.col2, q.group)
+                 for q in (p.preds[k] for k in range(lo, hi)))
 
 
 def aggs_shape(p) -> tuple:
@@ -891,6 +923,92 @@ def _common_args(args: Args) -> None:
     for n in ("psum", "pmin", "pmax"):
         args.add("p", n, "double*")
     args.add("p", "pcnt", "long long*")
+
+
+def _range_args(args: Args) -> Args:
+    """The row ranges and their tile prefix: the first slots of the streaming kernels."""
+    for n in ("rstart", "rlen", "tile_prefix"):
+        args.add("p", n, "const long long*")
+    return args
+
+
+class _Stream:
+    """What the streaming kernels' generators share (``_ScanAgg``, ``_JoinIndex``,
+    ``gen_pred_bitmap``, ``jit_runs.gen_run_scan``; ``gen_merge_join_agg`` for its tile loops):
+    the argument struct, the column descriptions, the first right-side slot ``split``, the slots
+    decoded with a reciprocal, the tile geometry (``NI`` rows per thread, ``T`` rows per tile,
+    ``ind`` the tile body's indent) and ``lds``, the kernel's LDS declarations, which ``finish``
+    emits in one place ahead of the body.  A builder that accumulates sets ``aggs``,
+    ``group_col`` / ``grouped`` and ``allslots``.  Stages add slots to ``args`` as they emit, and
+    the slot order is the ``Args`` struct - part of the source text, which the ahead-of-time code
+    objects are looked up by - so the order in which a driver calls its stages is fixed."""
+
+    def __init__(self, args: Args, cols, split: int, approx, NI: int,  # noqa: N803
+                 block: int = BLOCK):
+        self.args, self.cols, self.split, self.approx = args, cols, split, approx
+        self.NI, self.block, self.T, self.ind = NI, block, block * NI, "    "
+        self.lds: List[str] = []
+
+    def gen(self, lrow: str, rrow: str = None) -> _Gen:
+        """The expression builder over left row ``lrow`` / right row ``rrow`` (default: same)."""
+        return _Gen(self.args, self.cols, self.split, (lrow, rrow or lrow), self.approx, True)
+
+    def scalar_rows(self) -> List[str]:
+        """Row mapping of a strided tile: item k of a thread is the tile's row k * block +
+        threadIdx.x; items past the range's end are inactive and read the tile's first row."""
+        ind, B = self.ind, self.block  # noqa: N806
+        b = ["    const i64 tb0 = a.rstart[r] + off;",
+             f"    const i64 rows = a.rlen[r] - off < {self.T} ? a.rlen[r] - off : {self.T};"]
+        for it in range(self.NI):
+            b += [f"{ind}const bool act{it} = {it * B} + (i64)threadIdx.x < rows;",
+                  f"{ind}const i64 row{it} = tb0 + (act{it} ? {it * B} + (i64)threadIdx.x : 0);"]
+        return b
+
+    def group_index(self, gen: _Gen, it, pass_var: str) -> List[str]:
+        """``_Gen.group_index`` of the kernel's group column ``group_col`` at the tile indent."""
+        return gen.group_index(self.group_col, it, pass_var, self.ind)
+
+    def branch_free_tail(self, slots, with_j: bool, hk=None) -> List[str]:
+        """Phase 3 without lists: the aggregate inputs and group column ``slots`` of every item,
+        where rows that failed read the tile's first row (``with_j``: and right row 0) instead of
+        branching around the load, then group index and accumulation.  Adds the columns' and the
+        aggregates' term slots."""
+        NI, ind, b = range(self.NI), self.ind, []  # noqa: N806
+        gens = [self.gen(f"lq{it}", f"jq{it}" if with_j else None) for it in NI]
+        for it in NI if slots else ():
+            b.append(f"{ind}const i64 lq{it} = pass{it} ? row{it} : tb0;")
+            if with_j:
+                b.append(f"{ind}const i64 jq{it} = pass{it} ? j{it} : 0;")
+        for it in NI:
+            for s in slots:
+                _uload(gens[it], s, it, b, ind)
+        for it, g in zip(NI, gens):
+            if self.grouped:
+                b += self.group_index(g, it, f"pass{it}")
+            acc = JH._hash_accumulate(g, self.aggs, hk, f"pass{it}", ind) if hk is not None else \
+                _accumulate(g, self.aggs, self.grouped, f"pass{it}", f"gi{it}", ind)
+            b += [_rename(x, self.allslots, it) for x in acc]
+        return b
+
+    def finish(self, name: str, body: List[str], lds_bytes: int = 0, prelude: str = "") -> Kernel:
+        """The kernel: ``lds`` and ``body`` wrapped by ``_kernel``."""
+        return _kernel(name, self.args, self.lds + body, lds_bytes, block=self.block,
+                       prelude=prelude)
+
+
+# What ``_vec_tiles`` loads per tile.  A load fills the array ``<name>v`` of C type ``ctype`` from
+# ``ptr``: the thread's NI consecutive column elements, or its ``words`` dwords of a row-packed
+# stream (``words`` per NI rows; read lane-coalesced where ``lane`` names the lane index).  A
+# tile: ``loads``; per-thread ``scalars`` = (name, C type, expression over ``G0``) loaded with
+# them; per-tile ``tscalars`` = (name, C type, expression over ``{t}``); ``full`` = what the full
+# tiles load instead of ``loads``.
+_Load = collections.namedtuple("_Load", "name ctype ptr words lane", defaults=(0, None))
+_Tile = collections.namedtuple("_Tile", "loads scalars tscalars full", defaults=((), (), None))
+# what varies between ``_compacted_tail``'s callers: whether the list carries a ``j`` per row
+# (``j_fmt`` names it), ``j`` being the row's group index itself (``jgroup``), hash-mode
+# grouping (``hk``)
+_Tail = collections.namedtuple("_Tail", "with_j j_fmt jgroup hk",
+                               defaults=(True, "j{it}", False, None))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1087,52 +1205,11 @@ def _pack_extract(lay: RowPack, slot: int, it: int, arr: str) -> str:
     return f"((unsigned)((((u64){arr}[{k + 1}] << 32) | {arr}[{k}]) >> {sh}){mask})"
 
 
-def _pack_decode(b: List[str], gen: "_Gen", lay: RowPack, slot: int, it, field: str,
-                 ind: str) -> None:
+def _pack_regs(gen: "_Gen", slot: int, it, field: str) -> List[str]:
     """The registers ``_uload`` / ``_vec_load_slots`` make for column ``slot`` / item ``it``
     from its packed ``field`` expression: adding the offset back gives the stored code."""
-    ct = _CTYPE[gen.cols[slot][0]]
     off = gen.a.add("q", f"PO{slot}", "long long")
-    b.append(f"{ind}const int r{slot}_{it} = (int)({field} + (unsigned){off});")
-    if gen.cols[slot][2][1]:
-        base = gen.a.add("q", f"B{slot}", "long long")
-        b.append(f"{ind}const i64 q{slot}_{it} = {base} + (i64)r{slot}_{it};")
-    b.append(f"{ind}const {ct} x{slot}_{it} = {gen.decode(slot, f'r{slot}_{it}')};")
-
-
-def _packed_tail(args, cols, approx, aggs, allslots, lay: RowPack, NI: int, ind: str) -> List[str]:
-    """``_compacted_tail`` of a row-packed full tile: the per-wavefront list (same ballot
-    positions) holds each passing row's aggregate-input fields instead of its row offset, so the
-    walk decodes them from LDS - the same values in the same lanes and order, and no gather."""
-    tail = list(dict.fromkeys(_agg_slots(aggs)))
-    epos, o = {}, 0
-    for s in tail:
-        epos[s] = o
-        o += lay.field(s)[1]
-    b = [f"{ind}int wtot = 0;"]
-    for it in range(NI):
-        ent = " | ".join(f"((crow_t)f{s}_{it} << {epos[s]})" if epos[s] else f"(crow_t)f{s}_{it}"
-                         for s in tail) or "(crow_t)0"
-        b += [f"{ind}{{ const bool pz = pass{it}; const u64 bm = __ballot(pz);",
-              f"{ind}  const int pos{it} = wtot + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), "
-              f"__builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));",
-              f"{ind}  if (pz) {{ crow_s[wv][pos{it}] = {ent}; }}",
-              f"{ind}  wtot += __popcll(bm); }}"]
-    b += [f"{ind}{_wave_sync()}",
-          f"{ind}for (int cb = 0; cb < wtot; cb += 64) {{",
-          f"{ind}  const int ce = cb + cln;",
-          f"{ind}  bool cok = ce < wtot;",
-          f"{ind}  const crow_t cent = cok ? crow_s[wv][ce] : (crow_t)0;"]
-    ind2 = ind + "  "
-    g = _Gen(args, cols, NL.MAX_COLS, ("crow", "crow"), approx, True)
-    for s in tail:
-        bits = lay.field(s)[1]
-        sh = f"(cent >> {epos[s]})" if epos[s] else "cent"
-        mask = "" if bits == 32 else f" & {hex((1 << bits) - 1)}u"
-        _pack_decode(b, g, lay, s, "c", f"((unsigned){sh}{mask})", ind2)
-    b += [_rename(x, allslots, "c") for x in _accumulate(g, aggs, False, "cok", "gic", ind2)]
-    b += [f"{ind}}}", f"{ind}{_wave_sync()}"]
-    return b
+    return _item_regs(gen, slot, it, f"r{slot}_{it}", code=f"(int)({field} + (unsigned){off})")[0]
 
 
 def _pack_list_t(lay: RowPack, aggs) -> str:
@@ -1147,11 +1224,133 @@ def scan_agg_shape(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None,
     if pack is not None:
         return scan_agg_shape(p, compacts, vec, hk) + (("pack", SCAN_PACK_LDS) + tuple(pack),)
     cols = tuple(sorted(_col_specs(p, compacts).items()))
-    preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
-                   p.preds[k].group) for k in range(p.npreds))
+    preds = _preds_shape(p, 0, p.npreds)
     aggs = aggs_shape(p)
     return ("scan_agg", cols, preds, aggs, p.group_col, SCAN_ITEMS, SCAN_EAGER, vec,
             SCAN_COMPACT, WAVE_SYNC, VEC_PREFETCH, hk.shape() if hk is not None else None)
+
+
+class _ScanAgg(_Stream):
+    """The builder behind ``gen_scan_agg``: one method per phase of a tile - ``pred_loads``,
+    ``passes``, then ``packed_tail`` / ``_compacted_tail`` / ``branch_free_tail`` (which
+    accumulate) - which ``tile`` calls in that order for each kind of tile."""
+
+    def __init__(self, p: NL.ScanParams, compacts, vec: int, hk, pack: Optional[RowPack]):
+        args = _range_args(Args())
+        args.add("q", "R", "long long")
+        _common_args(args)
+        cols = _col_specs(p, compacts)
+        self.preds = preds = [(k, p.preds[k]) for k in range(p.npreds)]
+        self.aggs = aggs = aggs_of(p)
+        self.group_col, self.grouped = p.group_col, p.group_col >= 0
+        assert not (self.grouped and hk is not None)
+        pslots = _pred_slots(preds)
+        aslots = [s for s in _agg_slots(aggs) if s not in pslots]
+        if self.grouped and p.group_col not in pslots and p.group_col not in aslots:
+            aslots.append(p.group_col)
+        for s in (hk.slots if hk is not None else []):
+            if s not in pslots and s not in aslots:
+                aslots.append(s)
+        if SCAN_EAGER:
+            pslots, aslots = pslots + aslots, []
+        self.pslots, self.aslots, self.allslots = pslots, aslots, pslots + aslots
+        approx = _sum_only_slots(preds, aggs, p.group_col, cols) - set(hk.slots if hk else [])
+        super().__init__(args, cols, NL.MAX_COLS, approx, vec or SCAN_ITEMS)
+        if vec:
+            args.add("q", "nrows", "long long")
+        self.hk, self.pack = hk, pack
+        self.g0 = self.gen("row0")
+        self.compact = compact = SCAN_COMPACT and bool(aslots)
+        W = BLOCK // 64  # noqa: N806
+        if pack is not None:
+            assert vec == 8 and not self.grouped and hk is None and (compact or not aslots)
+            if SCAN_PACK_LDS:
+                self.lds.append(f"  __shared__ unsigned pks_s[{W}][{64 * pack.words}];")
+        if compact:
+            lt = _pack_list_t(pack, aggs) if pack is not None else _crow_t(self.T)
+            self.lds.append(f"  typedef {lt} crow_t; __shared__ crow_t "
+                            f"crow_s[{W}][{64 * self.NI}];")
+        if self.lds:
+            self.lds.append("  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;")
+
+    def tile(self, b: List[str], full: Optional[bool]) -> None:
+        """One tile's work; ``full`` = vectorized full tile / vectorized last tile / None
+        (strided)."""
+        packed = bool(full) and self.pack is not None
+        b += self.pred_loads(full)
+        b += self.passes()
+        if self.compact and packed:
+            b += self.packed_tail()
+        elif self.compact:
+            b += _compacted_tail(self, self.aggs, self.group_col, self.allslots,
+                                 _Tail(with_j=False, hk=self.hk))
+        else:
+            b += self.branch_free_tail(self.aslots, False, self.hk)
+
+    def pred_loads(self, full: Optional[bool]) -> List[str]:
+        """Phase 1: the registers of the predicate columns of every item - from the fields of
+        the packed dwords or from the raw vector arrays the tile loop loaded, or loaded here at
+        the strided rows.  Adds PO<slot> / B<slot> and the decodes' slots, or the columns'."""
+        NI, ind, pack, b = self.NI, self.ind, self.pack, []  # noqa: N806
+        if full and pack is not None:
+            tail = _agg_slots(self.aggs) if self.compact else []
+            if SCAN_PACK_LDS:
+                b.append(f"{ind}hs_pk_t<{pack.words}>(pks_s[wv], cln, pkv);")
+            for it in range(NI):
+                for s in dict.fromkeys(self.pslots + tail):
+                    b.append(f"{ind}const unsigned f{s}_{it} = "
+                             f"{_pack_extract(pack, s, it, 'pkv')};")
+                for s in self.pslots:
+                    b += [ind + x for x in _pack_regs(self.g0, s, it, f"f{s}_{it}")]
+        elif full is not None:
+            _vec_load_slots(b, self.g0, self.pslots, NI, ind)
+        else:
+            b += self.scalar_rows()
+            for it in range(NI):
+                for s in self.pslots:
+                    _uload(self.gen(f"row{it}"), s, it, b, ind)
+        return b
+
+    def passes(self) -> List[str]:
+        """The row filter per item.  Adds the predicates' literal slots."""
+        return [f"{self.ind}bool pass{it} = act{it} && "
+                f"{_rename(self.gen(f'row{it}').cnf(self.preds), self.allslots, it)};"
+                for it in range(self.NI)]
+
+    def packed_tail(self) -> List[str]:
+        """``_compacted_tail`` of a row-packed full tile: the per-wavefront list (same ballot
+        positions) holds each passing row's aggregate-input fields instead of its row offset, so
+        the walk decodes them from LDS - the same values in the same lanes and order, and no
+        gather."""
+        lay, ind = self.pack, self.ind
+        tail = list(dict.fromkeys(_agg_slots(self.aggs)))
+        epos, o = {}, 0
+        for s in tail:
+            epos[s] = o
+            o += lay.field(s)[1]
+        b = [f"{ind}int wtot = 0;"]
+        for it in range(self.NI):
+            ent = " | ".join(f"((crow_t)f{s}_{it} << {epos[s]})" if epos[s] else
+                             f"(crow_t)f{s}_{it}" for s in tail) or "(crow_t)0"
+            b += _list_pos(ind, it, f"pass{it}")
+            b += [f"{ind}  if (pz) {{ crow_s[wv][pos{it}] = {ent}; }}",
+                  f"{ind}  wtot += __popcll(bm); }}"]
+        b += [f"{ind}{_wave_sync()}",
+              f"{ind}for (int cb = 0; cb < wtot; cb += 64) {{",
+              f"{ind}  const int ce = cb + cln;",
+              f"{ind}  bool cok = ce < wtot;",
+              f"{ind}  const crow_t cent = cok ? crow_s[wv][ce] : (crow_t)0;"]
+        ind2 = ind + "  "
+        g = self.gen("crow")
+        for s in tail:
+            bits = lay.field(s)[1]
+            sh = f"(cent >> {epos[s]})" if epos[s] else "cent"
+            mask = "" if bits == 32 else f" & {hex((1 << bits) - 1)}u"
+            b += [ind2 + x for x in _pack_regs(g, s, "c", f"((unsigned){sh}{mask})")]
+        b += [_rename(x, self.allslots, "c")
+              for x in _accumulate(g, self.aggs, False, "cok", "gic", ind2)]
+        b += [f"{ind}}}", f"{ind}{_wave_sync()}"]
+        return b
 
 
 def gen_scan_agg(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None,
@@ -1166,127 +1365,24 @@ def gen_scan_agg(p: NL.ScanParams, compacts=None, vec: int = 0, hk=None,
     ``pack`` (``scan_pack_layout``): the full tiles read the thread's 8 rows as ``pack.words``
     dwords of the row-packed copy (argument ``PK``) and list a passing row's aggregate-input
     fields instead of its offset; the last, partial tiles keep the element loads of the
-    columns.  Same partials bit for bit."""
-    args = Args()
-    for n, ct in (("rstart", "const long long*"), ("rlen", "const long long*"),
-                  ("tile_prefix", "const long long*")):
-        args.add("p", n, ct)
-    args.add("q", "R", "long long")
-    _common_args(args)
-    cols = _col_specs(p, compacts)
-    preds = [(k, p.preds[k]) for k in range(p.npreds)]
-    aggs = aggs_of(p)
-    grouped = p.group_col >= 0
-    assert not (grouped and hk is not None)
-    pslots = _pred_slots(preds)
-    aslots = [s for s in _agg_slots(aggs) if s not in pslots]
-    if grouped and p.group_col not in pslots and p.group_col not in aslots:
-        aslots.append(p.group_col)
-    for s in (hk.slots if hk is not None else []):
-        if s not in pslots and s not in aslots:
-            aslots.append(s)
-    if SCAN_EAGER:
-        pslots, aslots = pslots + aslots, []
-    allslots = pslots + aslots
-    approx = _sum_only_slots(preds, aggs, p.group_col, cols) - set(hk.slots if hk else [])
-    NI = vec or SCAN_ITEMS
-    T = BLOCK * NI
+    columns.  Same partials bit for bit.
+
+    The driver of ``_ScanAgg``.  The struct: the header's slots, nrows, the group table's, PK,
+    the streamed columns', then what the tile's phases add."""
+    s = _ScanAgg(p, compacts, vec, hk, pack)
+    b = _acc_decls(s.aggs, s.grouped, s.args)
     if vec:
-        args.add("q", "nrows", "long long")
-    b: List[str] = []
-    b += _acc_decls(aggs, grouped, args)
-    if grouped:
-        base = args.add("q", "group_base", "long long")
-        ng = args.add("q", "num_groups", "long long")
-    ind = "    "
-    g0_ = _Gen(args, cols, NL.MAX_COLS, ("row0", "row0"), approx, True)
-    compact = SCAN_COMPACT and bool(aslots)
-
-    def body(b: List[str], full: Optional[bool]) -> None:
-        """Tile body; ``full`` = vectorized full tile / vectorized last tile / None (scalar)."""
-        if full and pack is not None:     # fields of the packed dwords the tile loop loaded
-            tail = _agg_slots(aggs) if compact else []
-            if SCAN_PACK_LDS:
-                b.append(f"{ind}hs_pk_t<{pack.words}>(pks_s[wv], cln, pkv);")
-            for it in range(NI):
-                for s in dict.fromkeys(pslots + tail):
-                    b.append(f"{ind}const unsigned f{s}_{it} = "
-                             f"{_pack_extract(pack, s, it, 'pkv')};")
-                for s in pslots:
-                    _pack_decode(b, g0_, pack, s, it, f"f{s}_{it}", ind)
-        elif full is not None:     # raw vector arrays come from the tile loop (_vec_tiles)
-            _vec_load_slots(b, g0_, pslots, NI, ind)
-        else:
-            b.extend(["    const i64 tb0 = a.rstart[r] + off;",
-                      f"    const i64 rows = a.rlen[r] - off < {T} ? a.rlen[r] - off : {T};"])
-            for it in range(NI):
-                b.extend([f"{ind}const bool act{it} = {it * BLOCK} + (i64)threadIdx.x < rows;",
-                          f"{ind}const i64 row{it} = tb0 + (act{it} ? {it * BLOCK} + (i64)threadIdx.x : 0);"])
-            for it in range(NI):
-                g1 = _Gen(args, cols, NL.MAX_COLS, (f"row{it}", f"row{it}"), approx, True)
-                for s in pslots:
-                    _uload(g1, s, it, b, ind)
-        for it in range(NI):
-            g1 = _Gen(args, cols, NL.MAX_COLS, (f"row{it}", f"row{it}"), approx, True)
-            b.append(f"{ind}bool pass{it} = act{it} && {_rename(g1.cnf(preds), allslots, it)};")
-        if compact and full and pack is not None:
-            b.extend(_packed_tail(args, cols, approx, aggs, allslots, pack, NI, ind))
-            return
-        if compact:
-            b.extend(_compacted_tail(args, cols, NL.MAX_COLS, approx, aggs, grouped, p.group_col,
-                                     aslots, allslots, NI, ind, with_j=False, hk=hk))
-            return
-        if aslots:
-            for it in range(NI):
-                b.append(f"{ind}const i64 lq{it} = pass{it} ? row{it} : tb0;")
-            for it in range(NI):
-                g2 = _Gen(args, cols, NL.MAX_COLS, (f"lq{it}", f"lq{it}"), approx, True)
-                for s in aslots:
-                    _uload(g2, s, it, b, ind)
-        for it in range(NI):
-            g2 = _Gen(args, cols, NL.MAX_COLS, (f"row{it}", f"row{it}"), approx, True)
-            gvar = f"gi{it}"
-            if grouped:
-                g = p.group_col
-                b.append(f"{ind}const i64 gl{it} = (i64){_rename(f'x{g}', allslots, it)} - {base};")
-                b.append(f"{ind}pass{it} = pass{it} && {_rename(g2.ok(g), allslots, it)} && "
-                         f"gl{it} >= 0 && gl{it} < {ng};")
-                b.append(f"{ind}const int {gvar} = pass{it} ? (int)gl{it} : 0;")
-            if hk is not None:
-                b.extend(_rename(x, allslots, it) for x in
-                         JH._hash_accumulate(g2, aggs, hk, f"pass{it}", ind))
-                continue
-            b.extend(_rename(x, allslots, it) for x in
-                     _accumulate(g2, aggs, grouped, f"pass{it}", gvar, ind))
-
-    if pack is not None:
-        assert vec == 8 and NI == 8 and not grouped and hk is None and (compact or not aslots)
-        pk = args.add("p", "PK", "const unsigned*")
-        _vec_tiles(b, T, NI, ind, _vec_loads(g0_, pslots), [], body,
-                   full_loads=[("pk", "unsigned", pk, pack.words) +
-                               (("cln",) if SCAN_PACK_LDS else ())])
-    elif vec:
-        _vec_tiles(b, T, NI, ind, _vec_loads(g0_, pslots), [], body)
+        full = pack and [_Load("pk", "unsigned", s.args.add("p", "PK", "const unsigned*"),
+                               pack.words, "cln" if SCAN_PACK_LDS else None)]
+        _vec_tiles(s, b, s.tile, _Tile(_vec_loads(s.g0, s.pslots), full=full))
     else:
-        _tile_loop(b, T, NI, 0)
-        body(b, None)
+        _tile_loop(b, s.T, s.NI, 0)
+        s.tile(b, None)
     b += ["  }"]
     if hk is None:
-        b += _flush(aggs, grouped)
-    if compact:
-        W = BLOCK // 64
-        lt = _pack_list_t(pack, aggs) if pack is not None else _crow_t(T)
-        b.insert(0, f"  typedef {lt} crow_t; __shared__ crow_t crow_s[{W}][{64 * NI}];")
-        b.insert(1, "  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;")
-    if pack is not None and SCAN_PACK_LDS:
-        if not compact:
-            b.insert(0, "  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;")
-        b.insert(0, f"  __shared__ unsigned pks_s[{BLOCK // 64}][{64 * pack.words}];")
-    src = (_PRELUDE + (_PACK_PRELUDE if pack is not None else "") + args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({BLOCK}) void hs_jit_scan_agg(Args a) {{\n' +
-           "\n".join(b) + "\n}\n")
-    lds = (len(aggs) * p.num_groups * 32) if grouped else 0
-    return Kernel(src, "hs_jit_scan_agg", args, lds)
+        b += _flush(s.aggs, s.grouped)
+    return s.finish("hs_jit_scan_agg", b, (len(s.aggs) * p.num_groups * 32) if s.grouped else 0,
+                    _PACK_PRELUDE if pack is not None else "")
 
 
 def scan_agg_values(p: NL.ScanParams, rstart, rlen, tile_prefix, parts,
@@ -1427,8 +1523,7 @@ def fill_preds_aggs(v: Dict[str, object], preds, aggs, compacts=None) -> None:
 # ------------------------------------------------------------------------------------------------
 def join_agg_shape(p: NL.JoinParams, compacts=None) -> tuple:
     cols = tuple(sorted(_col_specs(p, compacts).items()))
-    preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
-                   p.preds[k].group) for k in range(p.npreds))
+    preds = _preds_shape(p, 0, p.npreds)
     aggs = aggs_shape(p)
     return ("join_agg", cols, preds, p.nlp, aggs, p.group_col, p.lkey, p.rkey, p.key_is_float,
             JOIN_ITEMS, JOIN_LDS_KEYS, JOIN_EAGER, JOIN_BLOCK, JOIN_STAGE_RIGHT, JOIN_PIPELINE,
@@ -1633,27 +1728,17 @@ def gen_join_agg(p: NL.JoinParams, compacts=None) -> Kernel:
             for s in left_late:
                 g2.load(s, f"ps{it}", blk, "      ")
             b += [_rename(x, left_late, it) for x in blk]
-        gvar = f"gi{it}"
         if grouped:
-            g = p.group_col
-            base = args.add("q", "group_base", "long long")
-            ng = args.add("q", "num_groups", "long long")
-            b.append(f"      const i64 gl{it} = (i64)x{g}_{it} - {base};")
-            okg = f"n{g}_{it}" if cols[g][1] else "true"
-            b.append(f"      ps{it} = ps{it} && {okg} && gl{it} >= 0 && gl{it} < {ng};")
-            b.append(f"      const int {gvar} = ps{it} ? (int)gl{it} : 0;")
-        acc = _accumulate(g2, aggs, grouped, f"ps{it}", gvar, "      ")
+            b += g2.group_index(p.group_col, it, f"ps{it}", "      ")
+        acc = _accumulate(g2, aggs, grouped, f"ps{it}", f"gi{it}", "      ")
         b += [_rename(x, allslots, it) for x in acc]
         b += [f"      if (m{it}) {{ ++j{it};",
               f"        m{it} = j{it} < re && (staged ? skeys[j{it} - rs] : "
               f"{_key_expr(gen.value(rk, f'j{it}'), fl)}) == k{it}; }}"]
     b += ["    }", "    __syncthreads();", "  }"]
     b += _flush(aggs, grouped, BLOCK)
-    src = (_PRELUDE + args.struct_src() + "\n".join(pre) +
-           f'extern "C" __global__ __launch_bounds__({BLOCK}) void hs_jit_join_agg(Args a) {{\n' +
-           "\n".join(b) + "\n}\n")
     lds = (len(aggs) * p.num_groups * 32) if grouped else 0
-    return Kernel(src, "hs_jit_join_agg", args, lds, BLOCK)
+    return _kernel("hs_jit_join_agg", args, b, lds, tdefs=pre, block=BLOCK)
 
 
 def _pipeline_tiles(b: List[str], batch: List[str], fields, NI: int, BLOCK: int,  # noqa: N803
@@ -1674,7 +1759,7 @@ def _pipeline_tiles(b: List[str], batch: List[str], fields, NI: int, BLOCK: int,
            "i64 rs, i64 re) {",
            f"  const bool staged = re - rs <= {LDS_KEYS};"]
     pre += [x.replace("    ", "  ", 1) for x in body_la + batch]
-    pre += ["  Batch B_;"] + [f"  B_.{n} = {n};" for _, n in fields] + ["  return B_;", "}", ""]
+    pre += ["  Batch B_;"] + [f"  B_.{n} = {n};" for _, n in fields] + ["  return B_;", "}"]
     out = list(head)
     out += ["  i64 c_row0 = n_row0, c_rows = n_rows, c_rs = n_rs, c_re = n_re;",
             "  if (t0 + 1 < t1) { n_row0 = a.spans[4 * t0 + 4]; n_rows = a.spans[4 * t0 + 5];",
@@ -1706,7 +1791,6 @@ def _valid_expr(gen: _Gen, slot: int, row: str) -> str:
 
 def _rename(line: str, slots, it: int) -> str:
     """Suffix per-row-slot variables x<s>/n<s> with the batch item index."""
-    import re
     for s in sorted(set(slots), reverse=True):
         line = re.sub(rf"\b([xnqr]){s}\b", rf"\g<1>{s}_{it}", line)
     return line
@@ -1721,46 +1805,55 @@ _SOFF: Dict[int, tuple] = {}
 def join_index_agg_shape(p: NL.JoinParams, compacts=None, vec: int = 0, jw: int = 4,
                          jlog: int = 0, stage: bool = False, bitmap: bool = False) -> tuple:
     cols = tuple(sorted(_col_specs(p, compacts).items()))
-    preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
-                   p.preds[k].group) for k in range(p.npreds))
+    preds = _preds_shape(p, 0, p.npreds)
     aggs = aggs_shape(p)
     return ("join_index_agg", cols, preds, p.nlp, aggs, p.group_col, JI_ITEMS, vec, BLOCK, jw,
             jlog, JI_COMPACT, WAVE_SYNC, bool(stage and vec), bool(bitmap), VEC_PREFETCH)
 
 
+def _item_regs(gen: _Gen, slot: int, it, raw: str, valid=None, code: str = None,
+               assign: str = "") -> Tuple[List[str], List[Tuple[str, str]]]:
+    """The registers of column ``slot`` of batch item ``it`` from its stored element ``raw``:
+    ``x`` the logical value; ``n`` its validity (nullable columns); ``r`` the stored code as an
+    int (compact columns: what the code-bound predicates read) and ``q`` = base + code
+    (decimal-scaled ones: the integer predicates).  ``valid``: the validity byte's expression, or
+    a callable giving it (called after the decode, where it adds an argument slot).  ``code``: the
+    code's own expression, where ``raw`` names the ``r`` register it makes (a packed field).
+
+    Declares them (``const T name = v;``) or, with ``assign`` a name prefix, assigns
+    (``<prefix>name = v;``).  Returns the statements, without indent, and [(name, C type)] in
+    the order x, n, r, q.  Adds B<slot> and what the decode adds, in statement order r, q, x."""
+    t, has_valid, enc = gen.cols[slot]
+    sfx = f"{slot}_{it}"
+    regs = []
+    if enc:
+        regs.append((f"r{sfx}", "int", code or f"(int){raw}"))
+        if enc[1]:
+            base = gen.a.add("q", f"B{slot}", "long long")
+            regs.append((f"q{sfx}", "i64", f"{base} + (i64){raw}"))
+    regs.append((f"x{sfx}", _CTYPE[t], gen.decode(slot, raw)))
+    if has_valid:
+        regs.append((f"n{sfx}", "bool", f"{valid() if callable(valid) else valid} != 0"))
+    stmts = [f"{assign}{n} = {v};" if assign else f"const {ct} {n} = {v};" for n, ct, v in regs]
+    return stmts, [(n, ct) for n, ct, _ in sorted(regs, key=lambda r: "xnrq".index(r[0][0]))]
+
+
 def _uload_raw(gen: _Gen, slot: int, it, raw: str, vraw: str, out: List[str], ind: str) -> None:
     """``_uload``'s registers for column ``slot`` / item ``it`` from an already loaded stored
     element ``raw`` (and validity byte ``vraw``)."""
-    ct = _CTYPE[gen.cols[slot][0]]
-    enc = gen.cols[slot][2]
-    if enc:
-        out.append(f"{ind}const int r{slot}_{it} = (int){raw};")
-        if enc[1]:
-            base = gen.a.add("q", f"B{slot}", "long long")
-            out.append(f"{ind}const i64 q{slot}_{it} = {base} + (i64){raw};")
-    out.append(f"{ind}const {ct} x{slot}_{it} = {gen.decode(slot, raw)};")
-    if gen.cols[slot][1]:
-        out.append(f"{ind}const bool n{slot}_{it} = {vraw} != 0;")
+    out += [ind + x for x in _item_regs(gen, slot, it, raw, vraw)[0]]
 
 
 def _uload(gen: _Gen, slot: int, it: int, out: List[str], ind: str) -> None:
     """Unconditional load of column ``slot`` for batch item ``it`` at the generator's row
     variable (callers redirect rows that do not need the value to an always-valid shared row, so
     the load needs no branch and the wavefront's redirected lanes coalesce into one line)."""
-    ct = _CTYPE[gen.cols[slot][0]]
     r = gen.row(slot)
-    enc = gen.cols[slot][2]
-    if enc:
-        out.append(f"{ind}const {gen.raw_type(slot)} w{slot}_{it} = {gen.ptr(slot)}[{r}];")
-        out.append(f"{ind}const int r{slot}_{it} = (int)w{slot}_{it};")
-        if enc[1]:
-            base = gen.a.add("q", f"B{slot}", "long long")
-            out.append(f"{ind}const i64 q{slot}_{it} = {base} + (i64)w{slot}_{it};")
-        out.append(f"{ind}const {ct} x{slot}_{it} = {gen.decode(slot, f'w{slot}_{it}')};")
-    else:
-        out.append(f"{ind}const {ct} x{slot}_{it} = {gen.value(slot, r)};")
-    if gen.cols[slot][1]:
-        out.append(f"{ind}const bool n{slot}_{it} = {gen.vptr(slot)}[{r}] != 0;")
+    raw = f"{gen.ptr(slot)}[{r}]"
+    if gen.cols[slot][2]:
+        out.append(f"{ind}const {gen.raw_type(slot)} w{slot}_{it} = {raw};")
+        raw = f"w{slot}_{it}"
+    out += [ind + x for x in _item_regs(gen, slot, it, raw, lambda: f"{gen.vptr(slot)}[{r}]")[0]]
 
 
 def _crow_t(T: int) -> str:
@@ -1801,13 +1894,13 @@ def _vec_act(b: List[str], NI: int, ind: str) -> None:
               f"{ind}const i64 row{it} = g0 + {it};"]
 
 
-def _vec_loads(gen: "_Gen", slots, extra=()) -> List[Tuple[str, str, str]]:
-    """(array name, C type, pointer) of every streamed vector load of a tile: ``extra`` raw
-    arrays, the stored elements of ``slots`` and their validity bytes."""
-    loads = list(extra) + [(f"x{s}", gen.raw_type(s), gen.ptr(s)) for s in slots]
+def _vec_loads(gen: "_Gen", slots, extra=()) -> List[_Load]:
+    """Every streamed vector load of a tile: ``extra`` raw arrays, the stored elements of
+    ``slots`` and their validity bytes."""
+    loads = list(extra) + [_Load(f"x{s}", gen.raw_type(s), gen.ptr(s)) for s in slots]
     for s in slots:
         if gen.cols[s][1]:
-            loads.append((f"n{s}", "unsigned char", gen.vptr(s)))
+            loads.append(_Load(f"n{s}", "unsigned char", gen.vptr(s)))
     return loads
 
 
@@ -1821,11 +1914,13 @@ _TILE_HEAD = ["  const i64 ntiles = a.tile_prefix[a.R];",
               "    r = lo; }"]
 
 
-def _tile_loop(b: List[str], T: int, NI: int, vec: int, ind: str = "    ") -> None:
+def _tile_loop(b: List[str], T: int, NI: int, vec: int, ind: str = "    ",  # noqa: N803
+               head: bool = True) -> None:
     """Header of the persistent tile loop of the streaming kernels: each block owns a contiguous
-    run of ``T``-row tiles and ``r`` tracks the row range of the tile.  Vectorized tiles
-    (``vec``) also get the row geometry ``rs re tb0 g0 act<k> row<k>``."""
-    b += _TILE_HEAD
+    run of ``T``-row tiles (``head``: ``_TILE_HEAD``, where the caller has not emitted it) and
+    ``r`` tracks the row range of the tile.  Vectorized tiles (``vec``) also get the row
+    geometry ``rs re tb0 g0 act<k> row<k>``."""
+    b += _TILE_HEAD if head else []
     b += ["  for (i64 t = t0; t < t1; ++t) {",
           "    while (r + 1 < (int)a.R && a.tile_prefix[r + 1] <= t) ++r;",
           f"    const i64 off = (t - a.tile_prefix[r]) * {T};"]
@@ -1833,11 +1928,9 @@ def _tile_loop(b: List[str], T: int, NI: int, vec: int, ind: str = "    ") -> No
         _vec_rows(b, NI, ind)
 
 
-def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
-               tscalars=(), full_loads=None) -> None:
-    """Tile loops of a vectorized streaming kernel (``body(b, mode)`` emits one tile's work;
-    ``loads`` = (name, C type, pointer) vector arrays, ``scalars`` = (name, C type, expression
-    over ``G0``) per-thread values loaded with them).
+def _vec_tiles(st: _Stream, b: List[str], body, tile: _Tile) -> None:
+    """Tile loops of a vectorized streaming kernel over the loads of ``tile`` (``_Tile``);
+    ``body(b, full)`` emits one tile's work.
 
     Tiles that end inside the table (``tb0 + T <= nrows``: every tile but the table's last few)
     read their columns with unconditional aligned vector loads, the rest element-wise, behind a
@@ -1848,26 +1941,26 @@ def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
     at the top of tile t, before t's predicates, gathers and aggregate tail, so each wavefront
     keeps the next tile's stream in flight across this tile's dependent round trips.  Full
     tiles precede partial ones in a block's run, so the pipelined loop runs first and the
-    element-wise loop finishes the run.  ``tscalars`` = (name, C type, expression over ``{t}``)
-    per-tile values (span bounds, run windows) prefetched the same way.
+    element-wise loop finishes the run.  The per-tile values ``tile.tscalars`` (span bounds, run
+    windows) are prefetched the same way.
 
-    ``full_loads`` = what the full tiles load instead of ``loads`` (the partial tiles keep
-    those): (name, "unsigned", pointer, W) entries read the thread's W dwords of a row-packed
-    stream (W dwords per NI rows) into ``<name>v``."""
-    fl = loads if full_loads is None else full_loads
+    ``tile.full``: what the full tiles load instead of ``tile.loads`` (the partial tiles keep
+    those)."""
+    T, NI, ind = st.T, st.NI, st.ind  # noqa: N806
+    loads, scalars, tscalars = tile.loads, tile.scalars, tile.tscalars
+    fl = loads if tile.full is None else tile.full
+    # the per-tile values at ``t`` / the per-thread values at ``g0``, not prefetched
+    at_t = [f"{ind}const {ct} {name} = {expr.format(t='t')};" for name, ct, expr in tscalars]
+    at_g0 = [f"{ind}const {ct} {name} = {expr.replace('G0', 'g0')};" for name, ct, expr in scalars]
     if not VEC_PREFETCH:
         _tile_loop(b, T, NI, 1, ind)
-        for name, ct, expr in tscalars:
-            b.append(f"{ind}const {ct} {name} = {expr.format(t='t')};")
-        b.append(f"{ind}if (tb0 + {T} <= a.nrows) {{")
+        b += at_t + [f"{ind}if (tb0 + {T} <= a.nrows) {{"]
         _vec_issue(b, fl, NI, ind, True)
-        for name, ct, expr in scalars:
-            b.append(f"{ind}const {ct} {name} = {expr.replace('G0', 'g0')};")
+        b += at_g0
         body(b, True)
         b.append(f"{ind}}} else {{")
         _vec_issue(b, loads, NI, ind, False)
-        for name, ct, expr in scalars:
-            b.append(f"{ind}const {ct} {name} = {expr.replace('G0', 'g0')};")
+        b += at_g0
         body(b, False)
         b.append(f"{ind}}}")
         return
@@ -1891,7 +1984,7 @@ def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
 
     b.append("  i64 rsP = 0, reP = 0, tb0P = 0, g0P = 0; bool fullP = false;")
     for e in fl:
-        b.append(f"  {e[1]} {e[0]}vP[{_vec_load_len(e, NI)}];")
+        b.append(f"  {e.ctype} {e.name}vP[{_vec_load_len(e, NI)}];")
     for name, ct, _ in list(scalars) + list(tscalars):
         b.append(f"  {ct} {name}P = ({ct})0;")
     b.append("  i64 t = t0;")
@@ -1901,8 +1994,8 @@ def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
     b += ["  for (; t < t1 && fullP; ++t) {",
           "    const i64 rs = rsP, re = reP, tb0 = tb0P, g0 = g0P;"]
     for e in fl:
-        name, ct, n = e[0], e[1], _vec_load_len(e, NI)
-        b.append(f"{ind}{ct} {name}v[{n}]; " +
+        name, n = e.name, _vec_load_len(e, NI)
+        b.append(f"{ind}{e.ctype} {name}v[{n}]; " +
                  " ".join(f"{name}v[{k}] = {name}vP[{k}];" for k in range(n)))
     for name, ct, _ in list(scalars) + list(tscalars):
         b.append(f"{ind}const {ct} {name} = {name}P;")
@@ -1916,41 +2009,38 @@ def _vec_tiles(b: List[str], T: int, NI: int, ind: str, loads, scalars, body,
           "    while (r + 1 < (int)a.R && a.tile_prefix[r + 1] <= t) ++r;",
           f"    const i64 off = (t - a.tile_prefix[r]) * {T};"]
     _vec_rows(b, NI, ind)
-    for name, ct, expr in tscalars:
-        b.append(f"{ind}const {ct} {name} = {expr.format(t='t')};")
+    b += at_t
     _vec_issue(b, loads, NI, ind, False)
-    for name, ct, expr in scalars:
-        b.append(f"{ind}const {ct} {name} = {expr.replace('G0', 'g0')};")
+    b += at_g0
     body(b, False)
 
 
-def _vec_load_len(e, NI: int) -> int:
-    """Elements of a tile load's register array (``_vec_tiles`` ``loads`` / ``full_loads``)."""
-    return e[3] if len(e) > 3 else NI
+def _vec_load_len(e: _Load, NI: int) -> int:  # noqa: N803
+    """Elements of a tile load's register array."""
+    return e.words or NI
 
 
-def _vec_load_stmt(e, NI: int, g: str, suffix: str) -> str:
-    """The load of entry ``e`` for the NI rows at ``g`` into ``<name><suffix>``."""
-    name, ct, ptr = e[:3]
-    if len(e) > 4:      # lane-coalesced: from the first dword of the wavefront's row groups
-        return (f"ploadc<{e[3]}>({ptr}, (({g} >> {NI.bit_length() - 1}) - {e[4]}) * {e[3]}, "
-                f"{e[4]}, {name}{suffix});")
-    if len(e) > 3:
-        return f"pload<{e[3]}>({ptr}, ({g} >> {NI.bit_length() - 1}) * {e[3]}, {name}{suffix});"
-    return f"vload<{ct}, {NI}>({ptr}, {g}, {name}{suffix});"
+def _vec_load_stmt(e: _Load, NI: int, g: str, suffix: str) -> str:  # noqa: N803
+    """The load of ``e`` for the NI rows at ``g`` into ``<name><suffix>``."""
+    group = f"({g} >> {NI.bit_length() - 1})"
+    if e.lane:      # lane-coalesced: from the first dword of the wavefront's row groups
+        return (f"ploadc<{e.words}>({e.ptr}, ({group} - {e.lane}) * {e.words}, {e.lane}, "
+                f"{e.name}{suffix});")
+    if e.words:
+        return f"pload<{e.words}>({e.ptr}, {group} * {e.words}, {e.name}{suffix});"
+    return f"vload<{e.ctype}, {NI}>({e.ptr}, {g}, {e.name}{suffix});"
 
 
-def _vec_issue(b: List[str], loads, NI: int, ind: str, full: bool) -> None:
-    """Loads of the NI consecutive rows at ``g0`` into ``<name>v`` for every (name, C type,
-    pointer) of ``loads``: aligned vector loads in full tiles, guarded element loads otherwise."""
+def _vec_issue(b: List[str], loads, NI: int, ind: str, full: bool) -> None:  # noqa: N803
+    """Loads of the NI consecutive rows at ``g0`` into ``<name>v`` for every ``_Load`` of
+    ``loads``: aligned vector loads in full tiles, guarded element loads otherwise."""
     for e in loads:
-        name, ct, ptr = e[:3]
-        b.append(f"{ind}{ct} {name}v[{_vec_load_len(e, NI)}];")
+        b.append(f"{ind}{e.ctype} {e.name}v[{_vec_load_len(e, NI)}];")
         if full:
             b.append(f"{ind}{_vec_load_stmt(e, NI, 'g0', 'v')}")
         else:
             b.append(f"{ind}" + " ".join(
-                f"{name}v[{k}] = act{k} ? {ptr}[g0 + {k}] : ({ct})0;" for k in range(NI)))
+                f"{e.name}v[{k}] = act{k} ? {e.ptr}[g0 + {k}] : ({e.ctype})0;" for k in range(NI)))
 
 
 def _vec_load_slots(b: List[str], gen: "_Gen", slots, NI: int, ind: str) -> None:
@@ -1958,82 +2048,267 @@ def _vec_load_slots(b: List[str], gen: "_Gen", slots, NI: int, ind: str) -> None
     loaded for ``slots``."""
     for it in range(NI):
         for s in slots:
-            ct = _CTYPE[gen.cols[s][0]]
-            enc = gen.cols[s][2]
-            if enc:
-                b.append(f"{ind}const int r{s}_{it} = (int)x{s}v[{it}];")
-            if enc and enc[1]:
-                base = gen.a.add("q", f"B{s}", "long long")
-                b.append(f"{ind}const i64 q{s}_{it} = {base} + (i64)x{s}v[{it}];")
-            b.append(f"{ind}const {ct} x{s}_{it} = {gen.decode(s, f'x{s}v[{it}]')};")
-            if gen.cols[s][1]:
-                b.append(f"{ind}const bool n{s}_{it} = n{s}v[{it}] != 0;")
+            b += [ind + x for x in _item_regs(gen, s, it, f"x{s}v[{it}]", f"n{s}v[{it}]")[0]]
 
 
 def _vec_aligned_ptrs(ptrs) -> bool:
     return all(int(x) % 16 == 0 for x in ptrs if x)
 
 
-def _compacted_tail(args, cols, split, approx, aggs, grouped, group_col, third, allslots,
-                    NI: int, ind: str, with_j: bool = True, pass_fmt: str = "pass{it}",
-                    j_fmt: str = "j{it}", dump: bool = False, hk=None,
-                    jgroup: bool = False) -> List[str]:
+def _list_pos(ind: str, it: int, pv: str) -> List[str]:
+    """Opens item ``it``'s append: ``pz`` = its pass flag ``pv``, ``pos<it>`` = its position in
+    the wavefront's list - item-major order (all lanes' item 0, then item 1, ...), from one ballot
+    + mbcnt per item instead of a 6-step cross-lane prefix sum."""
+    return [f"{ind}{{ const bool pz = {pv}; const u64 bm = __ballot(pz);",
+            f"{ind}  const int pos{it} = wtot + (int)__builtin_amdgcn_mbcnt_hi("
+            f"(unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));"]
+
+
+def _compacted_tail(st: _Stream, aggs, group_col: int, allslots,
+                    opt: _Tail = _Tail()) -> List[str]:
     """Phase 3 over the passing rows only.  A join like TPC-H Q3 keeps a few percent of its
     rows, so decoding and accumulating all NI x 64 rows of a wavefront (branch-free) is mostly
     wasted VALU work: instead each lane appends its passing (row, j) pairs to a per-wavefront
     LDS list (positions from per-item ballots), and the wavefront walks the list 64
-    entries at a time — aggregate loads, decode and accumulation run once per passing row."""
-    # list position of a passing item: item-major order (all lanes' item 0, then item 1, ...),
-    # from one ballot + mbcnt per item instead of a 6-step cross-lane prefix sum
+    entries at a time — aggregate loads, decode and accumulation run once per passing row.
+    ``group_col``: the group column, -1 without a group table; ``opt``: ``_Tail``."""
+    NI, ind, hk = st.NI, st.ind, opt.hk  # noqa: N806
+    grouped = group_col >= 0
     b = [f"{ind}int wtot = 0;"]
     for it in range(NI):
-        pv = pass_fmt.format(it=it)
-        cj = f"cj_s[wv][pos{it}] = (int)({j_fmt.format(it=it)}); " if with_j else ""
-        b += [f"{ind}{{ const bool pz = {pv}; const u64 bm = __ballot(pz);",
-              f"{ind}  const int pos{it} = wtot + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), "
-              f"__builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));"]
-        if dump:
-            # branch-free: failing lanes write their own slot past the list (crow_s/cj_s carry
-            # 64 extra entries per wavefront), so no exec-mask save/restore per item
-            b += [f"{ind}  const int wp{it} = pz ? pos{it} : {64 * NI} + cln;",
-                  f"{ind}  crow_s[wv][wp{it}] = (crow_t)(row{it} - tb0); " +
-                  cj.replace(f"[pos{it}]", f"[wp{it}]")]
-        else:
-            b += [f"{ind}  if (pz) {{ crow_s[wv][pos{it}] = (crow_t)(row{it} - tb0); {cj}}}"]
-        b += [f"{ind}  wtot += __popcll(bm); }}"]
+        cj = f"cj_s[wv][pos{it}] = (int)({opt.j_fmt.format(it=it)}); " if opt.with_j else ""
+        b += _list_pos(ind, it, f"pass{it}")
+        b += [f"{ind}  if (pz) {{ crow_s[wv][pos{it}] = (crow_t)(row{it} - tb0); {cj}}}",
+              f"{ind}  wtot += __popcll(bm); }}"]
     b += [f"{ind}{_wave_sync()}",
           f"{ind}for (int cb = 0; cb < wtot; cb += 64) {{",
           f"{ind}  const int ce = cb + cln;",
           f"{ind}  bool cok = ce < wtot;",
           f"{ind}  const i64 crow = tb0 + (cok ? crow_s[wv][ce] : 0);",
-          f"{ind}  const i64 cj = cok ? (i64)cj_s[wv][ce] : 0;" if with_j else
+          f"{ind}  const i64 cj = cok ? (i64)cj_s[wv][ce] : 0;" if opt.with_j else
           f"{ind}  const i64 cj = crow;"]
     ind2 = ind + "  "
-    g = _Gen(args, cols, split, ("crow", "cj"), approx, True)
+    g = st.gen("crow", "cj")
     # every slot the aggregates and the group key read, re-loaded at the listed rows (the
     # phase-1/2 registers belong to the original, uncompacted rows)
-    tail = list(dict.fromkeys(_agg_slots(aggs) + ([group_col] if grouped and not jgroup else []) +
+    tail = list(dict.fromkeys(_agg_slots(aggs) +
+                              ([group_col] if grouped and not opt.jgroup else []) +
                               (hk.slots if hk is not None else [])))
     for sl in tail:
         _uload(g, sl, "c", b, ind2)
-    gvar = "gic"
-    if jgroup:
+    if opt.jgroup:
         # the listed j is the row's group index itself (jit_runs: a right-side group key's code
         # carried in the run tag)
-        b.append(f"{ind2}const int {gvar} = cok ? (int)cj : 0;")
+        b.append(f"{ind2}const int gic = cok ? (int)cj : 0;")
     elif grouped:
-        base = args.add("q", "group_base", "long long")
-        ng = args.add("q", "num_groups", "long long")
-        b.append(f"{ind2}const i64 glc = (i64){_rename(f'x{group_col}', allslots, 'c')} - {base};")
-        b.append(f"{ind2}cok = cok && {_rename(g.ok(group_col), allslots, 'c')} && "
-                 f"glc >= 0 && glc < {ng};")
-        b.append(f"{ind2}const int {gvar} = cok ? (int)glc : 0;")
+        b += g.group_index(group_col, "c", "cok", ind2)
     if hk is not None:
         b += [_rename(x, allslots, "c") for x in JH._hash_accumulate(g, aggs, hk, "cok", ind2)]
     else:
-        b += [_rename(x, allslots, "c") for x in _accumulate(g, aggs, grouped, "cok", gvar, ind2)]
+        b += [_rename(x, allslots, "c") for x in _accumulate(g, aggs, grouped, "cok", "gic", ind2)]
     b += [f"{ind}}}", f"{ind}{_wave_sync()}"]
     return b
+
+
+class _JoinIndex(_Stream):
+    """The builder behind ``gen_join_index_agg``: one method per phase of its docstring -
+    ``phase1``; ``phase2_global``, ``phase2_staged`` or ``phase2_bitmap``; ``phase3`` - which
+    ``tile`` calls in that order for each kind of tile."""
+
+    def __init__(self, p: NL.JoinParams, compacts, vec: int, jx: Tuple[int, int], stage, bitmap):
+        self.jw, self.jlog = jx
+        jw = self.jw
+        self.jct = {4: "int", 2: "unsigned short", 1: "unsigned char"}[jw]
+        self.sent = {2: "0xFFFF", 1: "0xFF"}.get(jw)
+        args = _range_args(Args())
+        args.add("p", "jidx", f"const {self.jct}*")
+        if jw < 4:
+            # block-coded join index (exec/join_index.py): j = jbase[row >> jlog] + code
+            args.add("p", "jbase", "const int*")
+        args.add("q", "R", "long long")
+        _common_args(args)
+        cols = _col_specs(p, compacts)
+        self.lpreds = lpreds = [(k, p.preds[k]) for k in range(p.nlp)]
+        self.rpreds = rpreds = [(k, p.preds[k]) for k in range(p.nlp, p.npreds)]
+        self.aggs = aggs = aggs_of(p)
+        self.group_col, self.grouped = p.group_col, p.group_col >= 0
+        self.first = first = _pred_slots(lpreds)
+        self.second = second = [s for s in _pred_slots(rpreds) if s not in first]
+        third = [s for s in _agg_slots(aggs) + ([p.group_col] if self.grouped else [])
+                 if s not in first and s not in second]
+        self.third = third = list(dict.fromkeys(third))
+        self.allslots = first + second + third
+        super().__init__(args, cols, 8, _sum_only_slots(lpreds + rpreds, aggs, p.group_col, cols),
+                         vec or JI_ITEMS)
+        if vec:
+            args.add("q", "nrows", "long long")
+        self.g1 = g1 = self.gen("row0")
+        self.compact = compact = JI_COMPACT and bool(third)
+        # the bitmap replaces phase 2 only when the aggregate tail re-loads what it needs
+        self.bitmap = bool(bitmap and second and compact and _right_only(p, 8))
+        self.stage = bool(vec and second and not self.bitmap and
+                          (JI_STAGE if stage is None else stage))
+        W = BLOCK // 64  # noqa: N806
+        if compact:
+            self.lds.append(f"  typedef {_crow_t(self.T)} crow_t; __shared__ crow_t "
+                            f"crow_s[{W}][{64 * self.NI}]; "
+                            f"__shared__ int cj_s[{W}][{64 * self.NI}];")
+        if self.stage:
+            for s in second:
+                self.lds.append(f"  __shared__ __attribute__((aligned(16))) {g1.raw_type(s)} "
+                                f"st{s}_s[{W}][512];")
+                if cols[s][1]:
+                    self.lds.append(f"  __shared__ unsigned char sn{s}_s[{W}][512];")
+        if self.lds:
+            self.lds.append("  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;")
+
+    def tile(self, b: List[str], full: Optional[bool]) -> None:
+        """One tile's work; ``full`` = vectorized full tile / vectorized last tile / None
+        (strided)."""
+        b += self.phase1(full)
+        if self.bitmap:
+            b += self.phase2_bitmap()
+        else:
+            b += self.phase2_staged() if self.stage else self.phase2_global()
+            b += [f"{self.ind}pass{it} = pass{it} && "
+                  f"{_rename(self.gen(f'row{it}', f'j{it}').cnf(self.rpreds), self.allslots, it)};"
+                  for it in range(self.NI)]
+        b += self.phase3()
+
+    def phase1(self, full: Optional[bool]) -> List[str]:
+        """Join index and left predicate columns of every item - from the raw vector arrays
+        (and ``jb``) the tile loop loaded, or loaded here at the strided rows - then the left
+        filter and the matched right row ``j``.  Adds the left predicate columns' decode slots
+        (strided: their pointers too) and the left predicates' literal slots."""
+        NI, ind, jw, sent, b = self.NI, self.ind, self.jw, self.sent, []  # noqa: N806
+        if full is not None:
+            _vec_load_slots(b, self.g1, self.first, NI, ind)
+            for it in range(NI):
+                if jw < 4:
+                    b.append(f"{ind}const int jr{it} = act{it} && jrv[{it}] != {sent} ? "
+                             f"jb + (int)jrv[{it}] : -1;")
+                else:
+                    b.append(f"{ind}const int jr{it} = act{it} ? jrv[{it}] : -1;")
+        else:
+            b += self.scalar_rows()
+            for it in range(NI):
+                if jw < 4:
+                    b.append(f"{ind}const {self.jct} jc{it} = a.jidx[row{it}];")
+                    b.append(f"{ind}const int jr{it} = jc{it} != {sent} ? "
+                             f"a.jbase[row{it} >> {self.jlog}] + (int)jc{it} : -1;")
+                else:
+                    b.append(f"{ind}const int jr{it} = a.jidx[row{it}];")
+                for s in self.first:
+                    _uload(self.gen(f"row{it}"), s, it, b, ind)
+        for it in range(NI):
+            cond = _rename(self.gen(f"row{it}").cnf(self.lpreds), self.allslots, it)
+            b.append(f"{ind}bool pass{it} = act{it} && jr{it} >= 0 && {cond};")
+            b.append(f"{ind}const i64 j{it} = pass{it} ? (i64)jr{it} : 0;")
+        return b
+
+    def phase2_global(self) -> List[str]:
+        """Right predicate columns gathered at the matched rows (non-matching rows read right
+        row 0).  Adds their slots."""
+        b = []
+        for it in range(self.NI):
+            for s in self.second:
+                _uload(self.gen(f"row{it}", f"j{it}"), s, it, b, self.ind)
+        return b
+
+    def _run_bounds(self) -> str:
+        """``mlo`` / ``mhi``: the thread's lowest and highest matched right row."""
+        NI = range(self.NI)  # noqa: N806
+        lo = " ".join(f"if (pass{it} && (int)j{it} < mlo) mlo = (int)j{it};" for it in NI)
+        hi = " ".join(f"if (pass{it} && (int)j{it} > mhi) mhi = (int)j{it};" for it in NI)
+        return f"{self.ind}int mlo = 0x7fffffff, mhi = -1; {lo} {hi}"
+
+    def phase2_bitmap(self) -> List[str]:
+        """Phase 2 as bit tests on the right side's predicate bitmap (``gen_pred_bitmap``).  A
+        thread's NI rows are consecutive and the join index is monotone within a bucket, so the
+        matched right rows of its passing items fall in at most two bitmap words (loaded once
+        each, unconditionally: word 0 stands in when nothing passes); an item whose word is
+        neither (a gap of over 64 right rows) loads its own.  Adds rbm."""
+        ind = self.ind
+        bm = self.args.add("p", "rbm", "const unsigned long long*")
+        b = [self._run_bounds(),
+             f"{ind}const int wlo = mhi >= 0 ? (mlo >> 6) : 0, whi = mhi >= 0 ? (mhi >> 6) : 0;",
+             f"{ind}const u64 bw0 = {bm}[wlo], bw1 = {bm}[whi];"]
+        for it in range(self.NI):
+            b += [f"{ind}if (pass{it}) {{ const int wi = (int)j{it} >> 6;",
+                  f"{ind}  const u64 w = wi == wlo ? bw0 : (wi == whi ? bw1 : {bm}[wi]);",
+                  f"{ind}  pass{it} = ((w >> ((int)j{it} & 63)) & 1ull) != 0ull; }}"]
+        return b
+
+    def phase2_staged(self) -> List[str]:
+        """Phase 2 through LDS: the matched right rows of a wavefront's passing items are one
+        short, monotone run (both sides sorted by key within a bucket, the wavefront's rows
+        consecutive), so the wavefront copies the 8-byte aligned window of every right predicate
+        column that holds the run [jlo, jhi] into its own LDS slice — one coalesced ``dwordx2``
+        per lane, i.e. one vector-memory instruction for the whole wavefront — and each item
+        then reads LDS, instead of NI divergent gathers per lane, which made vector-memory
+        instruction issue the kernel's limit.  Runs wider than the 512-byte window, or rows
+        outside the run (a non-monotone index), take the global gathers.  Adds the right
+        predicate columns' slots: pointers with the copy, decode slots with the reads."""
+        NI, ind, g1, second, cols = self.NI, self.ind, self.g1, self.second, self.cols  # noqa: N806
+        i2 = ind + "  "
+        # the window starts at jlo rounded down to 8 bytes of the widest staged element: every
+        # staged array holds 512 bytes of the widest, fewer bytes of narrower ones
+        esz = max(_SIZEOF[g1.raw_type(s)] for s in second)
+        span = 512 // esz
+        per = 8 // esz    # elements per lane: 8 bytes of the widest type
+        head = [self._run_bounds(),
+                f"{ind}const u64 anyp = __ballot(mhi >= 0);",
+                f"{ind}int jlo = 0, jhi = -1;",
+                f"{ind}if (anyp) {{ jlo = __builtin_amdgcn_readlane(mlo, __ffsll((long long)anyp) - 1);",
+                f"{ind}  jhi = __builtin_amdgcn_readlane(mhi, 63 - __clzll((long long)anyp)); }}",
+                f"{ind}const int jw0 = jlo & ~{8 // esz - 1 if esz < 8 else 0};",
+                f"{ind}const bool inrun = " + " && ".join(
+                    f"(!pass{it} || ((int)j{it} >= jlo && (int)j{it} <= jhi))"
+                    for it in range(NI)) + ";",
+                f"{ind}const bool staged = anyp != 0ull && jhi - jw0 < {span} && "
+                f"__ballot(!inrun) == 0ull;"]
+        # lane l copies elements [jw0 + l * per, + per) of each column; lanes whose piece starts
+        # past jhi stay idle (no read past the run's last 8-byte word, which lies inside the
+        # column's allocation)
+        copy = []
+        for s in second:
+            copy.append(f"{i2}if (jw0 + cln * {per} <= jhi) {{")
+            copy.append(f"{i2}  " + " ".join(f"st{s}_s[wv][cln * {per} + {k}] = "
+                                             f"{g1.ptr(s)}[jw0 + cln * {per} + {k}];"
+                                             for k in range(per))
+                        if _SIZEOF[g1.raw_type(s)] * per != 8 else
+                        f"{i2}  *reinterpret_cast<uint2*>(&st{s}_s[wv][cln * {per}]) = "
+                        f"*reinterpret_cast<const uint2*>({g1.ptr(s)} + jw0 + cln * {per});")
+            if cols[s][1]:
+                copy.append(f"{i2}  " + " ".join(f"sn{s}_s[wv][cln * {per} + {k}] = "
+                                                 f"{g1.vptr(s)}[jw0 + cln * {per} + {k}];"
+                                                 for k in range(per)))
+            copy.append(f"{i2}}}")
+        # the phase-2 registers, S-prefixed here and renamed to x/n/q/r after the branch, filled
+        # from LDS or by the global gathers
+        read, outs = [], []
+        for it in range(NI):
+            read.append(f"{i2}const int sj{it} = pass{it} ? (int)j{it} - jw0 : 0;")
+            for s in second:
+                stmts, regs = _item_regs(g1, s, it, f"st{s}_s[wv][sj{it}]",
+                                         f"sn{s}_s[wv][sj{it}]", assign="S")
+                read += [i2 + x for x in stmts]
+                outs += regs
+        return head + [
+            f"{ind}" + " ".join(f"{ct} S{n};" for n, ct in outs),
+            f"{ind}if (staged) {{"] + copy + [f"{i2}{_wave_sync(True)}"] + read + [
+            f"{i2}{_wave_sync(True)}",
+            f"{ind}}} else {{"] + [f"{i2}{line.strip()}" for line in self.phase2_global()] + [
+            f"{i2}" + " ".join(f"S{n} = {n};" for n, _ in outs),
+            f"{ind}}}",
+            f"{ind}" + " ".join(f"const {ct} {n} = S{n};" for n, ct in outs)]
+
+    def phase3(self) -> List[str]:
+        """Aggregate inputs and the group column, then accumulation: over the passing rows'
+        list, or branch-free."""
+        if self.compact:
+            return _compacted_tail(self, self.aggs, self.group_col, self.allslots)
+        return self.branch_free_tail(self.third, True)
 
 
 def gen_join_index_agg(p: NL.JoinParams, compacts=None, vec: int = 0, jw: int = 4,
@@ -2053,170 +2328,24 @@ def gen_join_index_agg(p: NL.JoinParams, compacts=None, vec: int = 0, jw: int = 
     3. aggregate inputs and the group column (failing rows read the tile's first row).
 
     Right rows of consecutive left rows are monotone (both sides sorted by key per bucket), so
-    the gathers of a wavefront hit a few adjacent cache lines."""
-    args = Args()
-    jct = {4: "int", 2: "unsigned short", 1: "unsigned char"}[jw]
-    sent = {2: "0xFFFF", 1: "0xFF"}.get(jw)
-    for n, ct in (("rstart", "const long long*"), ("rlen", "const long long*"),
-                  ("tile_prefix", "const long long*"), ("jidx", f"const {jct}*")):
-        args.add("p", n, ct)
-    if jw < 4:
-        # block-coded join index (exec/join_index.py): j = jbase[row >> jlog] + code
-        args.add("p", "jbase", "const int*")
-    args.add("q", "R", "long long")
-    _common_args(args)
-    cols = _col_specs(p, compacts)
-    split = 8
-    lpreds = [(k, p.preds[k]) for k in range(p.nlp)]
-    rpreds = [(k, p.preds[k]) for k in range(p.nlp, p.npreds)]
-    aggs = aggs_of(p)
-    grouped = p.group_col >= 0
-    first = _pred_slots(lpreds)
-    second = [s for s in _pred_slots(rpreds) if s not in first]
-    third = [s for s in _agg_slots(aggs) + ([p.group_col] if grouped else [])
-             if s not in first and s not in second]
-    third = list(dict.fromkeys(third))
-    allslots = first + second + third
-    approx = _sum_only_slots(lpreds + rpreds, aggs, p.group_col, cols)
-    NI = vec or JI_ITEMS
-    T = BLOCK * NI
-    if vec:
-        args.add("q", "nrows", "long long")
-    b: List[str] = []
-    b += _acc_decls(aggs, grouped, args)
-    if grouped:
-        base = args.add("q", "group_base", "long long")
-        ng = args.add("q", "num_groups", "long long")
-    ind = "    "
-    g1 = _Gen(args, cols, split, ("row0", "row0"), approx, True)
-    compact = JI_COMPACT and bool(third)
-    # the bitmap replaces phase 2 only when the aggregate tail re-loads what it needs
-    bitmap = bool(bitmap and second and compact and _right_only(p, split))
-    stage = bool(vec and second and not bitmap and (JI_STAGE if stage is None else stage))
+    the gathers of a wavefront hit a few adjacent cache lines.
 
-    def phase2_global(b: List[str]) -> None:
-        for it in range(NI):
-            g2 = _Gen(args, cols, split, (f"row{it}", f"j{it}"), approx, True)
-            for s in second:
-                _uload(g2, s, it, b, ind)
-
-    def body(b: List[str], full: Optional[bool]) -> None:
-        """Tile body; ``full`` = vectorized full tile / vectorized last tile / None (scalar)."""
-        if full is not None:     # raw vector arrays and jb come from the tile loop
-            _vec_load_slots(b, g1, first, NI, ind)
-            for it in range(NI):
-                if jw < 4:
-                    b.append(f"{ind}const int jr{it} = act{it} && jrv[{it}] != {sent} ? "
-                             f"jb + (int)jrv[{it}] : -1;")
-                else:
-                    b.append(f"{ind}const int jr{it} = act{it} ? jrv[{it}] : -1;")
-        else:
-            b.extend(["    const i64 tb0 = a.rstart[r] + off;",
-                      f"    const i64 rows = a.rlen[r] - off < {T} ? a.rlen[r] - off : {T};"])
-            for it in range(NI):
-                b.extend([f"{ind}const bool act{it} = {it * BLOCK} + (i64)threadIdx.x < rows;",
-                          f"{ind}const i64 row{it} = tb0 + (act{it} ? {it * BLOCK} + (i64)threadIdx.x : 0);"])
-            # phase 1: join index + left predicate columns of every item
-            for it in range(NI):
-                if jw < 4:
-                    b.append(f"{ind}const {jct} jc{it} = a.jidx[row{it}];")
-                    b.append(f"{ind}const int jr{it} = jc{it} != {sent} ? "
-                             f"a.jbase[row{it} >> {jlog}] + (int)jc{it} : -1;")
-                else:
-                    b.append(f"{ind}const int jr{it} = a.jidx[row{it}];")
-                g1i = _Gen(args, cols, split, (f"row{it}", f"row{it}"), approx, True)
-                for s in first:
-                    _uload(g1i, s, it, b, ind)
-        for it in range(NI):
-            g1i = _Gen(args, cols, split, (f"row{it}", f"row{it}"), approx, True)
-            cond = _rename(g1i.cnf(lpreds), allslots, it)
-            b.append(f"{ind}bool pass{it} = act{it} && jr{it} >= 0 && {cond};")
-            b.append(f"{ind}const i64 j{it} = pass{it} ? (i64)jr{it} : 0;")
-        # phase 2: right predicate columns at the matched rows
-        if bitmap:
-            _bitmap_phase2(b, args, NI, ind)
-            b.extend(_compacted_tail(args, cols, split, approx, aggs, grouped, p.group_col,
-                                     third, allslots, NI, ind))
-            return
-        if stage:
-            _ji_stage_phase2(b, g1, args, cols, split, approx, second, NI, stage, ind,
-                             phase2_global)
-        else:
-            phase2_global(b)
-        for it in range(NI):
-            g2 = _Gen(args, cols, split, (f"row{it}", f"j{it}"), approx, True)
-            b.append(f"{ind}pass{it} = pass{it} && {_rename(g2.cnf(rpreds), allslots, it)};")
-        if compact:
-            b.extend(_compacted_tail(args, cols, split, approx, aggs, grouped, p.group_col,
-                                     third, allslots, NI, ind))
-            return
-        # phase 3: aggregate inputs (rows that failed read the tile's first row / right row 0)
-        if third:
-            for it in range(NI):
-                b.extend([f"{ind}const i64 lq{it} = pass{it} ? row{it} : tb0;",
-                          f"{ind}const i64 jq{it} = pass{it} ? j{it} : 0;"])
-            for it in range(NI):
-                g3 = _Gen(args, cols, split, (f"lq{it}", f"jq{it}"), approx, True)
-                for s in third:
-                    _uload(g3, s, it, b, ind)
-        for it in range(NI):
-            g3 = _Gen(args, cols, split, (f"lq{it}", f"jq{it}"), approx, True)
-            gvar = f"gi{it}"
-            if grouped:
-                g = p.group_col
-                gx = _rename(f"x{g}", allslots, it)
-                ok = _rename(g3.ok(g), allslots, it)
-                b.append(f"{ind}const i64 gl{it} = (i64){gx} - {base};")
-                b.append(f"{ind}pass{it} = pass{it} && {ok} && gl{it} >= 0 && gl{it} < {ng};")
-                b.append(f"{ind}const int {gvar} = pass{it} ? (int)gl{it} : 0;")
-            b.extend(_rename(x, allslots, it) for x in
-                     _accumulate(g3, aggs, grouped, f"pass{it}", gvar, ind))
-
+    The driver of ``_JoinIndex``.  The struct: the header's slots, nrows, the group table's,
+    the streamed columns', then what the tile's phases add."""
+    s = _JoinIndex(p, compacts, vec, (jw, jlog), stage, bitmap)
+    b = _acc_decls(s.aggs, s.grouped, s.args)
     if vec:
         # NI | block size and g0 % NI == 0: the thread's rows share one join-index block
         sc = [("jb", "int", f"a.jbase[G0 >> {jlog}]")] if jw < 4 else []
-        _vec_tiles(b, T, NI, ind, _vec_loads(g1, first, extra=[("jr", jct, "a.jidx")]), sc, body)
+        _vec_tiles(s, b, s.tile,
+                   _Tile(_vec_loads(s.g1, s.first, extra=[_Load("jr", s.jct, "a.jidx")]), sc))
     else:
-        _tile_loop(b, T, NI, 0)
-        body(b, None)
+        _tile_loop(b, s.T, s.NI, 0)
+        s.tile(b, None)
     b += ["  }"]
-    b += _flush(aggs, grouped)
-    W = BLOCK // 64
-    pre = []
-    if compact:
-        pre.append(f"  typedef {_crow_t(T)} crow_t; __shared__ crow_t crow_s[{W}][{64 * NI}]; "
-                   f"__shared__ int cj_s[{W}][{64 * NI}];")
-    if stage:
-        for s in second:
-            pre.append(f"  __shared__ __attribute__((aligned(16))) {g1.raw_type(s)} st{s}_s[{W}][512];")
-            if cols[s][1]:
-                pre.append(f"  __shared__ unsigned char sn{s}_s[{W}][512];")
-    if compact or stage:
-        pre.append("  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;")
-    b = pre + b
-    src = (_PRELUDE + args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({BLOCK}) void hs_jit_join_index_agg(Args a) {{\n' +
-           "\n".join(b) + "\n}\n")
-    lds = (len(aggs) * p.num_groups * 32) if grouped else 0
-    return Kernel(src, "hs_jit_join_index_agg", args, lds)
-
-
-def _bitmap_phase2(b: List[str], args: Args, NI: int, ind: str) -> None:
-    """Phase 2 of the join-index kernel as bit tests on the right side's predicate bitmap
-    (``gen_pred_bitmap``).  A thread's NI rows are consecutive and the join index is monotone
-    within a bucket, so the matched right rows of its passing items fall in at most two bitmap
-    words (loaded once each, unconditionally: word 0 stands in when nothing passes); an item
-    whose word is neither (a gap of over 64 right rows) loads its own."""
-    bm = args.add("p", "rbm", "const unsigned long long*")
-    lo = " ".join(f"if (pass{it} && (int)j{it} < mlo) mlo = (int)j{it};" for it in range(NI))
-    hi = " ".join(f"if (pass{it} && (int)j{it} > mhi) mhi = (int)j{it};" for it in range(NI))
-    b += [f"{ind}int mlo = 0x7fffffff, mhi = -1; {lo} {hi}",
-          f"{ind}const int wlo = mhi >= 0 ? (mlo >> 6) : 0, whi = mhi >= 0 ? (mhi >> 6) : 0;",
-          f"{ind}const u64 bw0 = {bm}[wlo], bw1 = {bm}[whi];"]
-    for it in range(NI):
-        b += [f"{ind}if (pass{it}) {{ const int wi = (int)j{it} >> 6;",
-              f"{ind}  const u64 w = wi == wlo ? bw0 : (wi == whi ? bw1 : {bm}[wi]);",
-              f"{ind}  pass{it} = ((w >> ((int)j{it} & 63)) & 1ull) != 0ull; }}"]
+    b += _flush(s.aggs, s.grouped)
+    return s.finish("hs_jit_join_index_agg", b,
+                    (len(s.aggs) * p.num_groups * 32) if s.grouped else 0)
 
 
 def _right_only(p: NL.JoinParams, split: int = 8) -> bool:
@@ -2232,8 +2361,7 @@ def _right_only(p: NL.JoinParams, split: int = 8) -> bool:
 
 def pred_bitmap_shape(p: NL.JoinParams, compacts=None) -> tuple:
     cols = tuple((s, c) for s, c in sorted(_col_specs(p, compacts).items()) if s >= 8)
-    preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
-                   p.preds[k].group) for k in range(p.nlp, p.npreds))
+    preds = _preds_shape(p, p.nlp, p.npreds)
     return ("pred_bitmap", cols, preds, p.nlp)
 
 
@@ -2248,33 +2376,29 @@ def gen_pred_bitmap(p: NL.JoinParams, compacts=None) -> Kernel:
     args = Args()
     args.add("p", "rbm", "unsigned long long*")
     args.add("q", "rnrows", "long long")
-    cols = {s: c for s, c in _col_specs(p, compacts).items() if s >= 8}
+    st = _Stream(args, {s: c for s, c in _col_specs(p, compacts).items() if s >= 8}, 8,
+                 frozenset(), BITMAP_ITEMS)
     rpreds = [(k, p.preds[k]) for k in range(p.nlp, p.npreds)]
     slots = _pred_slots(rpreds)
-    NI = BITMAP_ITEMS
+    NI, ind = st.NI, st.ind  # noqa: N806
     b = ["  const int lane = threadIdx.x & 63;",
          "  const i64 nw = (a.rnrows + 63) >> 6;",
          f"  const i64 wstep = (i64)gridDim.x * {BLOCK // 64 * NI};",
          f"  for (i64 w0 = ((i64)blockIdx.x * {BLOCK // 64} + (threadIdx.x >> 6)) * {NI}; w0 < nw; "
          "w0 += wstep) {"]
-    ind = "    "
     for it in range(NI):
         b += [f"{ind}const i64 row{it} = ((w0 + {it}) << 6) + lane;",
               f"{ind}const bool act{it} = row{it} < a.rnrows;",
               f"{ind}const i64 jr{it} = act{it} ? row{it} : 0;"]
     for it in range(NI):
-        g = _Gen(args, cols, 8, (f"jr{it}", f"jr{it}"), frozenset(), True)
         for sl in slots:
-            _uload(g, sl, it, b, ind)
+            _uload(st.gen(f"jr{it}"), sl, it, b, ind)
     for it in range(NI):
-        g = _Gen(args, cols, 8, (f"jr{it}", f"jr{it}"), frozenset(), True)
-        b += [f"{ind}{{ const u64 m = __ballot(act{it} && {_rename(g.cnf(rpreds), slots, it)});",
+        cond = _rename(st.gen(f"jr{it}").cnf(rpreds), slots, it)
+        b += [f"{ind}{{ const u64 m = __ballot(act{it} && {cond});",
               f"{ind}  if (lane == 0 && w0 + {it} < nw) a.rbm[w0 + {it}] = m; }}"]
     b.append("  }")
-    src = (_PRELUDE + args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({BLOCK}) void hs_jit_pred_bitmap(Args a) {{\n' +
-           "\n".join(b) + "\n}\n")
-    return Kernel(src, "hs_jit_pred_bitmap", args)
+    return st.finish("hs_jit_pred_bitmap", b)
 
 
 def pred_bitmap(p: NL.JoinParams, compacts, rnrows: int, device):
@@ -2291,104 +2415,27 @@ def pred_bitmap(p: NL.JoinParams, compacts, rnrows: int, device):
     return bm
 
 
-def _ji_stage_phase2(b: List[str], g1: "_Gen", args, cols, split, approx, second, NI: int,
-                     stage: int, ind: str, fallback) -> None:
-    """Phase 2 of the join-index kernel through LDS: the matched right rows of a wavefront's
-    passing items are one short, monotone run (both sides sorted by key within a bucket, the
-    wavefront's rows consecutive), so the wavefront copies the 8-byte aligned window of every
-    right predicate column that holds the run [jlo, jhi] into its own LDS slice — one coalesced
-    ``dwordx2`` per lane, i.e. one vector-memory instruction for the whole wavefront — and each
-    item then reads LDS, instead of NI divergent gathers per lane, which made vector-memory
-    instruction issue the kernel's limit.  Runs wider than the 512-byte window, or rows outside
-    the run (a non-monotone index), take the global gathers."""
-    lo_terms = " ".join(f"if (pass{it} && (int)j{it} < mlo) mlo = (int)j{it};" for it in range(NI))
-    hi_terms = " ".join(f"if (pass{it} && (int)j{it} > mhi) mhi = (int)j{it};" for it in range(NI))
-    # the window starts at jlo rounded down to 8 bytes of the widest staged element: every staged
-    # array holds STAGE_W elements (512 bytes of the widest, fewer bytes of narrower ones)
-    esz = max(_SIZEOF[g1.raw_type(s)] for s in second)
-    span = 512 // esz
-    b += [f"{ind}int mlo = 0x7fffffff, mhi = -1; {lo_terms} {hi_terms}",
-          f"{ind}const u64 anyp = __ballot(mhi >= 0);",
-          f"{ind}int jlo = 0, jhi = -1;",
-          f"{ind}if (anyp) {{ jlo = __builtin_amdgcn_readlane(mlo, __ffsll((long long)anyp) - 1);",
-          f"{ind}  jhi = __builtin_amdgcn_readlane(mhi, 63 - __clzll((long long)anyp)); }}",
-          f"{ind}const int jw0 = jlo & ~{8 // esz - 1 if esz < 8 else 0};",
-          f"{ind}const bool inrun = " + " && ".join(
-              f"(!pass{it} || ((int)j{it} >= jlo && (int)j{it} <= jhi))" for it in range(NI)) + ";",
-          f"{ind}const bool staged = anyp != 0ull && jhi - jw0 < {span} && __ballot(!inrun) == 0ull;"]
-    # phase-2 registers (S-prefixed here, renamed to x/n/q after the branch), filled from LDS
-    # or by the global gathers
-    outs = []
-    for it in range(NI):
-        for s in second:
-            outs.append((f"x{s}_{it}", _CTYPE[cols[s][0]]))
-            if cols[s][1]:
-                outs.append((f"n{s}_{it}", "bool"))
-            enc = cols[s][2]
-            if enc:
-                outs.append((f"r{s}_{it}", "int"))
-            if enc and enc[1]:
-                outs.append((f"q{s}_{it}", "i64"))
-    b.append(f"{ind}" + " ".join(f"{ct} S{n};" for n, ct in outs))
-    b.append(f"{ind}if (staged) {{")
-    i2 = ind + "  "
-    # lane l copies elements [jw0 + l*8/esz, +8/esz) of each column: 8 bytes of the widest,
-    # fewer of narrower ones; lanes whose piece starts past jhi stay idle (no read past the run's
-    # last 8-byte word, which lies inside the column's allocation)
-    for s in second:
-        es = _SIZEOF[g1.raw_type(s)]
-        per = 8 // esz * 1    # elements of the widest type per lane
-        b.append(f"{i2}if (jw0 + cln * {per} <= jhi) {{")
-        b.append(f"{i2}  " + " ".join(f"st{s}_s[wv][cln * {per} + {k}] = {g1.ptr(s)}[jw0 + cln * {per} + {k}];"
-                                      for k in range(per)) if es * per != 8 else
-                 f"{i2}  *reinterpret_cast<uint2*>(&st{s}_s[wv][cln * {per}]) = "
-                 f"*reinterpret_cast<const uint2*>({g1.ptr(s)} + jw0 + cln * {per});")
-        if cols[s][1]:
-            b.append(f"{i2}  " + " ".join(f"sn{s}_s[wv][cln * {per} + {k}] = {g1.vptr(s)}[jw0 + cln * {per} + {k}];"
-                                          for k in range(per)))
-        b.append(f"{i2}}}")
-    b.append(f"{i2}{_wave_sync(True)}")
-    for it in range(NI):
-        b.append(f"{i2}const int sj{it} = pass{it} ? (int)j{it} - jw0 : 0;")
-        for s in second:
-            enc = cols[s][2]
-            raw = f"st{s}_s[wv][sj{it}]"
-            if enc:
-                b.append(f"{i2}Sr{s}_{it} = (int){raw};")
-            if enc and enc[1]:
-                base = args.add("q", f"B{s}", "long long")
-                b.append(f"{i2}Sq{s}_{it} = {base} + (i64){raw};")
-            b.append(f"{i2}Sx{s}_{it} = {g1.decode(s, raw)};")
-            if cols[s][1]:
-                b.append(f"{i2}Sn{s}_{it} = sn{s}_s[wv][sj{it}] != 0;")
-    b.append(f"{i2}{_wave_sync(True)}")
-    b.append(f"{ind}}} else {{")
-    gl: List[str] = []
-    fallback(gl)
-    b += [f"{i2}{line.strip()}" for line in gl]
-    b.append(f"{i2}" + " ".join(f"S{n} = {n};" for n, _ in outs))
-    b.append(f"{ind}}}")
-    b.append(f"{ind}" + " ".join(f"const {ct} {n} = S{n};" for n, ct in outs))
-
-
 def _stage_aligned(p: NL.JoinParams, compacts) -> bool:
     """LDS staging copies 8-byte words of the right predicate columns (and validity bytes)."""
+    return all(int(x) % 8 == 0 for x in _pred_ptrs(p, compacts, p.nlp, p.npreds) if x)
+
+
+def _col_ptrs(p, compacts, slots) -> list:
+    """Data (codes, for compact columns) and validity pointers of column ``slots``."""
     ptrs = []
-    for s in _pred_slots([(k, p.preds[k]) for k in range(p.nlp, p.npreds)]):
+    for s in slots:
         c = (compacts or {}).get(s)
-        ptrs.append(c.codes.data_ptr() if c else p.cols[s].data)
-        ptrs.append(p.cols[s].valid)
-    return all(int(x) % 8 == 0 for x in ptrs if x)
+        ptrs += [c.codes.data_ptr() if c else p.cols[s].data, p.cols[s].valid]
+    return ptrs
+
+
+def _pred_ptrs(p, compacts, lo: int, hi: int) -> list:
+    return _col_ptrs(p, compacts, _pred_slots([(k, p.preds[k]) for k in range(lo, hi)]))
 
 
 def _vec_aligned(p: NL.JoinParams, compacts, jidx) -> bool:
     """Vector loads need 16-byte aligned bases for every streamed left column."""
-    ptrs = [jidx.data_ptr()]
-    for s in _pred_slots([(k, p.preds[k]) for k in range(p.nlp)]):
-        c = (compacts or {}).get(s)
-        ptrs.append(c.codes.data_ptr() if c else p.cols[s].data)
-        ptrs.append(p.cols[s].valid)
-    return _vec_aligned_ptrs(ptrs)
+    return _vec_aligned_ptrs([jidx.data_ptr()] + _pred_ptrs(p, compacts, 0, p.nlp))
 
 
 def join_index_agg(p: NL.JoinParams, rstart, rlen, jx, compacts=None, nrows: int = 0,
@@ -2480,12 +2527,7 @@ def scan_vec(p: NL.ScanParams, compacts=None, nrows: int = 0) -> int:
     predicate columns must have 16-byte aligned bases."""
     if SCAN_VEC <= 0 or nrows <= 0:
         return 0
-    ptrs = []
-    for s in _pred_slots([(k, p.preds[k]) for k in range(p.npreds)]):
-        c = (compacts or {}).get(s)
-        ptrs.append(c.codes.data_ptr() if c else p.cols[s].data)
-        ptrs.append(p.cols[s].valid)
-    return SCAN_VEC if _vec_aligned_ptrs(ptrs) else 0
+    return SCAN_VEC if _vec_aligned_ptrs(_pred_ptrs(p, compacts, 0, p.npreds)) else 0
 
 
 def scan_agg(p: NL.ScanParams, rstart, rlen, tile_prefix=None, compacts=None, nrows: int = 0,

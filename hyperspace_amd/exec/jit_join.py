@@ -15,8 +15,7 @@ from ..ops import _lib as NL
 
 def merge_join_shape(p: NL.JoinParams, compacts=None, hk=None) -> tuple:
     cols = tuple(sorted(J._col_specs(p, compacts).items()))
-    preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
-                   p.preds[k].group) for k in range(p.npreds))
+    preds = J._preds_shape(p, 0, p.npreds)
     aggs = J.aggs_shape(p)
     return ("merge_join_agg", cols, preds, p.nlp, aggs, p.group_col, p.lkey, p.rkey,
             p.key_is_float, J.MJ_ITEMS, J.MJ_LDS_KEYS, J.MJ_STEPS, J.BLOCK, J.WAVE_SYNC,
@@ -147,18 +146,13 @@ def _deferred_drain(args, cols, split, approx, aggs, grouped, group_col, allslot
                               (hk.slots if hk is not None else [])))
     for sl in tail:
         J._uload(g, sl, "c", b, ind2)
-    gvar = "gic"
     if grouped:
-        base = args.add("q", "group_base", "long long")
-        ng = args.add("q", "num_groups", "long long")
-        b.append(f"{ind2}const i64 glc = (i64){J._rename(f'x{group_col}', allslots, 'c')} - {base};")
-        b.append(f"{ind2}cok = cok && {J._rename(g.ok(group_col), allslots, 'c')} && "
-                 f"glc >= 0 && glc < {ng};")
-        b.append(f"{ind2}const int {gvar} = cok ? (int)glc : 0;")
+        b += g.group_index(group_col, "c", "cok", ind2)
     if hk is not None:
         b += [J._rename(x, allslots, "c") for x in J.JH._hash_accumulate(g, aggs, hk, "cok", ind2)]
     else:
-        b += [J._rename(x, allslots, "c") for x in J._accumulate(g, aggs, grouped, "cok", gvar, ind2)]
+        b += [J._rename(x, allslots, "c")
+              for x in J._accumulate(g, aggs, grouped, "cok", "gic", ind2)]
     b += [f"{ind2}wcnt = cb;",
           f"{ind2}{J._wave_sync()}",
           f"{ind}}}"]
@@ -201,10 +195,8 @@ def gen_merge_join_agg(p: NL.JoinParams, compacts=None, hk=None) -> J.Kernel:
     BLOCK = J.MJ_BLOCK  # noqa: N806 — 64: one wavefront per workgroup, no block barriers
     T = BLOCK * NI  # noqa: N806
     LK = J.MJ_LDS_KEYS  # noqa: N806
-    args = J.Args()
-    for n, ct in (("rstart", "const long long*"), ("rlen", "const long long*"),
-                  ("tile_prefix", "const long long*"), ("spans", "const long long*")):
-        args.add("p", n, ct)
+    args = J._range_args(J.Args())
+    args.add("p", "spans", "const long long*")
     args.add("q", "R", "long long")
     args.add("q", "nrows", "long long")
     args.add("q", "rdup", "long long")
@@ -540,6 +532,7 @@ def gen_merge_join_agg(p: NL.JoinParams, compacts=None, hk=None) -> J.Kernel:
             b.append(f"{ind}ssC = ssN; seC = seN; ssN = ssNN; seN = seNN;")
 
     loads = J._vec_loads(g1, first)
+    st = J._Stream(args, cols, split, approx, NI, BLOCK)   # (the tile loops' geometry)
     if rpf:
         # the span registers and the first prefetch (tile t0), before the tile loop
         pre: List[str] = ["  i64 ssC = 0, seC = 0, ssN = 0, seN = 0;"]
@@ -555,24 +548,18 @@ def gen_merge_join_agg(p: NL.JoinParams, compacts=None, hk=None) -> J.Kernel:
         b += J._TILE_HEAD + pre
     if runs_pf:
         gi = "((G0 < a.nrows ? G0 : a.nrows - 1) >> 6)"
-        J._vec_tiles(b, T, NI, ind, loads,
-                   [("gm_", "unsigned long long", f"a.GM{lk}[{gi}]"),
-                    ("gr_", "int", f"a.GR{lk}[{gi}]")], body,
-                   [("ss", "i64", "a.spans[4 * ({t}) + 2]"), ("se", "i64", "a.spans[4 * ({t}) + 3]"),
-                    ("ra_", "int", "a.TR[2 * ({t})]"), ("nl_", "int", "a.TR[2 * ({t}) + 1]")])
+        J._vec_tiles(st, b, body, J._Tile(
+            loads,
+            [("gm_", "unsigned long long", f"a.GM{lk}[{gi}]"), ("gr_", "int", f"a.GR{lk}[{gi}]")],
+            [("ss", "i64", "a.spans[4 * ({t}) + 2]"), ("se", "i64", "a.spans[4 * ({t}) + 3]"),
+             ("ra_", "int", "a.TR[2 * ({t})]"), ("nl_", "int", "a.TR[2 * ({t}) + 1]")]))
     elif J.MJ_PREFETCH:
         # software-pipelined: tile t+1's left vectors are in flight during tile t's staging,
         # search and aggregate tail (the kernel waits on memory ~60% of its wave cycles:
         # profiles/pmc_merge_join_r3.txt)
-        J._vec_tiles(b, T, NI, ind, loads, [], body)
+        J._vec_tiles(st, b, body, J._Tile(loads))
     else:
-        if rpf:
-            b += ["  for (i64 t = t0; t < t1; ++t) {",
-                  "    while (r + 1 < (int)a.R && a.tile_prefix[r + 1] <= t) ++r;",
-                  f"    const i64 off = (t - a.tile_prefix[r]) * {T};"]
-            J._vec_rows(b, NI, ind)
-        else:
-            J._tile_loop(b, T, NI, 1, ind)
+        J._tile_loop(b, T, NI, 1, ind, head=not rpf)   # (rpf emitted the head with its prefetch)
         b.append(f"{ind}if (tb0 + {T} <= a.nrows) {{")
         J._vec_issue(b, loads, NI, ind, True)
         body(b, True)
@@ -588,11 +575,8 @@ def gen_merge_join_agg(p: NL.JoinParams, compacts=None, hk=None) -> J.Kernel:
                              "  ", final=True, hk=hk)
     if hk is None:
         b += J._flush(aggs, grouped, BLOCK)
-    src = (J._PRELUDE + args.struct_src() +
-           f'extern "C" __global__ __launch_bounds__({BLOCK}) void hs_jit_merge_join_agg(Args a) {{\n' +
-           "\n".join(b) + "\n}\n")
     lds = (len(aggs) * p.num_groups * 32) if grouped else 0
-    return J.Kernel(src, "hs_jit_merge_join_agg", args, lds, BLOCK)
+    return J._kernel("hs_jit_merge_join_agg", args, b, lds, block=BLOCK)
 
 
 def _runs_match(b: List[str], ind: str, g1: "_Gen", rk: int, rkv: str, rimg, NI: int,
@@ -669,12 +653,7 @@ def _eager_tail(args, cols, split, approx, aggs, grouped, group_col, allslots, r
         g = J._Gen(args, cols, split, (f"row{it}", "(ss + je)"), approx, True)
         gvar = f"gi{it}"
         if grouped:
-            base = args.add("q", "group_base", "long long")
-            ng = args.add("q", "num_groups", "long long")
-            b.append(f"{ind}  const i64 gl = (i64){J._rename(f'x{group_col}', allslots, it)} - {base};")
-            b.append(f"{ind}  pe = pe && {J._rename(g.ok(group_col), allslots, it)} && "
-                     f"gl >= 0 && gl < {ng};")
-            b.append(f"{ind}  const int {gvar} = pe ? (int)gl : 0;")
+            b += g.group_index(group_col, it, "pe", ind + "  ", ("gl", gvar))
             b += [J._rename(x, allslots, it) for x in _run_accumulate(g, aggs, "pe", gvar,
                                                                     ind + "  ")]
         else:
@@ -739,14 +718,9 @@ def merge_join_ok(p: NL.JoinParams, compacts=None, rnrows: int = 0, lnrows: int 
     left / right row indices that fit its int32 aggregate lists."""
     if J.MJ_ITEMS <= 0 or rnrows >= (1 << 31) or lnrows >= (1 << 31):
         return False
-    ptrs = []
     slots = [p.lkey] + J._pred_slots([(k, p.preds[k]) for k in range(p.nlp)]) + \
         [x for x in J._pred_slots([(k, p.preds[k]) for k in range(p.nlp, p.npreds)]) if x < 8]
-    for s in dict.fromkeys(slots):
-        c = (compacts or {}).get(s)
-        ptrs.append(c.codes.data_ptr() if c else p.cols[s].data)
-        ptrs.append(p.cols[s].valid)
-    return J._vec_aligned_ptrs(ptrs)
+    return J._vec_aligned_ptrs(J._col_ptrs(p, compacts, dict.fromkeys(slots)))
 
 
 def merge_join_agg(p: NL.JoinParams, rstart, rlen, rbucket, roff, compacts=None, nrows: int = 0,

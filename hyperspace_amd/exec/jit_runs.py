@@ -219,8 +219,7 @@ def tags2_shape(p: NL.JoinParams, compacts, W: int, ix32: bool = False, mode: st
                 prune: tuple = (), k16: bool = False, pair: bool = False) -> tuple:
     cols = tuple(sorted((s, c) for s, c in J._col_specs(p, compacts).items()
                         if s >= SPLIT or s == p.lkey))
-    preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
-                   p.preds[k].group) for k in range(p.nlp, p.npreds))
+    preds = J._preds_shape(p, p.nlp, p.npreds)
     return ("run_tags2", cols, preds, p.nlp, p.lkey, p.rkey, _tags_grouped(p) and p.group_col,
             W, RT2_UNROLL, J.BLOCK, ix32, mode, tuple(prune),
             bool(k16) and tags2_k16(p, compacts, ix32, mode),
@@ -287,16 +286,6 @@ def _tags_grouped(p: NL.JoinParams) -> bool:
     group (a single group's domain [group_base, group_base + 1) holds every value of the column,
     which is non-null here: ``applies``)."""
     return p.group_col >= SPLIT and p.num_groups > 1
-
-
-def _kernel(name: str, args: J.Args, body: List[str], lds: int = 0, tdefs=(),
-            attrs: str = "") -> J.Kernel:
-    """A generated kernel's translation unit: prelude, the ``Args`` struct as it stands now (so
-    after the last slot was added), file-scope typedefs, and ``body`` as the kernel function."""
-    src = (J._PRELUDE + args.struct_src() + "".join(t + "\n" for t in tdefs) +
-           f'extern "C" __global__ __launch_bounds__({J.BLOCK}){attrs} void {name}(Args a) {{\n' +
-           "\n".join(body) + "\n}\n")
-    return J.Kernel(src, name, args, lds)
 
 
 # Which phase-1 kernel is generated, resolved once (``_tags_form``): its name; the run /
@@ -960,7 +949,7 @@ def gen_run_tags2(p: NL.JoinParams, compacts, W: int, ix32: bool = False,
     else:
         b = s.images() + s.prologue() + s.seek() + \
             (s.block_loop() if s.f.wide == 4 else s.group_loop())
-    return _kernel(s.f.name, s.args, b, tdefs=s.vec_types() if s.f.wide == 4 else ())
+    return J._kernel(s.f.name, s.args, b, tdefs=s.vec_types() if s.f.wide == 4 else ())
 
 
 def copy_ok(p: NL.JoinParams, compacts) -> bool:
@@ -1009,7 +998,7 @@ def gen_match_gather(p: NL.JoinParams, compacts) -> J.Kernel:
             vp = args.add("p", f"SV{sl}", "unsigned char*")
             b.append(f"    {vp}[i] = {g.vptr(sl)}[j_];")
     b.append("  }")
-    return _kernel("hs_jit_match_gather", args, b)
+    return J._kernel("hs_jit_match_gather", args, b)
 
 
 def copy_matches(p: NL.JoinParams, compacts, m, vt: dict, dev) -> tuple:
@@ -1087,8 +1076,7 @@ def run_ranges(rstart, rlen, rbucket, roff, runs):
 
 def scan_shape(p: NL.JoinParams, compacts, W: int, NI: int) -> tuple:
     cols = tuple(sorted((s, c) for s, c in J._col_specs(p, compacts).items() if s < SPLIT))
-    preds = tuple((p.preds[k].kind, p.preds[k].op, p.preds[k].col, p.preds[k].col2,
-                   p.preds[k].group) for k in range(p.nlp))
+    preds = J._preds_shape(p, 0, p.nlp)
     aggs = tuple((p.aggs[i].kind, p.aggs[i].nterms, tuple(p.aggs[i].col[:p.aggs[i].nterms]))
                  for i in range(p.naggs))
     return ("run_scan", cols, preds, aggs, p.group_col, p.lkey, W, NI, J.BLOCK, J.WAVE_SYNC,
@@ -1113,21 +1101,19 @@ def gen_run_scan(p: NL.JoinParams, compacts, W: int, NI: int) -> J.Kernel:
     tail = J._agg_slots(aggs) + ([p.group_col] if grouped and not rgroup else [])
     allslots = list(dict.fromkeys(pslots + tail))
     approx = J._sum_only_slots(lpreds, aggs, p.group_col if grouped and not rgroup else -1, cols)
-    BLOCK = J.BLOCK  # noqa: N806
-    T = BLOCK * NI  # noqa: N806
     MASK = (1 << W) - 1  # noqa: N806
     KW = ((31 + (NI - 1) * W) >> 5) + 1  # noqa: N806 — tag words a thread's rows can touch
-    ind = "    "
-    g1 = J._Gen(args, cols, SPLIT, ("row0", "row0"), approx, True)
+    st = J._Stream(args, cols, SPLIT, approx, NI)
+    ind = st.ind
+    g1 = st.gen("row0")
     b: List[str] = []
     b += J._acc_decls(aggs, grouped, args)
 
     def body(b: List[str], full: bool) -> None:
         J._vec_load_slots(b, g1, pslots, NI, ind)
         for it in range(NI):
-            gi = J._Gen(args, cols, SPLIT, (f"row{it}", f"row{it}"), approx, True)
             b.append(f"{ind}bool pass{it} = act{it} && "
-                     f"{J._rename(gi.cnf(lpreds), allslots, it)};")
+                     f"{J._rename(st.gen(f'row{it}').cnf(lpreds), allslots, it)};")
         # row -> run: the thread's NI rows lie in one 64-row group (NI | 64, g0 % NI == 0)
         b += [f"{ind}const int sh_ = (int)(g0 & 63);",
               f"{ind}const i64 r0_ = (i64)gr_ + (i64)__popcll(gm_ & ((2ull << sh_) - 2ull));",
@@ -1144,27 +1130,25 @@ def gen_run_scan(p: NL.JoinParams, compacts, W: int, NI: int) -> J.Kernel:
             b += [f"{ind}  const unsigned tg = ({sel} >> (unsigned)(rel & 31)) & {MASK}u;",
                   f"{ind}  pass{it} = pass{it} && tg != 0u;",
                   f"{ind}  jg{it} = (int)tg - 1; }}"]
-        b.extend(J._compacted_tail(args, cols, SPLIT, approx, aggs, grouped, p.group_col,
-                                   tail, allslots, NI, ind, with_j=rgroup, j_fmt="jg{it}",
-                                   jgroup=rgroup))
+        b.extend(J._compacted_tail(st, aggs, p.group_col if grouped else -1, allslots,
+                                   J._Tail(with_j=rgroup, j_fmt="jg{it}", jgroup=rgroup)))
 
     def body_decl(b: List[str], full: bool) -> None:
         b.append(f"{ind}int " + ", ".join(f"jg{it} = 0" for it in range(NI)) + ";")
         body(b, full)
 
     gi = "((G0 < a.nrows ? G0 : a.nrows - 1) >> 6)"
-    J._vec_tiles(b, T, NI, ind, J._vec_loads(g1, pslots),
-                 [("gm_", "unsigned long long", f"a.GM{lk}[{gi}]"),
-                  ("gr_", "int", f"a.GR{lk}[{gi}]")], body_decl)
+    J._vec_tiles(st, b, body_decl, J._Tile(
+        J._vec_loads(g1, pslots),
+        [("gm_", "unsigned long long", f"a.GM{lk}[{gi}]"), ("gr_", "int", f"a.GR{lk}[{gi}]")]))
     b += ["  }"]
     b += J._flush(aggs, grouped)
-    Wv = BLOCK // 64  # noqa: N806
-    pre = [f"  typedef {J._crow_t(T)} crow_t; __shared__ crow_t crow_s[{Wv}][{64 * NI}];",
-           "  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;"]
+    Wv = J.BLOCK // 64  # noqa: N806
+    st.lds += [f"  typedef {J._crow_t(st.T)} crow_t; __shared__ crow_t crow_s[{Wv}][{64 * NI}];",
+               "  const int cln = threadIdx.x & 63, wv = threadIdx.x >> 6;"]
     if rgroup:
-        pre.append(f"  __shared__ int cj_s[{Wv}][{64 * NI}];")
-    return _kernel("hs_jit_run_scan", args, pre + b,
-                   (len(aggs) * p.num_groups * 32) if grouped else 0)
+        st.lds.append(f"  __shared__ int cj_s[{Wv}][{64 * NI}];")
+    return st.finish("hs_jit_run_scan", b, (len(aggs) * p.num_groups * 32) if grouped else 0)
 
 
 # phase 2 for 1-bit tags: masks 64 rows at a time (gen_run_sparse_scan; RS_BITS), aggregate
@@ -1514,7 +1498,7 @@ class _BitsScan:
             self.issue.append(
                 f"    bload<24>(hs_rsrc((const char*){pp} + (tbC >> 6) * 96, "
                 f"@LIVE@((a.nrows + 63 - tbC) >> 6) * 96), (unsigned)(ln * 96), x{sl}q@S@);")
-        for name, ct, ptr in ([] if f.p12 or f.cand else J._vec_loads(self.g1, self.pslots)):
+        for name, ct, ptr, *_ in ([] if f.p12 or f.cand else J._vec_loads(self.g1, self.pslots)):
             es = J._SIZEOF[ct]
             nw = 64 * es // 4
             per = 4 // es
@@ -1889,13 +1873,7 @@ class _BitsScan:
             w.append(f"{ind2}{{ bool cok = cok{k};")
             gvar = "gic"
             if f.grouped:
-                base = args.add("q", "group_base", "long long")
-                ng = args.add("q", "num_groups", "long long")
-                w.append(f"{ind2}const i64 glc = (i64){J._rename(f'x{p.group_col}', tail, it)} - "
-                         f"{base};")
-                w.append(f"{ind2}cok = cok && {J._rename(g.ok(p.group_col), tail, it)} && "
-                         f"glc >= 0 && glc < {ng};")
-                w.append(f"{ind2}const int {gvar} = cok ? (int)glc : 0;")
+                w += g.group_index(p.group_col, it, "cok", ind2, ("glc", gvar))
             if self.hk is not None:
                 w += [J._rename(x, tail, it)
                       for x in JH._hash_accumulate(g, self.aggs, self.hk, "cok", ind2, tk=tk,
@@ -2180,8 +2158,8 @@ def gen_run_sparse_scan(p: NL.JoinParams, compacts, hk=None, tk=None,
     # accumulators and mask; the union path alone fits six (73) - so five stays)
     waves = RS_WAVES or (5 if s.f.pair else 0)
     occ = f" __attribute__((amdgpu_waves_per_eu({waves}, {waves})))" if waves else ""
-    return _kernel(s.f.name, s.args, b, (len(s.aggs) * p.num_groups * 32) if s.f.grouped else 0,
-                   attrs=occ)
+    return J._kernel(s.f.name, s.args, b, (len(s.aggs) * p.num_groups * 32) if s.f.grouped else 0,
+                     attrs=occ)
 
 
 class TwoPhaseLauncher:

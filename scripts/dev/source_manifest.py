@@ -1,6 +1,6 @@
-"""What the generated-source manifests (``bits_scan_manifest.py``, ``tags2_manifest.py``) share:
-importing the tree under test, the per-case record, the enumeration into a manifest and its file
-form.
+"""What the generated-source manifests (``bits_scan_manifest.py``, ``tags2_manifest.py``,
+``stream_manifest.py``) share: importing the tree under test, the per-case record, the
+enumeration into a manifest and its file form.
 
 Per case the kernel name, sha1 of the source, sha1 of ``repr(args.slots)`` and ``lds_bytes`` - or
 ``!<exception type>`` if generation raises, or null where the form does not apply under the
